@@ -13,6 +13,11 @@ episode turnover the reference's loop performs: `reset` of finished episodes -- 
 device-resident pool of generated scenes (HOPE_AUTO_REDRAW; `--same-map`: on the same map) -- and its action-less
 observation step, fused into the step kernel (HOPE_AUTO_RESET).  Inputs (scene tiles, the scene pool, actions) are
 resident in HBM when the timed region starts.  Independent scenes shard over ranks with no data-path collective.
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line.  `--full` adds everything else the line can
+carry: per-kernel event timings and the rooflines, the longer repeat passes (value_steady / value_joined), the oracle witness
+(parity_check), the queue check and the CPU baseline.  `--dump-outputs DIR` writes the outputs of the last timed step as
+DIR/<name>.npy; with the same arguments the inputs, the pool refresh included, are the same in every run.
 """
 import argparse
 import json
@@ -55,7 +60,8 @@ def parse():
                          '(scene_gen.PoolRefresher: the native generator fills pinned staging on host threads, an asynchronous upload swaps the '
                          'pool in): the step loop polls it every this many steps, inside the timed region.  -1 (default) = at the rate the '
                          'batch consumes the pool: about 0.45 %% of the scenes draw a generated lot per step, so a pool of P lots is used up '
-                         'after P / (0.0045 N) steps (28 steps at 65 536 scenes and 8 192 lots; never below 8); 0 = a static pool')
+                         'after P / (0.0045 N) steps (28 steps at 65 536 scenes and 8 192 lots; never below 8); 0 = a static pool.  The '
+                         'schedule is fixed: one fill per period, committed at its end for the next step to draw from')
     ap.add_argument('--overlap', default='auto', choices=['auto', 'on', 'off'],
                     help='launch chains of the two tile classes on two streams (auto = on)')
     ap.add_argument('--refresh-threads', type=int, default=2, help='worker threads of the background pool refill (native generator)')
@@ -71,6 +77,12 @@ def parse():
                     help='--policy hope: stock levers on the inference forward of the rollout -- graph: captured device graph '
                          '(same fp32 results); amp: bf16 autocast on the token mixer and embedding MLPs (changes the policy\'s '
                          'numerics); reported next to the fp32 eager default')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: per-kernel event timings and rooflines, '
+                         '--repeat-passes, the --witness oracle check, the queue check and the CPU baseline (all off without it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the outputs of the last one (rank 0) as DIR/<name>.npy in float32 / float64; '
+                         'above 64 MB in all, the same seeded sample of scene rows of every output (DIR/scene_index.npy)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-scenes', type=int, default=2048)
     ap.add_argument('--cpu-steps', type=int, default=12)
@@ -88,16 +100,16 @@ def parse():
                          'enqueued (reported next to `value` as value_joined)')
     ap.add_argument('--witness', type=int, default=1024,
                     help='after the timed region: this many random scene slots of the TIMED configuration are rebuilt in the CPU '
-                         'oracle from the state on the device and one more fused step is compared (parity_check); 0 = off')
+                         'oracle from the state on the device and one more fused step is compared (parity_check); 0 = off.  With --full')
     ap.add_argument('--repeat-passes', type=int, default=5,
                     help='extra passes of --repeat-steps steps after the timed region (outside the driver-timed K steps): '
-                         'their run-to-run spread and the steady-state episode population are reported')
+                         'their run-to-run spread and the steady-state episode population are reported.  With --full')
     ap.add_argument('--repeat-steps', type=int, default=200)
     ap.add_argument('--preroll', type=int, default=300,
                     help='untimed steps of SETUP before the W warm-up steps that bring the batch to its stationary episode '
                          'population: every episode first gets a random age t ~ U[1, 200] (fresh episodes all time out together '
                          'at t = 201, and for their first steps fewer of them pass the Reeds-Shepp gate, so K steps timed right '
-                         'after a reset ran ~5 % faster than the loop ever runs again), then this many steps run.  The driver-timed '
+                         'after a reset ran ~5 %% faster than the loop ever runs again), then this many steps run.  The driver-timed '
                          '`value` is then the steady-state number (`repeat` cross-checks it).  0 = time fresh episodes')
     return ap.parse_args()
 
@@ -184,7 +196,7 @@ def main():
 
     overlap = {'auto': None, 'on': True, 'off': False}[args.overlap]
     env = ParkingBatch(N, args.max_obst, device=str(dev), obs_dtype=torch.float32, action_dtype=torch.float32,
-                       profile=True, image=args.image, overlap=overlap)
+                       profile=args.full, image=args.image, overlap=overlap)
     chunk = 8192
     for a in range(0, N, chunk):
         b = min(N, a + chunk)
@@ -235,13 +247,23 @@ def main():
             args.refresh_every = max(8, int(args.pool / (0.0045 * N)))
         if gl and args.refresh_every > 0 and args.policy == 'none':
             from hope_amd.scene_gen import PoolRefresher
-            bench_refresher = PoolRefresher(env, args.pool, levels=gl, seed=(args.seed + rank) * 31 + 5, relaxed=True, threads=args.refresh_threads)
+            # strict commits (relaxed=False): the step after a commit draws from the new lots, whatever the timing, so every run with
+            # the same arguments draws the same maps (a relaxed swap lands on whichever step is enqueued after its upload finished)
+            bench_refresher = PoolRefresher(env, args.pool, levels=gl, seed=(args.seed + rank) * 31 + 5, relaxed=False, threads=args.refresh_threads)
+        n_stepped = [0]                                       # steps enqueued so far (pre-roll, warm-up, timed, ...): the refresh schedule's clock
 
         def one_step(i, defer_=None):  # noqa: F811
             # the new map is drawn inside the step kernel (HOPE_AUTO_REDRAW = step + redraw(done) + reset_obs(active=done))
             env.step(act_bank[i % len(act_bank)], stages=stages, auto_reset=True, fresh=True, defer_rs=defer if defer_ is None else defer_)
-            if bench_refresher is not None and i % args.refresh_every == 0:
-                bench_refresher.poll()                        # never blocks: commits a finished batch of new lots, starts the next fill
+            if bench_refresher is not None:
+                # one fill per period of --refresh-every steps, committed at the period's end: batch b of new lots is always the b-th
+                # commit.  The fill starts as soon as the staging is free (no wait), from half the period on it waits for it.
+                ph = n_stepped[0] % args.refresh_every
+                if ph == 0 and bench_refresher.thread is not None:
+                    bench_refresher.poll(wait=True)
+                if bench_refresher.thread is None:
+                    bench_refresher.start_fill(block=ph >= args.refresh_every // 2)
+            n_stepped[0] += 1
 
     trainer = None
     if args.policy == 'hope':
@@ -271,11 +293,12 @@ def main():
                     set_img_amp(net, True)
         one_step = lambda i, defer_=None: trainer.step()  # noqa: E731
 
-    # HIP events bracket the launches of the kernel the roofline is stated for, live in the timed region; timing EVERY
+    # --full: HIP events bracket the launches of the kernel the roofline is stated for, live in the timed region; timing EVERY
     # launch costs ~4 % of the step in launch latency (16 event records per step), so the other kernels are timed in a
-    # short separate pass after it (ms_per_bench_step_by_kernel)
+    # short separate pass after it (ms_per_bench_step_by_kernel).  A plain run records no events.
     dom = 'k_bev_image' if args.image else 'k_env_step'
-    env.profile_kernels([dom])
+    if args.full:
+        env.profile_kernels([dom])
     if trainer is None:
         env.reset_obs(stages=stages)
         if args.preroll > 0:
@@ -295,8 +318,9 @@ def main():
         one_step(i)
     torch.cuda.synchronize(dev)
     commits0 = bench_refresher.commits if bench_refresher is not None else 0
-    env.kernel_union_ms(reset=True)
-    env.kernel_ms(reset=True)
+    if args.full:
+        env.kernel_union_ms(reset=True)
+        env.kernel_ms(reset=True)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -309,21 +333,24 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     commits_timed = (bench_refresher.commits - commits0) if bench_refresher is not None else 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, args.seed)
     n_break = min(args.steps, 10)
-    dom_union = env.kernel_union_ms(reset=True)[dom]
-    dom_stats = env.kernel_ms(reset=True)[dom]
-    env.profile_kernels(None)
-    for i in range(n_break):
-        one_step(args.warmup + args.steps + i)
-    torch.cuda.synchronize(dev)
-    env.kernel_union_ms(reset=True)
-    kstats = env.kernel_ms(reset=True)
+    if args.full:
+        dom_union = env.kernel_union_ms(reset=True)[dom]
+        dom_stats = env.kernel_ms(reset=True)[dom]
+        env.profile_kernels(None)
+        for i in range(n_break):
+            one_step(args.warmup + args.steps + i)
+        torch.cuda.synchronize(dev)
+        env.kernel_union_ms(reset=True)
+        kstats = env.kernel_ms(reset=True)
     done_frac = float(env.done.float().mean().item())
     rs_found = float((env.rs_word[:, 6] > 0).float().mean().item())
     # ---- outside the driver-timed K steps: run-to-run spread over longer passes (SURVEY.md §8(d) asks for >= 200 timed steps,
     # median of 5; the driver's command fixes K), at the episode population those passes converge to (OUTTIME needs t > 200)
     repeat = None
-    if args.repeat_passes > 0 and trainer is None:
+    if args.full and args.repeat_passes > 0 and trainer is None:
         env.profile_kernels([dom])                           # the configuration of the timed region
         ms = []
         dsum = 0.0
@@ -356,7 +383,7 @@ def main():
         bench_refresher.close()
     # ---- in-run correctness witness of exactly this configuration (after all timing)
     parity = None
-    if args.witness > 0 and trainer is None and rank == 0:
+    if args.full and args.witness > 0 and trainer is None and rank == 0:
         parity = parity_witness(env, stages, fresh, act_bank[3], args.witness, args.seed + 1234)
     rank_ms = [elapsed / args.steps * 1e3]
     rccl = None
@@ -382,90 +409,91 @@ def main():
     if rank == 0:
         total_scenes = N * world if args.scaling == 'weak' else args.scenes
         value = total_scenes * args.steps / elapsed
-        # HIP events recorded by the library on the launch stream: around every launch of the roofline kernel inside the
-        # timed region (dom_stats), around every launch of every kernel in the short pass after it (kstats).
-        # `kernel_ms` is the roofline kernel's AVERAGE LAUNCH duration over the timed region (directly comparable with
-        # rocprofv3's AverageNs: k_env_step is launched per tile class -- from 16 384 scenes on as two launches each, the
-        # motion half and the observation half (template instantiations PART 1 / 2, two rows in rocprof's table) -- i.e. 4
-        # launches per bench step at the default size; the average is over all of them);
-        # `algorithmic bytes per launch` is averaged over the same launches, so achieved = bytes/launch / kernel_ms.
-        per_step = {k: v[0] / max(n_break, 1) for k, v in kstats.items()}
-        # The roofline is stated for the kernel that moves the algorithmic bytes of §8(d): k_env_step (k_rs_validate
-        # takes about the same time but only re-reads obstacle tiles); with --image it is k_bev_image, which is then
-        # also the largest by time.  `largest_by_time` is reported next to it.
-        largest = max(per_step, key=per_step.get) if per_step else None
-        dom_total_ms, dom_launches = dom_stats
-        dom_ms = dom_total_ms / max(dom_launches, 1)
-        bytes_avg_launch = bytes_per_launch * args.steps / max(dom_launches, 1)
-        achieved = bytes_avg_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # Memory-side traffic and instruction counts are NOT measured in this run: they come from the PMC passes committed
-        # under profiles/ (tools/collect_profiles.sh: separate rocprofv3 --pmc passes of this same command) and are
-        # labelled as such.  They describe the default workload only.
-        default_workload = (N == 65536 and args.mix == 'mixed' and args.stages == 'all' and trainer is None and fresh)
-        traffic = traffic_source = None
-        pmc = next((q for q in (os.path.join(ROOT, 'profiles', f'{r}_pmc_traffic{"_image" if args.image else ""}.json') for r in ('r06', 'r05', 'r04'))
-                    if os.path.exists(q)), '')
-        if os.path.exists(pmc) and default_workload:
+        if args.full:
+            # HIP events recorded by the library on the launch stream: around every launch of the roofline kernel inside the
+            # timed region (dom_stats), around every launch of every kernel in the short pass after it (kstats).
+            # `kernel_ms` is the roofline kernel's AVERAGE LAUNCH duration over the timed region (directly comparable with
+            # rocprofv3's AverageNs: k_env_step is launched per tile class -- from 16 384 scenes on as two launches each, the
+            # motion half and the observation half (template instantiations PART 1 / 2, two rows in rocprof's table) -- i.e. 4
+            # launches per bench step at the default size; the average is over all of them);
+            # `algorithmic bytes per launch` is averaged over the same launches, so achieved = bytes/launch / kernel_ms.
+            per_step = {k: v[0] / max(n_break, 1) for k, v in kstats.items()}
+            # The roofline is stated for the kernel that moves the algorithmic bytes of §8(d): k_env_step (k_rs_validate
+            # takes about the same time but only re-reads obstacle tiles); with --image it is k_bev_image, which is then
+            # also the largest by time.  `largest_by_time` is reported next to it.
+            largest = max(per_step, key=per_step.get) if per_step else None
+            dom_total_ms, dom_launches = dom_stats
+            dom_ms = dom_total_ms / max(dom_launches, 1)
+            bytes_avg_launch = bytes_per_launch * args.steps / max(dom_launches, 1)
+            achieved = bytes_avg_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # Memory-side traffic and instruction counts are NOT measured in this run: they come from the PMC passes committed
+            # under profiles/ (tools/collect_profiles.sh: separate rocprofv3 --pmc passes of this same command) and are
+            # labelled as such.  They describe the default workload only.
+            default_workload = (N == 65536 and args.mix == 'mixed' and args.stages == 'all' and trainer is None and fresh)
+            traffic = traffic_source = None
+            pmc = next((q for q in (os.path.join(ROOT, 'profiles', f'{r}_pmc_traffic{"_image" if args.image else ""}.json') for r in ('r06', 'r05', 'r04'))
+                        if os.path.exists(q)), '')
+            if os.path.exists(pmc) and default_workload:
+                try:
+                    traffic = json.load(open(pmc))['kernels'][dom]['hbm_bytes']
+                    traffic_source = 'static: ' + os.path.relpath(pmc, ROOT) + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, per launch)'
+                except Exception:
+                    traffic = None
+            # Instruction-issue roofline (every kernel here is VALU-issue / latency bound, none is HBM bound), MIX-WEIGHTED: the issue
+            # rate of a wave64 VALU instruction depends on its class -- measured on this GPU type by tools/valu_rate.py
+            # (profiles/r03_valu_rates.json): float64 add / mul / fma ~4.4e11 wave-instructions/s chip-wide, float64 rcp / sqrt
+            # ~1.5e11, plain 32-bit ALU ops ~7.7e11 -- and the per-kernel instruction counts by class come from the committed
+            # rocprofv3 --pmc pass of this command (SQ_INSTS_VALU, SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64).  floor = sum over classes
+            # of count / rate; frac = floor / measured time.  Counts are static (labelled), the step time is this run's.
+            valu = None
+            sq = next((q for q in (os.path.join(ROOT, 'profiles', f'{r}_sq_counters.json') for r in ('r06', 'r05', 'r04')) if os.path.exists(q)), '')
+            vr = os.path.join(ROOT, 'profiles', 'r03_valu_rates.json')
+            if os.path.exists(sq) and os.path.exists(vr) and default_workload and not args.image:
+                try:
+                    sqd = json.load(open(sq))
+                    ceil = json.load(open(vr))['ceilings']
+                    r64, rtr, r32 = ceil['f64_arith_wave_insts_per_s'], ceil['f64_trans_wave_insts_per_s'], ceil['other_valu_wave_insts_per_s']
+                    per_kernel, floor_s, insts = {}, 0.0, 0.0
+                    for kname, c in sqd['kernels'].items():
+                        v = c.get('SQ_INSTS_VALU', 0.0)
+                        f64 = c.get('SQ_INSTS_VALU_ADD_F64', 0.0) + c.get('SQ_INSTS_VALU_MUL_F64', 0.0) + c.get('SQ_INSTS_VALU_FMA_F64', 0.0)
+                        tr = c.get('SQ_INSTS_VALU_TRANS_F64', 0.0)
+                        fl = f64 / r64 + tr / rtr + max(v - f64 - tr, 0.0) / r32
+                        nl = c.get('launches_per_bench_step', 1)
+                        per_kernel[kname] = {'valu_insts_per_launch': v, 'f64_share': (f64 + tr) / v if v else None, 'launches_per_bench_step': nl,
+                                             'floor_ms_per_bench_step': fl * nl * 1e3}
+                        floor_s += fl * nl
+                        insts += v * nl
+                    # (k_obs_pair / k_motion_pair -- the small-tile class's observation / motion launch, two scenes per wave -- are launches of the step kernel to the
+                    # library's event timers: its floor is compared with k_env_step's event time together with k_env_step's own)
+                    grp = lambda k: 'k_env_step' if k in ('k_obs_pair', 'k_motion_pair') else k  # noqa: E731
+                    for kname in per_kernel:
+                        fl_g = sum(q['floor_ms_per_bench_step'] for k2, q in per_kernel.items() if grp(k2) == grp(kname))
+                        t_meas = per_step.get(grp(kname), 0.0)
+                        per_kernel[kname]['frac_of_its_own_event_time'] = fl_g / t_meas if t_meas > 0 else None
+                    valu = {'valu_insts_per_bench_step': insts, 'mix_weighted_floor_ms_per_step': floor_s * 1e3,
+                            'frac': floor_s / (elapsed / args.steps), 'rates_wave_insts_per_s': {'f64_arith': r64, 'f64_trans': rtr, 'other': r32},
+                            'per_kernel': per_kernel,
+                            'source': 'static instruction counts by class: ' + os.path.relpath(sq, ROOT) + ' (rocprofv3 --pmc passes of this command); '
+                                      'issue rates: profiles/r03_valu_rates.json (tools/valu_rate.py on the same GPU type); step and kernel times: this run. '
+                                      'A single wave issues at most one instruction per ~8-10 cycles, so a kernel needs >= 4 waves per SIMD to reach these rates.'}
+                except Exception:
+                    valu = None
+            # the box's own streaming ceiling next to the 8 TB/s vendor peak: device-to-device copy of 1 GiB
+            copy_gbps = None
             try:
-                traffic = json.load(open(pmc))['kernels'][dom]['hbm_bytes']
-                traffic_source = 'static: ' + os.path.relpath(pmc, ROOT) + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, per launch)'
-            except Exception:
-                traffic = None
-        # Instruction-issue roofline (every kernel here is VALU-issue / latency bound, none is HBM bound), MIX-WEIGHTED: the issue
-        # rate of a wave64 VALU instruction depends on its class -- measured on this GPU type by tools/valu_rate.py
-        # (profiles/r03_valu_rates.json): float64 add / mul / fma ~4.4e11 wave-instructions/s chip-wide, float64 rcp / sqrt
-        # ~1.5e11, plain 32-bit ALU ops ~7.7e11 -- and the per-kernel instruction counts by class come from the committed
-        # rocprofv3 --pmc pass of this command (SQ_INSTS_VALU, SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64).  floor = sum over classes
-        # of count / rate; frac = floor / measured time.  Counts are static (labelled), the step time is this run's.
-        valu = None
-        sq = next((q for q in (os.path.join(ROOT, 'profiles', f'{r}_sq_counters.json') for r in ('r06', 'r05', 'r04')) if os.path.exists(q)), '')
-        vr = os.path.join(ROOT, 'profiles', 'r03_valu_rates.json')
-        if os.path.exists(sq) and os.path.exists(vr) and default_workload and not args.image:
-            try:
-                sqd = json.load(open(sq))
-                ceil = json.load(open(vr))['ceilings']
-                r64, rtr, r32 = ceil['f64_arith_wave_insts_per_s'], ceil['f64_trans_wave_insts_per_s'], ceil['other_valu_wave_insts_per_s']
-                per_kernel, floor_s, insts = {}, 0.0, 0.0
-                for kname, c in sqd['kernels'].items():
-                    v = c.get('SQ_INSTS_VALU', 0.0)
-                    f64 = c.get('SQ_INSTS_VALU_ADD_F64', 0.0) + c.get('SQ_INSTS_VALU_MUL_F64', 0.0) + c.get('SQ_INSTS_VALU_FMA_F64', 0.0)
-                    tr = c.get('SQ_INSTS_VALU_TRANS_F64', 0.0)
-                    fl = f64 / r64 + tr / rtr + max(v - f64 - tr, 0.0) / r32
-                    nl = c.get('launches_per_bench_step', 1)
-                    per_kernel[kname] = {'valu_insts_per_launch': v, 'f64_share': (f64 + tr) / v if v else None, 'launches_per_bench_step': nl,
-                                         'floor_ms_per_bench_step': fl * nl * 1e3}
-                    floor_s += fl * nl
-                    insts += v * nl
-                # (k_obs_pair / k_motion_pair -- the small-tile class's observation / motion launch, two scenes per wave -- are launches of the step kernel to the
-                # library's event timers: its floor is compared with k_env_step's event time together with k_env_step's own)
-                grp = lambda k: 'k_env_step' if k in ('k_obs_pair', 'k_motion_pair') else k  # noqa: E731
-                for kname in per_kernel:
-                    fl_g = sum(q['floor_ms_per_bench_step'] for k2, q in per_kernel.items() if grp(k2) == grp(kname))
-                    t_meas = per_step.get(grp(kname), 0.0)
-                    per_kernel[kname]['frac_of_its_own_event_time'] = fl_g / t_meas if t_meas > 0 else None
-                valu = {'valu_insts_per_bench_step': insts, 'mix_weighted_floor_ms_per_step': floor_s * 1e3,
-                        'frac': floor_s / (elapsed / args.steps), 'rates_wave_insts_per_s': {'f64_arith': r64, 'f64_trans': rtr, 'other': r32},
-                        'per_kernel': per_kernel,
-                        'source': 'static instruction counts by class: ' + os.path.relpath(sq, ROOT) + ' (rocprofv3 --pmc passes of this command); '
-                                  'issue rates: profiles/r03_valu_rates.json (tools/valu_rate.py on the same GPU type); step and kernel times: this run. '
-                                  'A single wave issues at most one instruction per ~8-10 cycles, so a kernel needs >= 4 waves per SIMD to reach these rates.'}
-            except Exception:
-                valu = None
-        # the box's own streaming ceiling next to the 8 TB/s vendor peak: device-to-device copy of 1 GiB
-        copy_gbps = None
-        try:
-            src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-            dst = torch.empty_like(src)
-            dst.copy_(src)
-            torch.cuda.synchronize(dev)
-            tc = time.perf_counter()
-            for _ in range(10):
+                src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+                dst = torch.empty_like(src)
                 dst.copy_(src)
-            torch.cuda.synchronize(dev)
-            copy_gbps = 10 * 2 * src.numel() * 4 / (time.perf_counter() - tc) / 1e9
-            del src, dst
-        except Exception:
-            pass
+                torch.cuda.synchronize(dev)
+                tc = time.perf_counter()
+                for _ in range(10):
+                    dst.copy_(src)
+                torch.cuda.synchronize(dev)
+                copy_gbps = 10 * 2 * src.numel() * 4 / (time.perf_counter() - tc) / 1e9
+                del src, dst
+            except Exception:
+                pass
         result = {
             'metric': 'parallel env steps/sec (full CarParking step incl. obs + RS search)', 'value': value,
             'unit': 'env-steps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -487,36 +515,37 @@ def main():
                                             if fresh else 'restart on the same map, fused into the step (HOPE_AUTO_RESET)'),
                        'host_generator_scenes_per_s': gen_rate,
                        'timed_window': f'{args.steps} steps between two synchronisations: `value` includes one pipeline fill and drain (the last '
-                                       'step\'s search chain runs out after its observation); value_steady is the same loop over '
-                                       f'{args.repeat_steps}-step passes',
-                       'done_frac_last': done_frac, 'rs_found_frac_last': rs_found},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
-                         'frac': achieved / 8000.0, 'traffic': traffic, 'traffic_source': traffic_source, 'kernel': dom,
-                         'largest_by_time': largest,
-                         'concurrent_launches': ('the launch chains of the two obstacle-tile classes run on two streams: the '
-                                                 'k_env_step launches overlap each other and the other class\'s kernels, so '
-                                                 'per-launch durations include that sharing; from 16 384 scenes on k_env_step is '
-                                                 'two launches per class (motion half, then the observation half on its own stream '
-                                                 'next to the Reeds-Shepp kernels); the small-tile class\'s two halves are the '
-                                                 'two-scenes-per-wave forms k_motion_pair / k_obs_pair (their own rows in rocprof\'s table; the library\'s event '
-                                                 'timers and this average count them as launches of the step kernel: profiles/*_kernel_stats_top.txt '
-                                                 'ends with the combined row)') if env.overlap else None,
-                         # the same kernel per step CALL: all its launches' bytes over the time during which at least one of them
-                         # ran (the union of the launch intervals) -- what the kernel sustains while its launches overlap
-                         'per_call': {'kernel_ms': dom_union[0] / max(dom_union[1], 1), 'calls': dom_union[1],
-                                      'achieved': bytes_per_launch * args.steps / max(dom_union[1], 1) / (dom_union[0] / max(dom_union[1], 1) * 1e-3) / 1e9 if dom_union[0] > 0 else None,
-                                      'frac': bytes_per_launch * args.steps / max(dom_union[1], 1) / (dom_union[0] / max(dom_union[1], 1) * 1e-3) / 1e9 / 8000.0 if dom_union[0] > 0 else None},
-                         'whole_step': {'achieved': bytes_per_launch / (elapsed / args.steps) / 1e9, 'unit': 'GB/s',
-                                        'frac': bytes_per_launch / (elapsed / args.steps) / 1e9 / 8000.0,
-                                        'note': 'algorithmic bytes of one bench step / driver-timed step'},
-                         'valu_issue': valu,
-                         'measured_copy_GBps': copy_gbps,
-                         'kernel_ms': dom_ms, 'kernel_launches': dom_launches,
-                         'algorithmic_bytes_per_launch': bytes_avg_launch,
-                         'algorithmic_bytes_per_bench_step': bytes_per_launch,
-                         'ms_per_bench_step_by_kernel': per_step, 'breakdown_steps': n_break},
+                                       'step\'s search chain runs out after its observation)' + (
+                                           f'; value_steady is the same loop over {args.repeat_steps}-step passes' if repeat is not None else ''),
+                       'done_frac_last': done_frac, 'rs_found_frac_last': rs_found, 'full': args.full},
         }
-        result['repeat'] = repeat
+        if args.full:
+            result['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
+                                  'frac': achieved / 8000.0, 'traffic': traffic, 'traffic_source': traffic_source, 'kernel': dom,
+                                  'largest_by_time': largest,
+                                  'concurrent_launches': ('the launch chains of the two obstacle-tile classes run on two streams: the '
+                                                          'k_env_step launches overlap each other and the other class\'s kernels, so '
+                                                          'per-launch durations include that sharing; from 16 384 scenes on k_env_step is '
+                                                          'two launches per class (motion half, then the observation half on its own stream '
+                                                          'next to the Reeds-Shepp kernels); the small-tile class\'s two halves are the '
+                                                          'two-scenes-per-wave forms k_motion_pair / k_obs_pair (their own rows in rocprof\'s table; the library\'s event '
+                                                          'timers and this average count them as launches of the step kernel: profiles/*_kernel_stats_top.txt '
+                                                          'ends with the combined row)') if env.overlap else None,
+                                  # the same kernel per step CALL: all its launches' bytes over the time during which at least one of them
+                                  # ran (the union of the launch intervals) -- what the kernel sustains while its launches overlap
+                                  'per_call': {'kernel_ms': dom_union[0] / max(dom_union[1], 1), 'calls': dom_union[1],
+                                               'achieved': bytes_per_launch * args.steps / max(dom_union[1], 1) / (dom_union[0] / max(dom_union[1], 1) * 1e-3) / 1e9 if dom_union[0] > 0 else None,
+                                               'frac': bytes_per_launch * args.steps / max(dom_union[1], 1) / (dom_union[0] / max(dom_union[1], 1) * 1e-3) / 1e9 / 8000.0 if dom_union[0] > 0 else None},
+                                  'whole_step': {'achieved': bytes_per_launch / (elapsed / args.steps) / 1e9, 'unit': 'GB/s',
+                                                 'frac': bytes_per_launch / (elapsed / args.steps) / 1e9 / 8000.0,
+                                                 'note': 'algorithmic bytes of one bench step / driver-timed step'},
+                                  'valu_issue': valu,
+                                  'measured_copy_GBps': copy_gbps,
+                                  'kernel_ms': dom_ms, 'kernel_launches': dom_launches,
+                                  'algorithmic_bytes_per_launch': bytes_avg_launch,
+                                  'algorithmic_bytes_per_bench_step': bytes_per_launch,
+                                  'ms_per_bench_step_by_kernel': per_step, 'breakdown_steps': n_break}
+            result['repeat'] = repeat
         if repeat is not None:
             # next to the driver-timed `value`: the steady-state figure (median of the longer passes) and the joined form, this rank x ranks
             result['value_steady'] = total_scenes / (repeat['median'] * 1e-3)
@@ -526,8 +555,9 @@ def main():
                                    'generator_seconds': bench_refresher.gen_seconds, 'lots_per_commit': args.pool,
                                    'host_generator_lots_per_s': (bench_refresher.commits + 1) * args.pool / max(bench_refresher.gen_seconds, 1e-9)}
                                   if bench_refresher is not None else None)
-        result['parity_check'] = parity
-        result['queue_check'] = env.queue_check() if env.overlap else None
+        if args.full:
+            result['parity_check'] = parity
+            result['queue_check'] = env.queue_check() if env.overlap else None
         if trainer is not None:
             from hope_amd.policy import count_parameters
             result['metric'] = 'env+agent steps/sec (full CarParking step + HOPE transformer policy' + \
@@ -542,13 +572,38 @@ def main():
                                      'gradient_allreduce': __import__('hope_amd.dist', fromlist=['x']).allreduce_stats(),
                                      'pool_refreshes_in_run': (trainer.refresher.commits if trainer.refresher is not None else 0),
                                      'rollout': trainer.stats()})
-        if not args.no_cpu_baseline and world == 1 and trainer is None:
+        if args.full and not args.no_cpu_baseline and world == 1 and trainer is None:
             result['cpu_baseline'] = cpu_baseline(args, (start, dest, bbox, verts, nob, nvert), stages)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result))
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(env, out_dir, seed):
+    """--dump-outputs: every output the last timed step gave its caller (the env's output arena: observation, reward, status,
+    done, pose, Reeds-Shepp word and lengths, the image with --image) as out_dir/<name>.npy.  Floating outputs keep their
+    dtype; int8 / uint8 become float32 and int32 float64 (exact).  When the whole set exceeds DUMP_BYTES, every output is
+    cut to the same seeded sample of scene rows, sorted, and out_dir/scene_index.npy lists them."""
+    import torch
+    torch.cuda.synchronize(env.device)                         # (the Reeds-Shepp outputs of a deferred step included)
+    host = env.download_outputs()
+    as_dt = {np.dtype(np.int8): np.float32, np.dtype(np.uint8): np.float32, np.dtype(np.int32): np.float64}
+    outs = {k: v.astype(as_dt.get(v.dtype, v.dtype)) for k, v in host.items()}
+    row_bytes = sum(v.nbytes // env.n for v in outs.values())
+    rows = None
+    if row_bytes * env.n + 128 * (len(outs) + 1) > DUMP_BYTES:
+        k = (DUMP_BYTES - 128 * (len(outs) + 1)) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed + 4321).choice(env.n, k, replace=False))
+        outs = {name: v[rows] for name, v in outs.items()}
+        outs['scene_index'] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in outs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(v))
 
 
 def parity_witness(env, stages, fresh, act, k, seed):

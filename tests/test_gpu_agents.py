@@ -312,6 +312,38 @@ def test_bench_as_eight_ranks_of_8192_scenes_sharing_the_gpu():
     assert d['host']['generator_threads'] == d['host']['cpus_this_rank']
 
 
+def test_bench_plain_line_and_reproducible_output_dumps(tmp_path):
+    """A plain `bench.py` run prints the headline keys and none of what --full adds; --dump-outputs of two runs with the same
+    arguments holds the same arrays, bit for bit -- with pool commits inside the timed steps (fixed refresh schedule)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dirs = [], []
+    for run in ('a', 'b'):
+        out = str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--scenes', '8192', '--steps', '24', '--warmup', '4',
+               '--preroll', '40', '--refresh-every', '8', '--dump-outputs', out]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.strip().split('\n') if ln.startswith('{')][-1]))
+        dirs.append(out)
+    d = lines[0]
+    assert d['steps'] == 24 and d['warmup'] == 4 and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['unit'] == 'env-steps/s' and d['metric'].startswith('parallel env steps/sec')
+    assert abs(d['value'] - 8192 * 24 / (d['ms_per_step'] * 24 * 1e-3)) < 1e-3 * d['value']
+    assert not any(k in d for k in ('roofline', 'repeat', 'value_steady', 'parity_check', 'queue_check', 'cpu_baseline'))
+    assert d['pool_refresh']['commits_in_timed_region'] == 3 and lines[1]['pool_refresh']['commits_in_timed_region'] == 3
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {'lidar.npy', 'action_mask.npy', 'target.npy', 'reward.npy', 'status.npy', 'done.npy', 'rs_word.npy'} <= set(names)
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in names) <= 64 * 1000 * 1000
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 8192, (f, a.dtype, a.shape)
+        assert np.array_equal(a, b, equal_nan=True), f
+
+
 def test_bench_gpus_n_launches_its_own_ranks():
     """VERDICT r4 #3b: `python bench.py --gpus 2` WITHOUT a launcher (the way the driver starts `--gpus 1`) must not stop at an error
     line: it starts its own ranks under torch.distributed.run and rank 0's JSON line passes through.  On the 1-GPU box the two ranks
@@ -324,7 +356,7 @@ def test_bench_gpus_n_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(HOPE_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--scenes', '8192', '--steps', '24', '--warmup', '4', '--preroll', '40',
-           '--refresh-every', '8', '--no-cpu-baseline', '--witness', '0', '--repeat-passes', '1', '--repeat-steps', '40']
+           '--refresh-every', '8', '--full', '--no-cpu-baseline', '--witness', '0', '--repeat-passes', '1', '--repeat-steps', '40']
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().split('\n') if ln.startswith('{')]

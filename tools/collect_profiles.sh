@@ -13,11 +13,11 @@ T="timeout 400"
 py() { $T python "$@" 2>>$O/stderr.log; }
 PRE="--preroll 100 --refresh-every 0"     # profiled runs: a shorter pre-roll to the stationary episode population (the default run uses 300), static pool
 
-py $R/bench.py | tail -1 > $O/${TAG}_bench_default.json
-py $R/bench.py | tail -1 > $O/${TAG}_bench_default_2.json
-py $R/bench.py --image --no-cpu-baseline | tail -1 > $O/${TAG}_bench_image.json
-py $R/bench.py --rs-join joined --no-cpu-baseline | tail -1 > $O/${TAG}_bench_joined.json
-py $R/bench.py --preroll 0 --no-cpu-baseline --witness 0 | tail -1 > $O/${TAG}_bench_fresh_episodes.json     # the round-3 form of the number
+py $R/bench.py --full | tail -1 > $O/${TAG}_bench_default.json
+py $R/bench.py --full | tail -1 > $O/${TAG}_bench_default_2.json
+py $R/bench.py --full --image --no-cpu-baseline | tail -1 > $O/${TAG}_bench_image.json
+py $R/bench.py --full --rs-join joined --no-cpu-baseline | tail -1 > $O/${TAG}_bench_joined.json
+py $R/bench.py --full --preroll 0 --no-cpu-baseline --witness 0 | tail -1 > $O/${TAG}_bench_fresh_episodes.json     # the round-3 form of the number
 
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats -- python $R/bench.py --steps 10 --warmup 3 $PRE --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1 > $O/${TAG}_bench_under_rocprof.json
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats_img -- python $R/bench.py --image --steps 10 --warmup 3 $PRE --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1 > $O/${TAG}_bench_image_under_rocprof.json
@@ -44,29 +44,29 @@ py $R/tools/stage_times.py --scenes 32768 > $O/${TAG}_stage_times.txt
 py $R/tools/bev_probe.py > $O/${TAG}_image_stage_times.txt
 # batch-size sweep, launch modes, new-map turnover, BASELINE configs 4 / 5 on one GPU, ranks sharing the GPU
 {
-  for NS in 4096 8192 16384 32768 65536 131072; do echo "== --scenes $NS"; py $R/bench.py --scenes $NS --no-cpu-baseline --witness 0 --repeat-passes 2 --steps 40 --warmup 10 | tail -1; done
-  echo "== --scenes 65536 --overlap off"; py $R/bench.py --overlap off --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 --witness 0 | tail -1
-  echo "== --same-map"; py $R/bench.py --same-map --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 | tail -1
-  echo "== --refresh-every 0 (static pool)"; py $R/bench.py --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
-  echo "== HOPE_RS_DEBUG=0x20000 (no screen pass: round 4's validation kernel)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
-  echo "== HOPE_PIPE=0 (steps not pipelined: the round-3 launch structure with this round's kernels)"; HOPE_PIPE=0 $T python $R/bench.py --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
-  for NS in 4096 8192 16384; do echo "== --scenes $NS HOPE_RS_DEBUG=0x20000 (no screen pass)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --scenes $NS --no-cpu-baseline --witness 0 --repeat-passes 2 --steps 40 --warmup 10 2>/dev/null | tail -1; done
-  echo "== --action-bank 16 (rounds 1-5: each scene repeats a 16-step action pattern)"; py $R/bench.py --action-bank 16 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
-  echo "== HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 (one scene per wave in both launches of the small-tile class)"; HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 $T python $R/bench.py --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
-  echo "== the driver's exact form: --steps 20 --warmup 5"; py $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline | tail -1
-  echo "== the driver's exact form, second run"; py $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline | tail -1
-  echo "== the driver's exact form, third run"; py $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline | tail -1
-  echo "== config 2: --stages motion --scenes 4096"; py $R/bench.py --scenes 4096 --stages motion --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 --witness 0 | tail -1
-  echo "== config 3: --scenes 16384 (full step)"; py $R/bench.py --scenes 16384 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 | tail -1
-  echo "== config 4 share: --policy hope --algo rollout --scenes 8192 --image"; py $R/bench.py --policy hope --algo rollout --scenes 8192 --image --no-cpu-baseline | tail -1
-  echo "== --policy hope --algo rollout (65536 scenes, no image)"; py $R/bench.py --policy hope --algo rollout --no-cpu-baseline | tail -1
-  echo "== config 5 share: --policy hope --algo ppo --scenes 16384"; py $R/bench.py --policy hope --algo ppo --scenes 16384 --no-cpu-baseline --steps 32 --warmup 16 | tail -1
+  for NS in 4096 8192 16384 32768 65536 131072; do echo "== --scenes $NS"; py $R/bench.py --full --scenes $NS --no-cpu-baseline --witness 0 --repeat-passes 2 --steps 40 --warmup 10 | tail -1; done
+  echo "== --scenes 65536 --overlap off"; py $R/bench.py --full --overlap off --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 --witness 0 | tail -1
+  echo "== --same-map"; py $R/bench.py --full --same-map --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 | tail -1
+  echo "== --refresh-every 0 (static pool)"; py $R/bench.py --full --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
+  echo "== HOPE_RS_DEBUG=0x20000 (no screen pass: round 4's validation kernel)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --full --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
+  echo "== HOPE_PIPE=0 (steps not pipelined: the round-3 launch structure with this round's kernels)"; HOPE_PIPE=0 $T python $R/bench.py --full --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
+  for NS in 4096 8192 16384; do echo "== --scenes $NS HOPE_RS_DEBUG=0x20000 (no screen pass)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --full --scenes $NS --no-cpu-baseline --witness 0 --repeat-passes 2 --steps 40 --warmup 10 2>/dev/null | tail -1; done
+  echo "== --action-bank 16 (rounds 1-5: each scene repeats a 16-step action pattern)"; py $R/bench.py --full --action-bank 16 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
+  echo "== HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 (one scene per wave in both launches of the small-tile class)"; HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 $T python $R/bench.py --full --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
+  echo "== the driver's exact form: --steps 20 --warmup 5"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1
+  echo "== the driver's exact form, second run"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1
+  echo "== the driver's exact form, third run"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1
+  echo "== config 2: --stages motion --scenes 4096"; py $R/bench.py --full --scenes 4096 --stages motion --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 --witness 0 | tail -1
+  echo "== config 3: --scenes 16384 (full step)"; py $R/bench.py --full --scenes 16384 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 | tail -1
+  echo "== config 4 share: --policy hope --algo rollout --scenes 8192 --image"; py $R/bench.py --full --policy hope --algo rollout --scenes 8192 --image --no-cpu-baseline | tail -1
+  echo "== --policy hope --algo rollout (65536 scenes, no image)"; py $R/bench.py --full --policy hope --algo rollout --no-cpu-baseline | tail -1
+  echo "== config 5 share: --policy hope --algo ppo --scenes 16384"; py $R/bench.py --full --policy hope --algo ppo --scenes 16384 --no-cpu-baseline --steps 32 --warmup 16 | tail -1
   echo "== 2 ranks sharing the GPU (gloo): weak scaling 16384 scenes/rank"
-  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --scenes 16384 --steps 20 --warmup 5 --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1
+  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --full --gpus 2 --scenes 16384 --steps 20 --warmup 5 --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1
   echo "== 8 ranks sharing the GPU (gloo): config 4's shape, 65536 scenes strong-scaled = 8192 per rank"
-  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 $R/bench.py --gpus 8 --scaling strong --scenes 65536 --steps 20 --warmup 5 --preroll 60 --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1
+  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 $R/bench.py --full --gpus 8 --scaling strong --scenes 65536 --steps 20 --warmup 5 --preroll 60 --no-cpu-baseline --witness 0 --repeat-passes 0 2>/dev/null | tail -1
   echo "== 2 ranks sharing the GPU (gloo): strong scaling 16384 scenes total, PPO with gradient all-reduce"
-  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 2 --scaling strong --scenes 16384 --policy hope --algo ppo --steps 16 --warmup 8 --no-cpu-baseline 2>/dev/null | tail -1
+  HOPE_BENCH_SHARE_GPU=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --full --gpus 2 --scaling strong --scenes 16384 --policy hope --algo ppo --steps 16 --warmup 8 --no-cpu-baseline 2>/dev/null | tail -1
 } > $O/${TAG}_bench_modes.txt
 # timeline of one step: joined form (one step can be cut out of the trace) and the last 60 launches of the pipelined form
 $T rocprofv3 --kernel-trace --output-format csv -d $O/tl -- python $R/bench.py --rs-join joined --steps 8 --warmup 8 $PRE --no-cpu-baseline --witness 0 --repeat-passes 0 > /dev/null 2>&1
