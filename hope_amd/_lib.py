@@ -13,6 +13,7 @@ ACTION_RESCALE_F32 = 0x80
 AUTO_REDRAW = 0x100
 DEFER_RS = 0x200
 STAGE_IMG = 0x40
+STAGE_NO_CULL, STAGE_ONE_SCENE = 0x4000, 0x8000   # reserved internal A/B switches (hope_amd/csrc/hope_internal.h): tests only
 IMG_SIZE, IMG_CHANNELS, TRAJ_RENDER_LEN = 64, 3, 20
 AUTO_RESET = 0x20
 KERNELS = ('k_kinematics', 'k_env_step', 'k_rs_words', 'k_rs_validate', 'k_bev_image', 'k_bev_prep', 'k_rs_compact', 'k_post', 'k_rs_segs', 'k_rs_screen')

@@ -1190,14 +1190,11 @@ hipError_t launch_bev_image(const BevParams& p, hipStream_t stream, LaunchTimer*
     hipLaunchKernelGGL(k_bev_prep, dim3(p.n), dim3(WAVE), 0, stream, p);
     if (timer) timer->end(stream);
     if (side && (e = hipStreamWaitEvent(stream, ev_join, 0)) != hipSuccess) return e;
-    const dim3 grid(p.n), block(BEV_WAVES * WAVE);
     if (timer) timer->begin(HOPE_K_IMAGE, stream);
     // (scenes with a box that is not a plain car box, or whose drawn boxes outgrew the trajectory torus: none in practice; first,
     // because the other launch empties the list)
-    hipLaunchKernelGGL(k_bev_image<true>, dim3(std::min(p.n, 1024)), block, bev_lds_bytes(true), stream, p);
-    static const bool one_wave = !(getenv("HOPE_BEV_WG") && atoi(getenv("HOPE_BEV_WG")) == 4);     // (A/B: 4 = four waves per workgroup)
-    if (one_wave) hipLaunchKernelGGL(k_bev_image_w, dim3(((p.n + 7) / 8) * 32), dim3(WAVE), (size_t)WAVE_LDS, stream, p);
-    else hipLaunchKernelGGL(k_bev_image<false>, grid, block, bev_lds_bytes(false), stream, p);
+    hipLaunchKernelGGL(k_bev_image<true>, dim3(std::min(p.n, 1024)), dim3(BEV_WAVES * WAVE), bev_lds_bytes(true), stream, p);
+    hipLaunchKernelGGL(k_bev_image_w, dim3(((p.n + 7) / 8) * 32), dim3(WAVE), (size_t)WAVE_LDS, stream, p);
     if (timer) timer->end(stream);
     return hipGetLastError();
 }

@@ -32,6 +32,19 @@ static int fail(int code, const std::string& msg) {
             return fail(HOPE_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
 
+// Stream roles of a step's launch structure.  The numbers are those hope_env_queue_check reports (include/hope_env.h).
+enum Role {
+    ROLE_CALLER = 0,      // the caller's stream
+    ROLE_CHAIN = 1,       // the second chain (small-tile class): all of it, or its search launches in a pipelined step
+    ROLE_IMAGE = 2,       // the image (joined steps) / the static-layer rebuild next to it (pipelined steps)
+    ROLE_OBS_LARGE = 3,   // observation half of the first chain (large-tile class)
+    ROLE_OBS_SMALL = 4,   // observation half of the second chain (small-tile class)
+    ROLE_SEARCH0 = 5,     // search launches of the first chain in a pipelined step
+    ROLE_SPARE = 6,       // created, never used: the runtime spreads streams over hardware queues in creation order
+    ROLE_OBS_SUB = 7,     // observation half of the second sub-chain of a single-class batch
+    N_ROLES = 8
+};
+
 struct hope_env {
     int n = 0, max_obst = 0, device = 0;
     uint32_t flags = 0;
@@ -73,7 +86,7 @@ struct hope_env {
     std::vector<uint8_t> slot_cls_host;          // draw / launch class of every scene slot (0: <= 32 obstacles, 1: larger lots)
     uint8_t* slot_cls = nullptr;                 // the same on the device
     double* rs_rec = nullptr;
-    int32_t* rs_surv_count = nullptr;            // [MAX_CHAINS] two-kernel validation: searches k_rs_screen left a word of, per chain
+    int32_t* rs_surv_count = nullptr;            // [MAX_CHAIN] two-kernel validation: searches k_rs_screen left a word of, per chain
     int2* rs_surv = nullptr;                     // [2 n] (queue index, queue entry), laid out like rs_list
     uint8_t* active_snap = nullptr; // [n] the caller's `active` mask as the motion launch saw it (read by k_rs_compact, HOPE_DEFER_RS)
     // StepCold (rarely used kernel parameters) in device memory: a ring of immutable versions, uploaded stream-ordered on change
@@ -130,21 +143,19 @@ struct hope_env {
     int32_t* pool_overflow = nullptr;            // [1] device counter: draws truncated to max_obst obstacles
     int32_t* cur_pool = nullptr;    // [n] pool entry a scene currently holds (-1: uploaded by set_scenes; -1 - c... see hope_env.h)
     uint32_t* episode = nullptr;    // [n] redraw counter (part of the draw's hash)
-    // HOPE_F_OVERLAP: the two tile classes' launches go to two streams (fork / join with events)
-    static constexpr int MAX_CHAINS = 8;                    // launch chains in flight: tile classes x HOPE_CHAINS sub-lists
-    int sub_chains = 1;
-    bool sub_chains_auto = true;                            // HOPE_CHAINS not given: hope_env_step picks (single-class batches, see there)
-    hipStream_t side[MAX_CHAINS] = {};                     // [0] unused: chain 0 runs on the caller's stream
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_CHAINS] = {}, ev_step[2] = {}, ev_segs[2] = {}, ev_post[2] = {};
+    // HOPE_F_OVERLAP: the two tile classes' launches go to library streams, one per role (fork / join with events)
+    static constexpr int MAX_CHAIN = 2;                     // launch chains of a step: one per tile class, or two sub-chains of one class
+    hipStream_t side[N_ROLES] = {};                         // stream of each role ([ROLE_CALLER] unused: the caller's stream)
+    hipEvent_t ev_fork = nullptr, ev_step[MAX_CHAIN] = {}, ev_segs[MAX_CHAIN] = {}, ev_post[MAX_CHAIN] = {};
+    hipEvent_t ev_chain1_done = nullptr, ev_image_done = nullptr, ev_obs_done[MAX_CHAIN] = {}, ev_search0_done = nullptr;
     hipEvent_t ev_collect = nullptr;                        // round 6: ONE join point for the caller's stream (the library stream of the other chain's observation collects the rest)
     bool last_via_steps = false;                            // the last step recorded ev_step[0 / 1] behind both motion launches (the pool's only readers)
     hipEvent_t ev_bev[2] = {};                              // image: fork / join of the static-layer rebuild next to k_bev_prep
     int rs_parity = 0;                                      // which of the two queue counters of a chain this step uses (pipelined steps)
-    int queue_of_role[MAX_CHAINS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // measured hardware-queue class of role r's stream ([0]: the NULL stream)
+    int queue_of_role[N_ROLES] = {-1, -1, -1, -1, -1, -1, -1, -1};   // measured hardware-queue class of role r's stream ([0]: the NULL stream)
     int n_queues = 0;
     double queue_check_ms = 0.0;
-    // HOPE_DEFER_RS: the chains of the last step have not been joined into the caller's stream (events ev_join[1], ev_join[RS_SIDE])
-    static constexpr int RS_SIDE = 5;                       // the stream of the first chain when it may not run on the caller's
+    // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
 
@@ -517,16 +528,16 @@ extern "C" {
 // HOPE_DEFER_RS bookkeeping: `s` waits for the chains the last step left unjoined / the host does
 static int join_rs(hope_env_t* h, hipStream_t s) {
     if (!h->rs_pending) return HOPE_OK;
-    HIPCHK(hipStreamWaitEvent(s, h->ev_join[1], 0));
-    HIPCHK(hipStreamWaitEvent(s, h->ev_join[hope_env::RS_SIDE], 0));
+    HIPCHK(hipStreamWaitEvent(s, h->ev_chain1_done, 0));
+    HIPCHK(hipStreamWaitEvent(s, h->ev_search0_done, 0));
     h->rs_pending = false;
     return HOPE_OK;
 }
 static int settle_rs(hope_env_t* h) {
     if (!h || !h->rs_pending) return HOPE_OK;
     DeviceGuard guard(h->device);
-    HIPCHK(hipEventSynchronize(h->ev_join[1]));
-    HIPCHK(hipEventSynchronize(h->ev_join[hope_env::RS_SIDE]));
+    HIPCHK(hipEventSynchronize(h->ev_chain1_done));
+    HIPCHK(hipEventSynchronize(h->ev_search0_done));
     h->rs_pending = false;
     return HOPE_OK;
 }
@@ -589,7 +600,7 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
     ALLOC(h->mask_bsc, NBEAM * sizeof(double));
     ALLOC(h->hull_base, NBEAM * sizeof(double));
     ALLOC(h->beam_ab, 2 * NBEAM * sizeof(double));
-    ALLOC(h->rs_count, 2 * hope_env::MAX_CHAINS * sizeof(int32_t));
+    ALLOC(h->rs_count, 2 * hope_env::MAX_CHAIN * sizeof(int32_t));
     ALLOC(h->rs_list, 2 * N * sizeof(int32_t));
     ALLOC(h->rs_in, 2 * N * RS_IN_WORDS * sizeof(double));
     ALLOC(h->rs_flag, N);
@@ -598,7 +609,7 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
     ALLOC(h->cls_list[0], N * sizeof(int32_t));
     ALLOC(h->cls_list[1], N * sizeof(int32_t));
     ALLOC(h->rs_rec, N * rs_rec_bytes_per_scene());
-    ALLOC(h->rs_surv_count, hope_env::MAX_CHAINS * sizeof(int32_t));
+    ALLOC(h->rs_surv_count, hope_env::MAX_CHAIN * sizeof(int32_t));
     ALLOC(h->rs_surv, 2 * N * sizeof(int2));
     ALLOC(h->cur_pool, N * sizeof(int32_t));
     ALLOC(h->episode, N * sizeof(uint32_t));
@@ -632,9 +643,9 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
     HIPCHK(hipMemset(h->scene_c, 0, N * SC_WORDS * sizeof(double)));
     HIPCHK(hipMemset(h->state, 0, N * ST_WORDS * sizeof(double)));
     HIPCHK(hipMemset(h->tstep, 0, N * sizeof(int32_t)));
-    HIPCHK(hipMemset(h->rs_count, 0, 2 * hope_env::MAX_CHAINS * sizeof(int32_t)));
+    HIPCHK(hipMemset(h->rs_count, 0, 2 * hope_env::MAX_CHAIN * sizeof(int32_t)));
     HIPCHK(hipMemset(h->rs_flag, 0, N));
-    HIPCHK(hipMemset(h->rs_surv_count, 0, hope_env::MAX_CHAINS * sizeof(int32_t)));
+    HIPCHK(hipMemset(h->rs_surv_count, 0, hope_env::MAX_CHAIN * sizeof(int32_t)));
     HIPCHK(hipMemset(h->rs_surv, 0, 2 * N * sizeof(int2)));
     HIPCHK(hipMemset(h->rs_in, 0, 2 * N * RS_IN_WORDS * sizeof(double)));
     HIPCHK(hipMemset(h->rs_list, 0, 2 * N * sizeof(int32_t)));      // (k_rs_words / k_rs_segs read queue entries before they know the queue length)
@@ -646,19 +657,8 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
     HIPCHK(hipHostMalloc((void**)&h->cold_host, hope_env::COLD_RING * sizeof(StepCold)));
     for (int i = 0; i < hope_env::COLD_RING; i++) HIPCHK(hipEventCreateWithFlags(&h->cold_ev[i], hipEventDisableTiming));
     memset(&h->cold_last, 0, sizeof(h->cold_last));
-    if (getenv("HOPE_DEBUG_PTRS")) {
-        fprintf(stderr, "hope_env %p: verts %p obb %p scene_c %p state %p kin %p post %p rs_rec %p rs_list %p cls0 %p cls1 %p", (void*)h, (void*)h->verts, (void*)h->obb, (void*)h->scene_c,
-                (void*)h->state, (void*)h->kin, (void*)h->post, (void*)h->rs_rec, (void*)h->rs_list, (void*)h->cls_list[0], (void*)h->cls_list[1]);
-        if (h->traj) fprintf(stderr, " traj %p layer %p..%p bev_list %p scratch %p..%p", (void*)h->traj, (void*)h->bev_layer, (void*)(h->bev_layer + N * (size_t)BEV_LAYER_ROWS * BEV_LAYER_STRIDE),
-                             (void*)h->bev_list, (void*)h->bev_scratch, (void*)(h->bev_scratch + N * BEV_SCENE_INTS));
-        fprintf(stderr, "\n");
-    }
     HIPCHK(rs_init_tables());        // (a synchronous symbol copy: here, never inside a captured step)
-    if (getenv("HOPE_OBS_WPC0") || getenv("HOPE_OBS_WPC1")) {
-        for (const void* f : {(const void*)k_env_step<float, float, false, 2>, (const void*)k_env_step<float, double, false, 2>,
-                              (const void*)k_env_step<double, float, false, 2>, (const void*)k_env_step<double, double, false, 2>})
-            HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    } else if (lds > 48 * 1024) {
+    if (lds > 48 * 1024) {
         for (const void* f : {(const void*)k_env_step<float, float>, (const void*)k_env_step<float, float, true>,
                               (const void*)k_env_step<float, double>, (const void*)k_env_step<double, float>,
                               (const void*)k_env_step<double, double>,
@@ -671,72 +671,36 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
             HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     if (flags & HOPE_F_OVERLAP) {
-        const char* ch = getenv("HOPE_CHAINS");              // sub-lists per tile class, each its own chain / stream
-        h->sub_chains = ch ? std::max(1, std::min(hope_env::MAX_CHAINS / 2, atoi(ch))) : 1;
-        h->sub_chains_auto = ch == nullptr;
         HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->ev_collect, hipEventDisableTiming));
         for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&h->ev_bev[i], hipEventDisableTiming));
         for (int i = 0; i < 2; i++) { HIPCHK(hipEventCreateWithFlags(&h->ev_step[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->ev_segs[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->ev_post[i], hipEventDisableTiming)); }
-        // HOPE_PRIO=1 (experiment, rejected): highest stream priority for the launch chains (the critical path), lowest for
-        // the observation / image streams [2], [3], [4].  Measured 0.80 -> 1.08 ms per step at 65 536 scenes: the second
-        // chain's kernels then wait hundreds of microseconds between launches behind the first chain's.
-        int prio_lo = 0, prio_hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        // HOPE_PRIO (experiment): stream priorities by ROLE -- 1: chains highest, observation / image lowest; 2: chains default,
-        // observation lowest; 3: chains highest, observation default; 4: chains (the search streams of pipelined steps) lowest
-        static const int prio_mode = getenv("HOPE_PRIO") ? atoi(getenv("HOPE_PRIO")) : 0;
-        int perm[hope_env::MAX_CHAINS] = {0, 1, 6, 3, 2, 5, 4, 7};
+        for (hipEvent_t* e : {&h->ev_chain1_done, &h->ev_image_done, &h->ev_obs_done[0], &h->ev_obs_done[1], &h->ev_search0_done})
+            HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         // Which library stream plays which role decides which roles share a HARDWARE queue (the runtime spreads streams over a few
-        // queues in creation order, and launches of streams that share one serialise): HOPE_SIDE_PERM="a,b,c,d,e,f,g" gives role i
-        // (1: chain of the small-tile class, 2: image, 3 / 4: observation half of the large- / small-tile class, 5: chain of the
-        // large-tile class with HOPE_DEFER_RS) the a-th ... created stream.  Default: the two observation launches on streams that do
-        // not share a hardware queue (3 and 7; with 3 and 4 the larger class's observation started only when the smaller class's
-        // was done, 180 us after its motion launch): 0.695 -> 0.675 ms (profiles/r04_stream_roles.txt).  Third session, final
-        // (pipelined) structure, profiles/r04_stream_roles_pipelined.txt: the deferred forms use roles 1, 3, 5 (+ the caller's stream)
-        // and their assignment is in the best class; role 4 matters to the JOINED form, which wants it on the 2nd stream (65 536 scenes
-        // 0.672 -> 0.660 ms, 16 384: 0.343 -> 0.305), and to the second sub-chain of a single-class batch, which wants the 7th stream
-        // (on the 2nd: 0.68 -> 0.89 ms) and therefore takes role 7 (hope_env_step).
+        // queues in creation order, and launches of streams that share one serialise).  perm[role] = the created stream (1 .. 7) that
+        // plays it.  Default: the two observation launches on streams that do not share a hardware queue (3 and 7; with 3 and 4 the
+        // larger class's observation started only when the smaller class's was done, 180 us after its motion launch): 0.695 -> 0.675 ms
+        // (profiles/r04_stream_roles.txt).  Third session, final (pipelined) structure, profiles/r04_stream_roles_pipelined.txt: the
+        // deferred forms use ROLE_CHAIN, ROLE_OBS_LARGE, ROLE_SEARCH0 (+ the caller's stream) and their assignment is in the best class;
+        // ROLE_OBS_SMALL matters to the JOINED form, which wants it on the 2nd stream (65 536 scenes 0.672 -> 0.660 ms, 16 384: 0.343 ->
+        // 0.305), and ROLE_OBS_SUB to the second sub-chain of a single-class batch, which wants the 7th stream (on the 2nd: 0.68 -> 0.89 ms).
         // A handle with the image (HOPE_F_IMAGE) has six streams at work in a step (the image on the caller's stream, two env, two search
         // streams, the layer rebuild): other roles have to share.  Measured over 40 random assignments under the final launch structure
         // (profiles/r04_stream_roles_pipelined.txt): 65 536 scenes 1.92 -> 1.85 ms, 8 192 scenes 0.527 -> 0.445 ms with the image; the
         // same assignment costs a step WITHOUT the image 15 % (0.60 -> 0.69 ms), hence by the handle's flag, not for everyone.
-        if (flags & HOPE_F_IMAGE) { static const int pi[hope_env::MAX_CHAINS] = {0, 6, 2, 3, 1, 4, 5, 7}; for (int i = 0; i < hope_env::MAX_CHAINS; i++) perm[i] = pi[i]; }
-        {
-            const char* pe = getenv("HOPE_SIDE_PERM");
-            if (pe) {
-                int k = 1, tmp[hope_env::MAX_CHAINS] = {0, 1, 2, 3, 4, 5, 6, 7};
-                for (const char* q = pe; *q && k < hope_env::MAX_CHAINS; k++) {
-                    tmp[k] = atoi(q);
-                    while (*q && *q != ',') q++;
-                    if (*q == ',') q++;
-                }
-                bool used[hope_env::MAX_CHAINS] = {};
-                bool ok = true;
-                for (int i = 1; i < hope_env::MAX_CHAINS; i++) { if (tmp[i] < 1 || tmp[i] >= hope_env::MAX_CHAINS || used[tmp[i]]) ok = false; else used[tmp[i]] = true; }
-                if (ok) for (int i = 1; i < hope_env::MAX_CHAINS; i++) perm[i] = tmp[i];
-            }
-        }
-        hipStream_t created[hope_env::MAX_CHAINS] = {};
-        for (int c = 1; c < hope_env::MAX_CHAINS; c++) {          // streams in creation order; the role of the c-th decides its priority
-            int role = c;
-            for (int r = 1; r < hope_env::MAX_CHAINS; r++) if (perm[r] == c) role = r;
-            const bool is_obs = role >= 2 && role <= 4, is_chain = role == 1 || role == 5;
-            int prio = 0;
-            if (prio_mode == 1) prio = is_obs ? prio_lo : prio_hi;
-            else if (prio_mode == 2) prio = is_obs ? prio_lo : 0;
-            else if (prio_mode == 3) prio = is_chain ? prio_hi : 0;
-            else if (prio_mode == 4) prio = is_chain ? prio_lo : 0;      // round 6: the search streams lowest, everything else default
-            HIPCHK(hipStreamCreateWithPriority(&created[c], hipStreamNonBlocking, prio));
-            HIPCHK(hipEventCreateWithFlags(&h->ev_join[c], hipEventDisableTiming));
-        }
+        // (Stream priorities by role were measured and rejected, DESIGN.md 9a: every stream has priority 0.)
+        static const int perm_plain[N_ROLES] = {0, 1, 6, 3, 2, 5, 4, 7}, perm_image[N_ROLES] = {0, 6, 2, 3, 1, 4, 5, 7};
+        int perm[N_ROLES];
+        for (int r = 0; r < N_ROLES; r++) perm[r] = (flags & HOPE_F_IMAGE) ? perm_image[r] : perm_plain[r];
+        hipStream_t created[N_ROLES] = {};
+        for (int c = 1; c < N_ROLES; c++) HIPCHK(hipStreamCreateWithPriority(&created[c], hipStreamNonBlocking, 0));
         // ---- which created streams share a hardware queue: measure, then give the roles that are busy together different queues ----
         // cls[c]: queue class of the c-th created stream (c = 0: the NULL stream, where PyTorch's default current stream lives).
         // A stream is compared with one representative of every class seen so far: <= 4 classes x 7 streams pairs.
-        int cls[hope_env::MAX_CHAINS];
-        for (int c = 0; c < hope_env::MAX_CHAINS; c++) cls[c] = -1;
-        static const bool no_check = getenv("HOPE_QUEUE_CHECK") && atoi(getenv("HOPE_QUEUE_CHECK")) == 0;
-        if (!no_check) {
+        int cls[N_ROLES];
+        for (int c = 0; c < N_ROLES; c++) cls[c] = -1;
+        {
             const auto t_begin = std::chrono::steady_clock::now();
             const long long ticks = 10000;                    // 100 us at 100 MHz
             // Two spin kernels, one per stream: they OVERLAP on the GPU's clock iff the streams sit on different hardware queues.  An overlap
@@ -757,11 +721,10 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
                 }
                 return 0;
             };
-            created[0] = nullptr;
             hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, created[1], 100LL, (long long*)nullptr);      // (first launch of the kernel: module load, not measured)
             hipStreamSynchronize(created[1]);
-            int rep[hope_env::MAX_CHAINS], n_cls = 0;
-            for (int c = 0; c < hope_env::MAX_CHAINS && ok; c++) {
+            int rep[N_ROLES], n_cls = 0;
+            for (int c = 0; c < N_ROLES && ok; c++) {
                 int found = -1;
                 for (int k = 0; k < n_cls && found < 0 && ok; k++) {
                     const int ov = pair_overlaps(created[rep[k]], created[c]);
@@ -774,28 +737,34 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
             if (stamps) hipHostFree(stamps);
             HIPCHK(hipGetLastError());
             h->queue_check_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-            if (!ok) { for (int c = 0; c < hope_env::MAX_CHAINS; c++) cls[c] = -1; n_cls = 0; }
+            if (!ok) { for (int c = 0; c < N_ROLES; c++) cls[c] = -1; n_cls = 0; }
             h->n_queues = n_cls;
-            // Assignment.  Roles busy at the same time: deferred step {caller, 5, 1, 3}; joined step {caller, 1, 3, 4}; two sub-chains of one
-            // class {5, 1, 3, 7}.  Greedy in that order of importance: every role takes the free stream whose class collides with the fewest
-            // roles it must not share with; ties keep the hand-found table (so a box that shows nothing to gain gets exactly round 4's
-            // assignment).  Not for image handles (six busy streams on four queues: the measured table stays), not when the user gave one.
-            if (n_cls >= 2 && !getenv("HOPE_SIDE_PERM") && !(flags & HOPE_F_IMAGE)) {
-                static const int order[7] = {5, 1, 3, 4, 7, 2, 6};
-                static const int conflicts[hope_env::MAX_CHAINS][4] = {{-1, -1, -1, -1}, {0, 5, -1, -1}, {-1, -1, -1, -1}, {0, 5, 1, -1},
-                                                                       {0, 1, 3, -1}, {0, -1, -1, -1}, {-1, -1, -1, -1}, {5, 1, 3, -1}};
-                int newperm[hope_env::MAX_CHAINS] = {0, 0, 0, 0, 0, 0, 0, 0};
-                bool taken[hope_env::MAX_CHAINS] = {};
-                for (int oi = 0; oi < 7; oi++) {
-                    const int r = order[oi];
+            // Assignment.  Roles busy at the same time: deferred step {caller, SEARCH0, CHAIN, OBS_LARGE}; joined step {caller, CHAIN,
+            // OBS_LARGE, OBS_SMALL}; two sub-chains of one class {SEARCH0, CHAIN, OBS_LARGE, OBS_SUB}.  Greedy in that order of importance:
+            // every role takes the free stream whose class collides with the fewest roles it must not share with; ties keep the hand-found
+            // table (so a box that shows nothing to gain gets exactly round 4's assignment).  Not for image handles (six busy streams on
+            // four queues: the measured table stays).
+            if (n_cls >= 2 && !(flags & HOPE_F_IMAGE)) {
+                static const int order[N_ROLES - 1] = {ROLE_SEARCH0, ROLE_CHAIN, ROLE_OBS_LARGE, ROLE_OBS_SMALL, ROLE_OBS_SUB, ROLE_IMAGE, ROLE_SPARE};
+                static const int conflicts[N_ROLES][4] = {
+                    /* ROLE_CALLER    */ {-1, -1, -1, -1},
+                    /* ROLE_CHAIN     */ {ROLE_CALLER, ROLE_SEARCH0, -1, -1},
+                    /* ROLE_IMAGE     */ {-1, -1, -1, -1},
+                    /* ROLE_OBS_LARGE */ {ROLE_CALLER, ROLE_SEARCH0, ROLE_CHAIN, -1},
+                    /* ROLE_OBS_SMALL */ {ROLE_CALLER, ROLE_CHAIN, ROLE_OBS_LARGE, -1},
+                    /* ROLE_SEARCH0   */ {ROLE_CALLER, -1, -1, -1},
+                    /* ROLE_SPARE     */ {-1, -1, -1, -1},
+                    /* ROLE_OBS_SUB   */ {ROLE_SEARCH0, ROLE_CHAIN, ROLE_OBS_LARGE, -1}};
+                int newperm[N_ROLES] = {0, 0, 0, 0, 0, 0, 0, 0};
+                bool taken[N_ROLES] = {};
+                for (const int r : order) {
                     int best = -1, best_cost = 1 << 30;
-                    for (int c = 1; c < hope_env::MAX_CHAINS; c++) {
+                    for (int c = 1; c < N_ROLES; c++) {
                         if (taken[c]) continue;
                         int cost = 0;
-                        for (int k = 0; k < 4; k++) {
-                            const int o = conflicts[r][k];
+                        for (const int o : conflicts[r]) {
                             if (o < 0) continue;
-                            const int oc = o == 0 ? cls[0] : (newperm[o] ? cls[newperm[o]] : -2);
+                            const int oc = o == ROLE_CALLER ? cls[0] : (newperm[o] ? cls[newperm[o]] : -2);
                             if (oc == cls[c]) cost += 4;
                         }
                         if (c != perm[r]) cost += 1;          // prefer the table's stream among equals
@@ -803,17 +772,12 @@ int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int devic
                     }
                     newperm[r] = best; taken[best] = true;
                 }
-                for (int r = 1; r < hope_env::MAX_CHAINS; r++) perm[r] = newperm[r];
+                for (int r = 1; r < N_ROLES; r++) perm[r] = newperm[r];
             }
         }
-        if (getenv("HOPE_DEBUG")) {
-            fprintf(stderr, "hope_env_create: stream of role 1..7 =");
-            for (int r = 1; r < hope_env::MAX_CHAINS; r++) fprintf(stderr, " %d(q%d)", perm[r], cls[perm[r]]);
-            fprintf(stderr, "; caller q%d; queue check %.2f ms\n", cls[0], h->queue_check_ms);
-        }
-        for (int r = 1; r < hope_env::MAX_CHAINS; r++) h->side[r] = created[perm[r]];
-        h->queue_of_role[0] = cls[0];
-        for (int r = 1; r < hope_env::MAX_CHAINS; r++) h->queue_of_role[r] = cls[perm[r]];
+        for (int r = 1; r < N_ROLES; r++) h->side[r] = created[perm[r]];
+        h->queue_of_role[ROLE_CALLER] = cls[0];
+        for (int r = 1; r < N_ROLES; r++) h->queue_of_role[r] = cls[perm[r]];
     }
     HIPCHK(hipDeviceSynchronize());
     { std::lock_guard<std::mutex> lk(g_live_m); g_live.insert(h); }
@@ -834,11 +798,9 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     DeviceGuard guard(h->device);
     drain_events(h);
     hipDeviceSynchronize();
-    for (hipEvent_t e : {h->ev_collect, h->ev_bev[0], h->ev_bev[1], h->ev_fork, h->ev_step[0], h->ev_step[1], h->ev_segs[0], h->ev_segs[1], h->ev_post[0], h->ev_post[1]}) if (e) hipEventDestroy(e);
-    for (int i = 0; i < hope_env::MAX_CHAINS; i++) {
-        if (h->ev_join[i]) hipEventDestroy(h->ev_join[i]);
-        if (h->side[i]) hipStreamDestroy(h->side[i]);
-    }
+    for (hipEvent_t e : {h->ev_collect, h->ev_bev[0], h->ev_bev[1], h->ev_fork, h->ev_step[0], h->ev_step[1], h->ev_segs[0], h->ev_segs[1], h->ev_post[0], h->ev_post[1],
+                         h->ev_chain1_done, h->ev_image_done, h->ev_obs_done[0], h->ev_obs_done[1], h->ev_search0_done}) if (e) hipEventDestroy(e);
+    for (hipStream_t q : h->side) if (q) hipStreamDestroy(q);
     if (h->pool_stream) hipStreamDestroy(h->pool_stream);
     for (hipEvent_t e : h->cold_ev) if (e) hipEventDestroy(e);
     if (h->cold_host) hipHostFree(h->cold_host);
@@ -908,7 +870,7 @@ int hope_debug_rs_log(int32_t* out, int cap, int32_t* n, int reset) {
 
 int hope_env_queue_check(hope_env_t* h, int32_t* queue_of_role, int32_t* n_queues, double* ms) {
     if (!h) return fail(HOPE_EINVAL, "hope_env_queue_check: null handle");
-    if (queue_of_role) for (int r = 0; r < hope_env::MAX_CHAINS; r++) queue_of_role[r] = h->queue_of_role[r];
+    if (queue_of_role) for (int r = 0; r < N_ROLES; r++) queue_of_role[r] = h->queue_of_role[r];
     if (n_queues) *n_queues = h->n_queues;
     if (ms) *ms = h->queue_check_ms;
     return HOPE_OK;
@@ -1095,15 +1057,119 @@ static int sync_cold(hope_env_t* h, hipStream_t s) {
     return HOPE_OK;
 }
 
-// Enqueues the launches of one step on `s`.  With a side stream `s2` (HOPE_F_OVERLAP) the two tile classes run
-// concurrently: fork -> { k_kinematics, k_env_step, k_rs_compact, k_rs_words, k_rs_validate of class 1 | of class 0 } -> join -> image.  Every class kernel is latency-bound per wave, so at
-// <= 16 k scenes per GPU (BASELINE config 4: 8 192) one class alone cannot fill the 1024 SIMDs.
+// ---- the step's launch plan ----
+// One chain of launches per tile class (scenes with few obstacles get a small LDS tile and therefore more resident waves):
+// [k_kinematics ->] k_env_step -> k_post, and with the search k_rs_compact -> k_rs_words -> k_rs_segs -> k_rs_validate.  The chains
+// share nothing but read-only data (own scene list, own queue counter, record slots filled from opposite ends), so with HOPE_F_OVERLAP
+// they run concurrently from the fork to the join: every class kernel is latency-bound per wave, and at <= 16 k scenes per GPU one
+// class alone cannot fill the 1024 SIMDs.  The form of the step is decided by these measured thresholds (steady ms per step):
+//
+// Two-launch step kernel (the motion launch, then the observation half on its own stream next to the search of the same class): from
+// 16 384 scenes (+4.5 % at 65 536 scenes, +3.7 % at 131 072, 0 at 16 384, -3 % at 8 192 and below: two more launches per class) ...
+constexpr int SPLIT_MIN_SCENES = 16384;
+// ... and from 32 768 scenes with pipelined steps (HOPE_DEFER_RS), where the one-launch form stays the faster one: 16 384 scenes
+// 0.249 vs 0.266 ms.  HOPE_SPLIT_MIN overrides both (read per call: the tests force the split at small sizes).
+constexpr int SPLIT_MIN_SCENES_DEFER = 32768;
+// One-launch form with the kinematics fused in (the step kernel's waves compute their scene's sub-step poses themselves): the step
+// is a chain of launch latencies there, and the kinematics launch cost the critical stream ~16 us plus a launch gap.  Only where the
+// GPU is far from full: the wave-per-scene form spends ~2x the vector instructions of k_kinematics' four lanes per scene (fused /
+// separate: 4 096 scenes 0.152 / 0.156, 8 192 0.186 / 0.176, 16 384 0.249 / 0.222).
+constexpr int FUSE_KIN_MAX_SCENES = 4096;
+// A batch whose scenes all sit in ONE tile class has one chain: no second stream, and none of the two-chain forms (observation half
+// on its own stream, pipelined steps).  Pipelined steps cut that class's list into two sub-chains where that was measured to pay
+// (profiles/r04_single_class_chains.txt; same bits: the chains share nothing): the small-tile class from 32 768 scenes (65 536
+// generated lots 0.790 -> 0.680 ms; below that the single chain in the one-launch form is the faster one), the large-tile class from
+// 4 096 to 32 768 scenes (4 096 Dragon-Lake scenes 0.190 -> 0.155 ms, 16 384: 0.278 -> 0.232; 65 536: 0.698 vs 0.717, not there).
+// {lo, hi} of the small-tile class, then of the large-tile class; HOPE_AUTO_CHAINS=lo0:hi0:lo1:hi1 moves them (read per call: tests).
+constexpr int AUTO_SUBS_RANGE[4] = {32768, 1 << 30, 4096, 32768};
+
+enum MotionKernel { MOTION_ONE_LAUNCH, MOTION_FUSED_KIN, MOTION_TIMING, MOTION_SPLIT, MOTION_PAIR };
+enum ObsKernel { OBS_IN_STEP, OBS_SPLIT, OBS_PAIR };     // OBS_IN_STEP: the one-launch step kernel computes the observation
+
+struct StepPlan {
+    struct Chain {
+        int c, a, b;              // tile class and the range [a, b) of its scene list
+        int tile_cap;             // LDS tile capacity of the class's launches
+        Role search, kin, obs;    // streams of the search launches, of the kinematics + motion launch, of the observation + k_post
+        bool on_caller;           // pipelined: this chain's env launches are on the caller's stream itself
+        bool post_on_search;      // k_post heads the search stream instead of following the observation launch
+        MotionKernel motion;
+        ObsKernel obs_kernel;
+    } chain[hope_env::MAX_CHAIN];
+    int n_chain;
+    bool want_rs;
+    bool fork;                    // two chains on their own streams: HOPE_F_OVERLAP and n_chain == 2
+    bool split;                   // two-launch step kernel
+    bool pipe;                    // pipelined (deferred) step: the search streams stay unjoined (HOPE_DEFER_RS)
+    bool pipe1;                   // pipelined with the one-launch step kernel
+    bool fuse_kin;                // one-launch step kernel with the kinematics fused in
+    bool auto_subs;               // two sub-chains of one tile class
+};
+
+// What one step enqueues (no HIP calls).
+static StepPlan plan_step(const hope_env_t* h, uint32_t stages, bool want_rs, bool overlap, int has_action, bool step_timing) {
+    StepPlan pl = {};
+    pl.want_rs = want_rs;
+    const int n_cls = h->max_obst > SMALL_TILE ? 2 : 1;
+    const bool obs = stages & HOPE_STAGE_OBS, defer_rs = stages & HOPE_DEFER_RS, img = stages & HOPE_STAGE_IMG;
+    int subs = 1;
+    if (overlap && want_rs && obs && defer_rs && !img && (h->cls_count[0] == 0) != (h->cls_count[1] == 0)) {
+        int range[4] = {AUTO_SUBS_RANGE[0], AUTO_SUBS_RANGE[1], AUTO_SUBS_RANGE[2], AUTO_SUBS_RANGE[3]};
+        if (const char* e = getenv("HOPE_AUTO_CHAINS")) sscanf(e, "%d:%d:%d:%d", range, range + 1, range + 2, range + 3);
+        const int c1 = h->cls_count[0] == 0 ? 1 : 0, cnt = h->cls_count[c1];
+        if (cnt >= range[2 * c1] && cnt <= range[2 * c1 + 1]) { subs = 2; pl.auto_subs = true; }
+    }
+    // chains with work, the large-tile class first (its chain is the longer one); two sub-chains only when the other class is empty
+    for (int c = n_cls - 1; c >= 0; c--)
+        for (int j = 0; j < subs; j++) {
+            const int a = (int)((long long)h->cls_count[c] * j / subs), b = (int)((long long)h->cls_count[c] * (j + 1) / subs);
+            if (b > a) {
+                StepPlan::Chain& ch = pl.chain[pl.n_chain++];
+                ch.c = c; ch.a = a; ch.b = b;
+                ch.tile_cap = (c == 0 && n_cls == 2) ? SMALL_TILE : h->max_obst;
+            }
+        }
+    pl.fork = overlap && pl.n_chain == 2;
+    const bool two_stream_forms = pl.fork && want_rs && obs && !step_timing;
+    const char* split_min = getenv("HOPE_SPLIT_MIN");
+    pl.split = two_stream_forms && h->n >= (split_min ? atoi(split_min) : defer_rs ? SPLIT_MIN_SCENES_DEFER : SPLIT_MIN_SCENES);
+    pl.pipe = two_stream_forms && defer_rs;
+    pl.pipe1 = pl.pipe && !pl.split;
+    pl.fuse_kin = h->n <= FUSE_KIN_MAX_SCENES && !pl.split && !step_timing;
+    const bool of64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
+    for (int i = 0; i < pl.n_chain; i++) {
+        StepPlan::Chain& ch = pl.chain[i];
+        // joined: the first chain on the caller's stream, the second on ROLE_CHAIN; pipelined: the search launches on ROLE_SEARCH0 /
+        // ROLE_CHAIN, so that step k + 1's kinematics and motion launch do not queue behind step k's validation kernel
+        ch.search = (pl.fork && i == 1) ? ROLE_CHAIN : pl.pipe ? ROLE_SEARCH0 : ROLE_CALLER;
+        // pipelined: the env launches of the class with MORE scenes are on the caller's stream itself -- its kernels are the step's
+        // critical cycle (kinematics -> motion -> observation -> the caller's next actions -> kinematics ...), and every hop between a
+        // library stream and the caller's costs that cycle 20-30 us (two hops per step: 0.648 -> 0.60 ms).  Not with the image, which
+        // runs on the caller's stream next to the observation launches; not for two sub-chains of one class (both would land on the
+        // caller's stream and serialise: 0.80 vs 0.68 ms).  (With exactly equal class counts both chains take the caller's stream.)
+        ch.on_caller = pl.pipe && !pl.auto_subs && !img && h->cls_count[ch.c] >= h->cls_count[1 - ch.c];
+        ch.obs = !(pl.split || pl.pipe1) ? ch.search : ch.on_caller ? ROLE_CALLER : (pl.auto_subs && i == 1) ? ROLE_OBS_SUB : (Role)(ROLE_OBS_LARGE + i);
+        ch.kin = pl.pipe ? ch.obs : ch.search;
+        // pipelined two-launch form: k_post, whose outputs the caller's stream joins too, runs at the head of the search stream
+        // instead of behind the observation launch (the search stream has slack, the env stream is the critical one).  In the
+        // one-launch form k_post stays behind the step kernel (8 192 scenes 0.205 vs 0.188 ms: the search chain is the longer one)
+        ch.post_on_search = pl.pipe && pl.split;
+        // small-tile class, moving step: two scenes per wave (hope_motion_pair.h, hope_obs_pair.h; STAGE_ONE_SCENE: the one-scene kernels)
+        const bool one_scene = stages & STAGE_ONE_SCENE;
+        if (pl.split) ch.motion = (ch.c == 0 && n_cls == 2 && (stages & HOPE_STAGE_MOTION) && has_action && !one_scene) ? MOTION_PAIR : MOTION_SPLIT;
+        else if (step_timing && !of64 && !af64) ch.motion = MOTION_TIMING;
+        else ch.motion = pl.fuse_kin ? MOTION_FUSED_KIN : MOTION_ONE_LAUNCH;
+        ch.obs_kernel = !pl.split ? OBS_IN_STEP : (ch.tile_cap == SMALL_TILE && !one_scene) ? OBS_PAIR : OBS_SPLIT;
+    }
+    return pl;
+}
+
+// Enqueues the launches of one step (plan_step) on the caller's stream `s` and the handle's role streams.
 static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* active, uint32_t stages, const hope_step_out* out,
                         hipStream_t s, bool overlap, int has_action, LaunchTimer* tm) {
     StepParams p;
     memset(&p, 0, sizeof(p));
-    static const uint32_t dbg_stages = getenv("HOPE_DEBUG_STAGES") ? (uint32_t)strtol(getenv("HOPE_DEBUG_STAGES"), nullptr, 0) : 0;   // profiling switches 0x1000 / 0x2000 (results invalid)
-    p.n = h->n; p.max_obst = h->max_obst; p.stages = stages | dbg_stages; p.has_action = has_action;
+    p.n = h->n; p.max_obst = h->max_obst; p.stages = stages; p.has_action = has_action;
     p.hflags = h->traj ? STEP_HF_TRAJ : 0;
     p.verts = h->verts; p.obb = h->obb; p.eflag = h->eflag; p.n_obst = h->n_obst; p.scene_c = h->scene_c; p.state = h->state; p.cs = h->cs; p.tstep = h->tstep;
     p.active = active; p.active_out = active ? h->active_snap : nullptr; p.kin = h->kin; p.actions = actions; p.post = h->post;
@@ -1112,145 +1178,42 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
     p.cold = h->cold_dev + h->cold_idx;                     // (sync_cold ran on the caller's stream before any launch of this step)
     const uint8_t* active_rs = active ? h->active_snap : nullptr;   // what the Reeds-Shepp chain reads instead of the caller's mask
     const bool of64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
-    dim3 block(WAVE);
-
-    // One chain of launches per tile class (scenes with few obstacles get a small LDS tile and therefore more resident
-    // waves): k_env_step -> k_rs_compact -> k_rs_words -> k_rs_validate.  The chains share nothing but read-only data
-    // (own scene list, own queue counter, record slots filled from opposite ends), so with a side stream they run
-    // concurrently from the fork after the kinematics to the join before the image.
+    const dim3 block(WAVE);
     static const bool step_timing = getenv("HOPE_STEP_TIMING") != nullptr;      // cycle accounting build (tools/step_timing.py)
-    const int n_cls = h->max_obst > SMALL_TILE ? 2 : 1;
     const bool want_rs = (stages & HOPE_STAGE_RS) && out->rs_word;
-    // chains: (class, sub-list) pairs with work, the large-tile class first (its chains are the longer ones)
-    struct Chain { int c, a, b, st; };                      // st: 0 = the caller's stream, k = side[k]
-    Chain chains[hope_env::MAX_CHAINS];
-    int n_chain = 0, n_streams = 1;
-    int subs = overlap ? h->sub_chains : 1;
-    // A batch whose scenes all sit in ONE tile class has one chain: no second stream, and none of the two-chain forms below (observation
-    // half on its own stream, pipelined steps).  Cut that class's list into two sub-chains where that was measured to pay for
-    // deferred steps (profiles/r04_single_class_chains.txt; same bits: the chains share nothing): the small-tile class from 32 768
-    // scenes (65 536 generated lots 0.790 -> 0.680 ms; below that the single chain in the one-launch form is the faster one), the
-    // large-tile class from 4 096 to 32 768 scenes (4 096 Dragon-Lake scenes 0.190 -> 0.155 ms, 16 384: 0.278 -> 0.232; 65 536: 0.698 vs 0.717, not there).
-    // HOPE_CHAINS=n overrides; HOPE_AUTO_CHAINS=lo0:hi0:lo1:hi1 moves the two ranges (tests force the form at small sizes).
-    bool auto_subs = false;
-    if (overlap && h->sub_chains_auto && want_rs && (stages & HOPE_STAGE_OBS) && (stages & HOPE_DEFER_RS) && !(stages & HOPE_STAGE_IMG) &&
-        (h->cls_count[0] == 0) != (h->cls_count[1] == 0)) {
-        int range[4] = {32768, 1 << 30, 4096, 32768};
-        if (const char* e = getenv("HOPE_AUTO_CHAINS")) sscanf(e, "%d:%d:%d:%d", range, range + 1, range + 2, range + 3);   // (read per call)
-        const int c1 = h->cls_count[0] == 0 ? 1 : 0, cnt = h->cls_count[c1];
-        if (cnt >= range[2 * c1] && cnt <= range[2 * c1 + 1]) { subs = 2; auto_subs = true; }
-    }
-    static const int balance = getenv("HOPE_BALANCE") ? atoi(getenv("HOPE_BALANCE")) : 100;
-    // experiment: 1 = the chain of the class with more scenes is enqueued first; 2 = and the other chain starts only when the
-    // first chain's motion launch is done (its kinematics / motion kernels then do not share the GPU with the critical ones)
-    const int order_mode = getenv("HOPE_ORDER") ? atoi(getenv("HOPE_ORDER")) : 0;
-    if (overlap && subs == 1 && n_cls == 2 && balance < 100 && h->cls_count[0] > 0 && h->cls_count[1] > 0) {
-        // two streams, three chains: the large-tile class, then the tail of the small-tile class behind it on the side stream,
-        // the head of the small-tile class on the caller's stream -- so that both streams finish together
-        const int cut = (int)((long long)h->cls_count[0] * balance / 100);
-        chains[n_chain++] = {1, 0, h->cls_count[1], 1};
-        if (cut > 0) chains[n_chain++] = {0, 0, cut, 0};
-        if (cut < h->cls_count[0]) chains[n_chain++] = {0, cut, h->cls_count[0], 1};
-        n_streams = 2;
-    } else {
-        // the class with more scenes first: its chain is the step's critical path (HOPE_ORDER=0: the large-tile class first)
-        const bool big_first = n_cls == 2 && order_mode > 0 && h->cls_count[0] > h->cls_count[1];
-        for (int cc = n_cls - 1; cc >= 0; cc--) {
-            const int c = big_first ? (n_cls - 1 - cc) : cc;
-            for (int j = 0; j < subs; j++) {
-                const int a = (int)((long long)h->cls_count[c] * j / subs), b = (int)((long long)h->cls_count[c] * (j + 1) / subs);
-                if (b > a) { chains[n_chain] = {c, a, b, overlap ? n_chain : 0}; n_chain++; }
-            }
-        }
-        n_streams = overlap ? n_chain : 1;
-    }
-    const bool fork = overlap && n_streams > 1;
-    // the observation half of the step kernel on its own stream, next to the Reeds-Shepp kernels of the same class
-    static const bool no_split = getenv("HOPE_NO_SPLIT") != nullptr;
-    // (measured: +4.5 % at 65 536 scenes, +3.7 % at 131 072, 0 at 16 384, -3 % at 8 192 and below: two more launches per class)
-    const char* split_min = getenv("HOPE_SPLIT_MIN");      // (read per call: the tests force the split at small sizes)
-    // (with pipelined steps -- HOPE_DEFER_RS, below -- the one-launch form stays the faster one up to 32 768 scenes: 16 384 scenes
-    // 0.249 vs 0.266 ms)
-    static const bool pipe_env0 = !(getenv("HOPE_PIPE") && atoi(getenv("HOPE_PIPE")) == 0);
-    const bool split = fork && n_chain == 2 && want_rs && (stages & HOPE_STAGE_OBS) && !step_timing && !no_split &&
-                       h->n >= (split_min ? atoi(split_min) : ((stages & HOPE_DEFER_RS) && pipe_env0) ? 32768 : 16384);
-    // HOPE_DEFER_RS: both chains on library streams, the caller's stream joins the observation half only (hope_env.h)
-    // (measured: 32 768 scenes 0.433 -> 0.426 ms, 65 536 0.681 -> 0.669; 16 384 0.322 -> 0.361: below 32 768 the joined form)
-    // Round 4: with pipelined steps (below) the bit pays at every batch size, in the one-launch form of the step kernel too (pipe1:
-    // env stream = k_kinematics -> k_env_step, search stream = k_post -> k_rs_compact -> ... -> k_rs_validate_f): a small batch is
-    // launch-latency bound, seven dependent launches per class, and overlapping the search of step k with the env launches of step
-    // k + 1 hides most of that chain (8 192 scenes 0.266 -> see RESULTS.md).  HOPE_DEFER_MIN restores a threshold.
-    static const bool pipe_env = !(getenv("HOPE_PIPE") && atoi(getenv("HOPE_PIPE")) == 0);
-    const char* defer_min = getenv("HOPE_DEFER_MIN");
-    const bool defer_ok = fork && n_chain == 2 && want_rs && (stages & HOPE_STAGE_OBS) && !step_timing && (stages & HOPE_DEFER_RS) &&
-                          h->n >= (defer_min ? atoi(defer_min) : pipe_env ? 0 : 32768);
-    const bool pipe1 = defer_ok && !split && pipe_env;      // pipelined steps with the one-launch step kernel
-    const bool defer = (split && defer_ok) || pipe1;
-    if (!defer) { int rcj = join_rs(h, s); if (rcj != HOPE_OK) return rcj; }    // (a deferred step's launches follow the unjoined ones on the same streams)
-    // PIPELINED steps (round 4; with HOPE_DEFER_RS, HOPE_PIPE=0 switches it off): each tile class runs on TWO library streams --
-    //   env stream  : k_kinematics -> k_env_step<motion> -> k_env_step<observation> -> k_post     (what the caller's stream joins)
+    const StepPlan pl = plan_step(h, stages, want_rs, overlap, has_action, step_timing);
+    auto stream = [&](Role r) { return r == ROLE_CALLER ? s : h->side[r]; };
+
+    if (!pl.pipe) { int rcj = join_rs(h, s); if (rcj != HOPE_OK) return rcj; }    // (a deferred step's launches follow the unjoined ones on the same streams)
+    // PIPELINED steps (HOPE_DEFER_RS): each chain runs on TWO streams --
+    //   env stream   : k_kinematics -> k_env_step<motion> -> k_env_step<observation> -> k_post     (what the caller's stream joins)
     //   search stream: [motion done] k_rs_compact -> k_rs_words -> k_rs_segs -> k_rs_validate      (hope_env_wait_rs / never)
-    // so that step k + 1's kinematics and motion launch do not queue behind step k's validation kernel, the longest launch of the
-    // step: they only wait for step k's k_rs_segs (the last reader of `state` / `post` on the search stream) and -- through the
-    // caller's stream -- for its observation.  The search of step k may then read obstacle tiles that step k + 1's episode
-    // turnover is rewriting: only for scenes whose episode ended in step k + 1, whose search result nobody can read any more
-    // (k_rs_compact of step k + 1 clears it, after the validation kernel, on the same stream), and all reads stay inside the
-    // scene's own tile slots.  The queue counter alternates between two words per chain (the motion launch of step k + 1 zeroes
-    // the one step k + 1 uses while step k's validation blocks are still reading theirs).
-    const bool pipe = defer && pipe_env && n_chain == 2;
+    // so that step k + 1's kinematics and motion launch only wait for step k's k_rs_compact (the last reader of `state` / `post` on the
+    // search stream) and -- through the caller's stream -- for its observation.  The search of step k may then read obstacle tiles
+    // that step k + 1's episode turnover is rewriting: only for scenes whose episode ended in step k + 1, whose search result nobody
+    // can read any more (k_rs_compact of step k + 1 clears it, after the validation kernel, on the same stream), and all reads stay
+    // inside the scene's own tile slots.  The queue counter alternates between two words per chain (the motion launch of step k + 1
+    // zeroes the one step k + 1 uses while step k's validation blocks are still reading theirs).
     if (want_rs) h->rs_parity ^= 1;
-    if (fork) {
+    if (pl.fork) {
         HIPCHK(hipEventRecord(h->ev_fork, s));
-        for (int i = 1; i < n_streams; i++) HIPCHK(hipStreamWaitEvent(h->side[i], h->ev_fork, 0));
-        if (defer) HIPCHK(hipStreamWaitEvent(h->side[hope_env::RS_SIDE], h->ev_fork, 0));
+        HIPCHK(hipStreamWaitEvent(h->side[ROLE_CHAIN], h->ev_fork, 0));
+        if (pl.pipe) HIPCHK(hipStreamWaitEvent(h->side[ROLE_SEARCH0], h->ev_fork, 0));
     }
-    bool joined_on_caller[2] = {false, false}, post_on_rs[2] = {false, false};
-    hipStream_t obs_stream[2] = {nullptr, nullptr};
     // every chain's motion launch is followed by its ev_step record: those two events cover the pool's readers (the pool upload waits
     // for them instead of a per-step record on the caller's stream)
     h->last_via_steps = false;
-    for (int i = 0; i < n_chain; i++) {
-        const Chain& ch = chains[i];
+    for (int i = 0; i < pl.n_chain; i++) {
+        const StepPlan::Chain& ch = pl.chain[i];
         const int c = ch.c;
-        hipStream_t sc = (fork && ch.st > 0) ? h->side[ch.st] : defer ? h->side[hope_env::RS_SIDE] : s;
-        int32_t* counter = h->rs_count + i + hope_env::MAX_CHAINS * h->rs_parity;
-        // two-launch form: everything the search does not wait for goes to its own stream.  (Experiment knobs: HOPE_OBS_SIDE0 / 1 =
-        // which library stream carries the observation half of chain 0 / 1, HOPE_OBS_WPC0 / 1 = its waves per CU, enforced
-        // through the LDS request.)
-        static const int obs_side[2] = {getenv("HOPE_OBS_SIDE0") ? atoi(getenv("HOPE_OBS_SIDE0")) : 3, getenv("HOPE_OBS_SIDE1") ? atoi(getenv("HOPE_OBS_SIDE1")) : 4};
-        static const int obs_wpc[2] = {getenv("HOPE_OBS_WPC0") ? atoi(getenv("HOPE_OBS_WPC0")) : 0, getenv("HOPE_OBS_WPC1") ? atoi(getenv("HOPE_OBS_WPC1")) : 0};
-        hipStream_t so = (split || pipe1) ? h->side[(auto_subs && (i & 1)) ? 7 : std::max(1, std::min(hope_env::MAX_CHAINS - 1, obs_side[i & 1]))] : sc;
-        // pipelined: the env stream of the class with MORE scenes is the caller's stream itself -- its kernels are the step's critical
-        // cycle (kinematics -> motion -> observation -> the caller's next actions -> kinematics ...), and every hop between a library
-        // stream and the caller's costs that cycle 20-30 us (two hops per step: 0.648 -> 0.60 ms).  Not with the image, which
-        // runs on the caller's stream next to the observation launches.
-        static const bool pipe_on_caller = !(getenv("HOPE_PIPE_CALLER") && atoi(getenv("HOPE_PIPE_CALLER")) == 0);
-        // (two sub-chains of one class: neither -- both would land on the caller's stream and serialise: 0.80 vs 0.68 ms)
-        const bool on_caller = pipe && pipe_on_caller && !auto_subs && !(stages & HOPE_STAGE_IMG) && h->cls_count[c] >= h->cls_count[1 - c];
-        if (on_caller) so = s;
-        // ... and k_post, whose outputs the caller's stream joins too, runs at the head of the search stream instead of behind the
-        // observation launch (the search stream has slack, the env stream is the critical one)
-        // (two-launch form only: in the one-launch form of small batches k_post stays behind the step kernel on the env stream --
-        // 8 192 scenes 0.205 vs 0.188 ms -- the search chain is the longer one there; HOPE_POST_SEARCH=0 / 1 forces either)
-        static const int post_on_search = getenv("HOPE_POST_SEARCH") ? atoi(getenv("HOPE_POST_SEARCH")) : -1;
-        const bool post_rs = pipe && want_rs && (post_on_search < 0 ? split : post_on_search != 0);
-        if (i < 2) { joined_on_caller[i] = on_caller; post_on_rs[i] = post_rs; obs_stream[i] = so; }
-        hipStream_t sk = pipe ? so : sc;                        // the stream of the kinematics and the motion launch
-        if (pipe && !on_caller) HIPCHK(hipStreamWaitEvent(sk, h->ev_fork, 0));
-        p.tile_cap = (c == 0 && n_cls == 2) ? SMALL_TILE : h->max_obst;
+        const hipStream_t sc = stream(ch.search), sk = stream(ch.kin), so = stream(ch.obs);
+        int32_t* counter = h->rs_count + i + hope_env::MAX_CHAIN * h->rs_parity;
+        if (pl.pipe && !ch.on_caller) HIPCHK(hipStreamWaitEvent(sk, h->ev_fork, 0));
+        p.tile_cap = ch.tile_cap;
         p.scene_list = h->cls_list[c] + ch.a;
         p.n_list = ch.b - ch.a;
         p.rs_count_zero = want_rs ? counter : nullptr;
-        if (order_mode >= 2 && fork && n_chain == 2 && i == 1 && (split || (stages & HOPE_STAGE_IMG)))
-            HIPCHK(hipStreamWaitEvent(sc, h->ev_step[0], 0));   // staggered: behind the first chain's motion launch
-        // one-launch form (small batches): the step kernel's waves compute their scene's sub-step poses themselves -- the step is a
-        // chain of launch latencies there, and the kinematics launch cost the critical stream ~16 us plus a launch gap
-        // Only where the GPU is far from full: the wave-per-scene form spends ~2x the vector instructions of k_kinematics' four
-        // lanes per scene (measured, steady ms per step, fused / separate: 4 096 scenes 0.152 / 0.156, 8 192 0.186 / 0.176,
-        // 16 384 0.249 / 0.222).  HOPE_FUSE_KIN = largest batch that takes it (0: never).
-        static const int fuse_kin_max = getenv("HOPE_FUSE_KIN") ? atoi(getenv("HOPE_FUSE_KIN")) : 4096;
-        const bool fuse_kin = h->n <= fuse_kin_max && !split && !step_timing;
-        if ((stages & HOPE_STAGE_MOTION) && has_action && !fuse_kin) {       // this class's sub-step poses head its chain
+        if ((stages & HOPE_STAGE_MOTION) && has_action && !pl.fuse_kin) {       // this chain's sub-step poses head it
             dim3 kg((p.n_list + KIN_SCENES_PER_BLOCK - 1) / KIN_SCENES_PER_BLOCK);
             if (tm) tm->begin(HOPE_K_KINEMATICS, sk);
             if (af64) hipLaunchKernelGGL((k_kinematics<double>), kg, block, 0, sk, p.n_list, p.scene_list, h->state, actions, active, stages, h->scene_c, h->kin);
@@ -1258,56 +1221,44 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
             if (tm) tm->end(sk);
         }
         const dim3 grid(p.n_list);
-        size_t lds = step_lds_bytes(p.tile_cap);
-        // pipelined: the last step's k_rs_compact / k_rs_words / k_rs_segs (search stream) read `post` and `state`, which the motion
-        // launch rewrites
-        if (pipe) HIPCHK(hipStreamWaitEvent(sk, h->ev_segs[i], 0));
+        const size_t lds = step_lds_bytes(p.tile_cap);
+        // pipelined: the last step's k_rs_compact (search stream) reads `post` and `state`, which the motion launch rewrites
+        if (pl.pipe) HIPCHK(hipStreamWaitEvent(sk, h->ev_segs[i], 0));
         if (tm) tm->begin(HOPE_K_STEP, sk);
-        // small-tile class, moving step: two scenes per wave (hope_motion_pair.h; HOPE_MOTION_PAIR=0 or stage bit 0x8000: the one-scene kernel)
-        static const bool motion_pair = !(getenv("HOPE_MOTION_PAIR") && atoi(getenv("HOPE_MOTION_PAIR")) == 0);
-        if (split && motion_pair && c == 0 && n_cls == 2 && p.tile_cap == SMALL_TILE && (stages & HOPE_STAGE_MOTION) && has_action && !(stages & 0x8000))
-            hipLaunchKernelGGL(k_motion_pair, dim3((p.n_list + 1) / 2), block, MP_LDS_BYTES, sk, p);
-        else if (split) launch_env_step<1>(of64, af64, grid, block, lds, sk, p);
-        else if (step_timing && !of64 && !af64) hipLaunchKernelGGL((k_env_step<float, float, true>), grid, block, lds, sk, p);
-        else if (fuse_kin) launch_env_step<0, true>(of64, af64, grid, block, lds, sk, p);
-        else launch_env_step<0>(of64, af64, grid, block, lds, sk, p);
+        switch (ch.motion) {
+        case MOTION_PAIR: hipLaunchKernelGGL(k_motion_pair, dim3((p.n_list + 1) / 2), block, MP_LDS_BYTES, sk, p); break;
+        case MOTION_SPLIT: launch_env_step<1>(of64, af64, grid, block, lds, sk, p); break;
+        case MOTION_TIMING: hipLaunchKernelGGL((k_env_step<float, float, true>), grid, block, lds, sk, p); break;
+        case MOTION_FUSED_KIN: launch_env_step<0, true>(of64, af64, grid, block, lds, sk, p); break;
+        case MOTION_ONE_LAUNCH: launch_env_step<0>(of64, af64, grid, block, lds, sk, p); break;
+        }
         if (tm) tm->end(sk);
-        if (fork && n_chain == 2 && (split || pipe || (stages & HOPE_STAGE_IMG))) { HIPCHK(hipEventRecord(h->ev_step[i], sk)); h->last_via_steps = true; }   // poses final
-        if (split && !pipe) HIPCHK(hipStreamWaitEvent(so, h->ev_step[i], 0));
-        // k_post BEHIND the observation half on that stream: nothing waits for its outputs before the join, the observation is the
-        // long launch (0.675 -> 0.669 ms; HOPE_POST_LAST=0: the round-3 order)
-        static const bool post_last = !(getenv("HOPE_POST_LAST") && atoi(getenv("HOPE_POST_LAST")) == 0);
-        auto launch_post = [&]() {                              // scalar outputs, reward / target arithmetic: one lane per scene
+        if (pl.fork && (pl.split || pl.pipe || (stages & HOPE_STAGE_IMG))) { HIPCHK(hipEventRecord(h->ev_step[i], sk)); h->last_via_steps = true; }   // poses final
+        if (pl.split && !pl.pipe) HIPCHK(hipStreamWaitEvent(so, h->ev_step[i], 0));
+        auto launch_post = [&](hipStream_t sp) {                // scalar outputs, reward / target arithmetic: one lane per scene
             dim3 pg((p.n_list + WAVE - 1) / WAVE);
-            if (tm) tm->begin(HOPE_K_POST, so);
-            if (of64) hipLaunchKernelGGL((k_post<double>), pg, block, 0, so, p.n_list, p.scene_list, active, stages, h->scene_c, h->state, h->post, h->rs_flag, *out);
-            else hipLaunchKernelGGL((k_post<float>), pg, block, 0, so, p.n_list, p.scene_list, active, stages, h->scene_c, h->state, h->post, h->rs_flag, *out);
-            if (tm) tm->end(so);
+            if (tm) tm->begin(HOPE_K_POST, sp);
+            if (of64) hipLaunchKernelGGL((k_post<double>), pg, block, 0, sp, p.n_list, p.scene_list, active, stages, h->scene_c, h->state, h->post, h->rs_flag, *out);
+            else hipLaunchKernelGGL((k_post<float>), pg, block, 0, sp, p.n_list, p.scene_list, active, stages, h->scene_c, h->state, h->post, h->rs_flag, *out);
+            if (tm) tm->end(sp);
         };
-        if (!(split && post_last) && !post_rs) launch_post();
-        if (split) {
+        if (!pl.split) launch_post(so);
+        else {
             if (tm) tm->begin(HOPE_K_STEP, so);
-            const size_t lds_obs = obs_wpc[i & 1] > 0 ? std::max(lds, (size_t)((158 * 1024 / obs_wpc[i & 1]) & ~255)) : lds;
-            // small-tile class: two scenes per wave (hope_obs_pair.h; HOPE_OBS_PAIR=0: the one-scene kernel, its reference)
-            static const bool obs_pair = !(getenv("HOPE_OBS_PAIR") && atoi(getenv("HOPE_OBS_PAIR")) == 0);
-            if (obs_pair && p.tile_cap == SMALL_TILE && !(stages & 0x8000)) {          // (0x8000: A/B switch of the tests, one-scene kernel)
-                const dim3 pgrid((p.n_list + 1) / 2);
-                const size_t lds_pair = obs_wpc[i & 1] > 0 ? std::max(OP_LDS_BYTES, (size_t)((158 * 1024 / obs_wpc[i & 1]) & ~255)) : OP_LDS_BYTES;
-                if (of64) hipLaunchKernelGGL((k_obs_pair<double>), pgrid, block, lds_pair, so, p);
-                else hipLaunchKernelGGL((k_obs_pair<float>), pgrid, block, lds_pair, so, p);
-            } else
-            launch_env_step<2>(of64, af64, grid, block, lds_obs, so, p);
+            if (ch.obs_kernel == OBS_PAIR) {
+                if (of64) hipLaunchKernelGGL((k_obs_pair<double>), dim3((p.n_list + 1) / 2), block, OP_LDS_BYTES, so, p);
+                else hipLaunchKernelGGL((k_obs_pair<float>), dim3((p.n_list + 1) / 2), block, OP_LDS_BYTES, so, p);
+            } else launch_env_step<2>(of64, af64, grid, block, lds, so, p);
             if (tm) tm->end(so);
-            if (post_last && !post_rs) launch_post();
-            if (!on_caller) HIPCHK(hipEventRecord(h->ev_join[3 + i], so));   // (the event index stays 3 + i whatever stream carries the launch)
-        } else if (pipe1 && !on_caller) HIPCHK(hipEventRecord(h->ev_join[3 + i], so));     // one-launch form: the observation is part of it
+            // k_post BEHIND the observation half on that stream: nothing waits for its outputs before the join, the observation is
+            // the long launch (0.675 -> 0.669 ms)
+            if (!ch.post_on_search) launch_post(so);
+        }
+        if ((pl.split || pl.pipe1) && !ch.on_caller) HIPCHK(hipEventRecord(h->ev_obs_done[i], so));
         if (!want_rs) continue;
-        if (pipe) HIPCHK(hipStreamWaitEvent(sc, h->ev_step[i], 0));  // the search stream starts behind this step's motion launch
-        if (post_rs) {
-            hipStream_t keep = so;
-            so = sc;                                                  // (launch_post launches on `so`)
-            launch_post();
-            so = keep;
+        if (pl.pipe) HIPCHK(hipStreamWaitEvent(sc, h->ev_step[i], 0));  // the search stream starts behind this step's motion launch
+        if (ch.post_on_search) {
+            launch_post(sc);
             HIPCHK(hipEventRecord(h->ev_post[i], sc));
         }
         int32_t* qlist = h->rs_list + (size_t)c * h->n + ch.a;       // this chain's part of the class's queue storage
@@ -1322,15 +1273,11 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
         }
         if (tm) tm->end(sc);
         // pipelined steps: the next step's motion launch rewrites `state` / `post` (and, on an episode turnover, the scene constants),
-        // which k_post and k_rs_compact are the last to read -- k_rs_words / k_rs_segs work from k_rs_compact's rows (RS_IN_WORDS).
-        // (Rounds 4-5a waited for k_rs_segs: at small batches the step's critical cycle was motion -> compact -> words -> segs ->
-        // motion; HOPE_PIPE_AFTER=segs restores that for A/B runs.)
-        static const bool after_segs = getenv("HOPE_PIPE_AFTER") && !strcmp(getenv("HOPE_PIPE_AFTER"), "segs");
-        if (pipe && !after_segs) HIPCHK(hipEventRecord(h->ev_segs[i], sc));
+        // which k_post and k_rs_compact are the last to read -- k_rs_words / k_rs_segs work from k_rs_compact's rows (RS_IN_WORDS)
+        if (pl.pipe) HIPCHK(hipEventRecord(h->ev_segs[i], sc));
         RsParams r;
         r.n = h->n; r.max_obst = h->max_obst; r.obs_f64 = of64;
-        static const int prio_front = getenv("HOPE_PRIO_FRONT") ? atoi(getenv("HOPE_PRIO_FRONT")) : 0;
-        r.prio_front = prio_front;
+        r.prio_front = 0;
         r.tile_cap = p.tile_cap;
         r.max_queue = p.n_list;
         r.slot_base = (c == 0) ? ch.a : h->n - 1 - ch.a;    // the two classes fill the record storage from both ends
@@ -1342,7 +1289,7 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
         r.surv_count = h->rs_surv_count + i;
         r.surv_list = h->rs_surv + (size_t)c * h->n + ch.a;
         r.rs_word = out->rs_word; r.rs_lengths = out->rs_lengths;
-        HIPCHK(launch_rs_search(r, sc, tm, (pipe && after_segs) ? h->ev_segs[i] : nullptr));
+        HIPCHK(launch_rs_search(r, sc, tm));
     }
     HIPCHK(hipGetLastError());
     if (stages & HOPE_STAGE_IMG) {
@@ -1353,53 +1300,43 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
         b.legacy_list = h->bev_legacy;
         // with auto-reset every scene shows its NEW episode's first observation, like lidar / action_mask / target
         b.active = active;
-        b.debug = (stages >> 12) & 0xF;
-        if (const char* e_ = getenv("HOPE_BEV_DEBUG")) b.debug |= atoi(e_);   // (profiling) further switches: 16 no block cache, 64 no image stores
+        b.debug = 0;
+        if (const char* e_ = getenv("HOPE_BEV_DEBUG")) b.debug |= atoi(e_);   // (profiling switches, hope_bev.hip: 16 no block cache, 64 no image stores, ...)
         if (getenv("HOPE_BEV_LEGACY")) b.debug |= 32;          // (tests) the per-tile raster of the moving boxes instead of the trajectory layer
-        if (fork && n_chain == 2) {
+        if (pl.fork) {
             // the image depends on the step kernels only (pose, trajectory ring), not on the Reeds-Shepp search: render it on
-            // a third stream while the two chains run k_rs_words / k_rs_validate
-            // (with HOPE_DEFER_RS both chains run on library streams and the caller's stream is idle during the step: the image,
-            // which the caller waits for anyway, goes there -- the third library stream shares a hardware queue with a chain)
-            hipStream_t si = defer ? s : h->side[2];
+            // ROLE_IMAGE while the two chains run k_rs_words / k_rs_validate.  Pipelined steps: both chains run on library streams and
+            // the caller's stream is idle during the step: the image, which the caller waits for anyway, goes there, and the static-layer
+            // rebuild goes to ROLE_IMAGE
+            const hipStream_t si = pl.pipe ? s : h->side[ROLE_IMAGE];
             HIPCHK(hipStreamWaitEvent(si, h->ev_step[0], 0));
             HIPCHK(hipStreamWaitEvent(si, h->ev_step[1], 0));
-            // (pipelined steps: the image is on the caller's stream and the third library stream is free for the layer rebuild)
-            static const bool bev_side = !(getenv("HOPE_BEV_SIDE") && atoi(getenv("HOPE_BEV_SIDE")) == 0);
-            if (defer && bev_side && h->side[2] && h->ev_bev[0]) HIPCHK(launch_bev_image(b, si, tm, h->side[2], h->ev_bev[0], h->ev_bev[1]));
+            if (pl.pipe) HIPCHK(launch_bev_image(b, si, tm, h->side[ROLE_IMAGE], h->ev_bev[0], h->ev_bev[1]));
             else HIPCHK(launch_bev_image(b, si, tm));
-            HIPCHK(hipEventRecord(h->ev_join[2], si));
-        } else {
-            if (fork) for (int i = 1; i < n_streams; i++) { HIPCHK(hipEventRecord(h->ev_join[i], h->side[i])); HIPCHK(hipStreamWaitEvent(s, h->ev_join[i], 0)); }
-            if (split) for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(s, h->ev_join[3 + i], 0));
-            HIPCHK(launch_bev_image(b, s, tm));
-            return HOPE_OK;
-        }
+            HIPCHK(hipEventRecord(h->ev_image_done, si));
+        } else HIPCHK(launch_bev_image(b, s, tm));           // (no fork: every launch of the step is on the caller's stream)
     }
-    if (fork) {
-        if (defer) {                                            // the chains stay unjoined: hope_env_wait_rs / the next step
-            HIPCHK(hipEventRecord(h->ev_join[1], h->side[1]));
-            HIPCHK(hipEventRecord(h->ev_join[hope_env::RS_SIDE], h->side[hope_env::RS_SIDE]));
-            h->rs_pending = true;
-        } else
-            for (int i = 1; i < n_streams; i++) { HIPCHK(hipEventRecord(h->ev_join[i], h->side[i])); HIPCHK(hipStreamWaitEvent(s, h->ev_join[i], 0)); }
-        if ((stages & HOPE_STAGE_IMG) && n_chain == 2) HIPCHK(hipStreamWaitEvent(s, h->ev_join[2], 0));
-        if (split || pipe1) {
-            // Round 6: every event the caller's stream waits for or records is a packet in ITS queue, in front of the next step's
-            // kinematics -- the head of the step's critical cycle: three waits + two records made a 50 us hole behind the observation
-            // launch (profiles/r05_step_timeline_pipelined.txt).  With one chain on the caller's stream the OTHER chain's observation
-            // stream -- it has slack -- waits for the two k_post launches and records ONE event for the caller (HOPE_JOIN_COLLECT=0: the
-            // round-5 joins).
-            static const bool collect_on = !(getenv("HOPE_JOIN_COLLECT") && atoi(getenv("HOPE_JOIN_COLLECT")) == 0);
-            if (collect_on && h->ev_collect && n_chain == 2 && joined_on_caller[0] != joined_on_caller[1]) {
-                const int o = joined_on_caller[0] ? 1 : 0;
-                for (int i = 0; i < 2; i++) if (post_on_rs[i]) HIPCHK(hipStreamWaitEvent(obs_stream[o], h->ev_post[i], 0));
-                HIPCHK(hipEventRecord(h->ev_collect, obs_stream[o]));
-                HIPCHK(hipStreamWaitEvent(s, h->ev_collect, 0));
-            } else for (int i = 0; i < 2; i++) {
-                if (!joined_on_caller[i]) HIPCHK(hipStreamWaitEvent(s, h->ev_join[3 + i], 0));
-                if (post_on_rs[i]) HIPCHK(hipStreamWaitEvent(s, h->ev_post[i], 0));
-            }
+    if (!pl.fork) return HOPE_OK;
+    HIPCHK(hipEventRecord(h->ev_chain1_done, h->side[ROLE_CHAIN]));
+    if (pl.pipe) {                                          // the search streams stay unjoined: hope_env_wait_rs / the next step
+        HIPCHK(hipEventRecord(h->ev_search0_done, h->side[ROLE_SEARCH0]));
+        h->rs_pending = true;
+    } else HIPCHK(hipStreamWaitEvent(s, h->ev_chain1_done, 0));
+    if (stages & HOPE_STAGE_IMG) HIPCHK(hipStreamWaitEvent(s, h->ev_image_done, 0));
+    if (pl.split || pl.pipe1) {
+        // Round 6: every event the caller's stream waits for or records is a packet in ITS queue, in front of the next step's
+        // kinematics -- the head of the step's critical cycle: three waits + two records made a 50 us hole behind the observation
+        // launch (profiles/r05_step_timeline_pipelined.txt).  With one chain on the caller's stream the OTHER chain's observation
+        // stream -- it has slack -- waits for the two k_post launches and records ONE event for the caller.
+        const StepPlan::Chain* ch = pl.chain;
+        if (ch[0].on_caller != ch[1].on_caller) {
+            const hipStream_t so = stream(ch[ch[0].on_caller ? 1 : 0].obs);
+            for (int i = 0; i < 2; i++) if (ch[i].post_on_search) HIPCHK(hipStreamWaitEvent(so, h->ev_post[i], 0));
+            HIPCHK(hipEventRecord(h->ev_collect, so));
+            HIPCHK(hipStreamWaitEvent(s, h->ev_collect, 0));
+        } else for (int i = 0; i < 2; i++) {
+            if (!ch[i].on_caller) HIPCHK(hipStreamWaitEvent(s, h->ev_obs_done[i], 0));
+            if (ch[i].post_on_search) HIPCHK(hipStreamWaitEvent(s, h->ev_post[i], 0));
         }
     }
     return HOPE_OK;

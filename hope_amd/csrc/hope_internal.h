@@ -6,6 +6,12 @@
 
 namespace hope {
 
+// Internal hope_env_step stage bits (reserved in hope_env.h; tests and tools only, never the image kernel's switches):
+constexpr uint32_t STAGE_NO_BEAMS = 0x1000;    // profiling: the lidar skips its beam loop (results invalid)
+constexpr uint32_t STAGE_NO_MASK = 0x2000;     // profiling: no action mask (results invalid)
+constexpr uint32_t STAGE_NO_CULL = 0x4000;     // A/B: the lidar tests every obstacle edge (same results)
+constexpr uint32_t STAGE_ONE_SCENE = 0x8000;   // A/B: the one-scene kernels instead of the pair kernels (same results)
+
 // One Reeds-Shepp word as the validation kernel reads it (64 B)
 struct RsWord {
     double len[5];   // normalised (curvature-1) signed lengths
@@ -102,7 +108,7 @@ struct BevParams {
     int* scratch;             // [n][BEV_SCENE_INTS] map + box headers + span tables (k_bev_prep -> k_bev_image)
     const uint8_t* active;    // [n] or null
     uint8_t* img;             // [n][3][64][64]
-    int debug;                // internal profiling switches (stages bits 0x1000.. >> 12)
+    int debug;                // internal profiling switches (HOPE_BEV_DEBUG; 32: HOPE_BEV_LEGACY)
 };
 
 // optional per-launch profiling hook: begin(kind) / end() bracket ONE kernel launch
@@ -111,7 +117,7 @@ struct LaunchTimer {
     virtual void end(hipStream_t s) = 0;
 };
 // launches the Reeds-Shepp feasibility kernels over the scenes queued in rs_list (hope_rs.hip)
-hipError_t launch_rs_search(const RsParams& p, hipStream_t stream, LaunchTimer* timer, hipEvent_t after_segs = nullptr);   // one tile class; after_segs: recorded behind k_rs_segs
+hipError_t launch_rs_search(const RsParams& p, hipStream_t stream, LaunchTimer* timer);   // one tile class
 hipError_t rs_prof_read(unsigned long long* out /*[16]*/, int reset);   // HOPE_RS_TIMING cycle accounting
 hipError_t rs_init_tables();                                              // k_rs_validate_f's sample table, once per device (hope_env_create)
 hipError_t rs_fstat_read(unsigned long long* out /*[16]*/, int reset);    // float32-filter statistics (HOPE_RS_DEBUG & 0x4000)

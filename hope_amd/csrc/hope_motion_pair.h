@@ -1,6 +1,6 @@
 // hope_motion_pair.h -- the motion launch of the SMALL-TILE class (scenes of <= 32 obstacles) with TWO SCENES PER WAVEFRONT: lanes
 // 0..31 step list entry 2 b, lanes 32..63 entry 2 b + 1.  Same results, bit for bit, as k_env_step<.., PART 1> (hope_step_kernel.h),
-// which stays the large-tile class's motion launch, the reset observation's, and this kernel's reference (stage bit 0x8000 selects it:
+// which stays the large-tile class's motion launch, the reset observation's, and this kernel's reference (stage bit STAGE_ONE_SCENE selects it:
 // tests/test_gpu_parity.py).  Replaces, per scene (reference file:line):
 //   CarParking.step's sub-step loop and retreat   car_parking_base.py:255-277 (the ten poses come from k_kinematics)
 //   _check_arrived / _detect_collision / _check_status   car_parking_base.py:153-184

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) void k_obs_pair(StepParams p) {
     };
     {
         const float PITCH = 6.283185307179586f / NBEAM, MARGIN = 2e-3f;
-        for (int base_i = 0; base_i < nk_max && !(p.stages & 0x1000); base_i += OP_HALF) {   // 0x1000: profiling switch
+        for (int base_i = 0; base_i < nk_max && !(p.stages & STAGE_NO_BEAMS); base_i += OP_HALF) {   // profiling switch
             const int i = base_i + hl;
             const bool in = i < n_kslots;
             const int e = in ? 4 * klist[i >> 2] + (i & 3) : 0;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64) void k_obs_pair(StepParams p) {
                 const unsigned long long rb = __ballot(risky), fb = __ballot(front), bb2 = __ballot(back);
                 const int sh = lane & ~3;
                 const bool ring_ok = ((rb >> sh) & 0xF) == 0 && ((fb >> sh) & 0xF) != 0 && ((bb2 >> sh) & 0xF) != 0;
-                if (ring_ok && back && !(p.stages & 0x4000)) cnt = 0;          // (0x4000: A/B switch, no cull)
+                if (ring_ok && back && !(p.stages & STAGE_NO_CULL)) cnt = 0;   // (A/B switch)
             }
             constexpr int NARROW = HOPE_PAIR_NARROW;          // edges of at most this many beams are appended lane-parallel (A/B: 4 / 8 not faster)
             const int tag = (hw << 14) | (e << 7);
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(64) void k_obs_pair(StepParams p) {
             if (bi < NBEAM) lo_[bi] = (OT)lid[r];
         }
     }
-    if (!p.action_mask || (p.stages & 0x2000)) return;            // 0x2000: internal profiling switch
+    if (!p.action_mask || (p.stages & STAGE_NO_MASK)) return;     // (internal profiling switch)
 
     // ---- action mask (action_mask.py:166-196; the coarse-beam decision of hope_step_kernel.h) ---------------------------------
     ssync();                                                      // every lane has read its best[] words: xs[] takes their place

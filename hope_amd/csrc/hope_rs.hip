@@ -1281,7 +1281,7 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate_f(RsParams p, int obs_f
     const int lane = threadIdx.x;
     // Raised wave priority: this kernel ends the longer launch chain -- the step's critical path -- and shares the CUs with the
     // observation half of k_env_step, which has slack.  Measured at 65 536 scenes: 0.672 -> 0.656 ms per step (priority 1, 2 and
-    // 3 alike); the same on k_rs_words costs 9 %, on k_rs_segs 1 %.  (flag bit 0x10000 = default priority, HOPE_RS_PRIO=0)
+    // 3 alike); the same on k_rs_words costs 9 %, on k_rs_segs 1 %.  (flag bit 0x10000 = default priority: launch_rs_search)
     if (!(obs_f64 & 0x10000)) __builtin_amdgcn_s_setprio(1);
     unsigned long long tsec[16] = {};
     const unsigned long long tstart_ = TIMING ? __builtin_readcyclecounter() : 0;
@@ -1804,49 +1804,44 @@ hipError_t rs_init_tables() {
     return e;
 }
 
-hipError_t launch_rs_search(const RsParams& p, hipStream_t stream, LaunchTimer* timer, hipEvent_t after_segs) {
+// Waves of the large-tile validation launch per CU, enforced through its LDS request.  It shares the GPU with the observation half
+// of k_env_step: measured at 65 536 scenes, steady state, 0.692 ms per step with 4 .. 8 waves per CU, 0.705 with 10, 0.73 with the
+// 13 its 9.5 KB of LDS would allow -- the step kernel's waves are the better use of the wave slots (round 5, with the screen pass:
+// 6 -> 0.4930 ms, 8 -> 0.4958, 12 -> 0.500, unlimited 0.503).  The small-tile launch must not be limited (8 per CU: 0.92 ms).
+constexpr int RS_LARGE_TILE_WPC = 6;
+// Raised wave priority of the validation kernel (k_rs_validate_f) only for the launch of the class with more scenes, i.e. the
+// longer chain (both launches: 0.657 ms / steady 0.688; only the longer chain's: 0.657 / 0.678; only the shorter chain's:
+// 0.672 / 0.696), and only from this many scenes per handle: below, neutral to -1.6 %.
+constexpr int RS_PRIO_MIN_SCENES = 32768;
+
+hipError_t launch_rs_search(const RsParams& p, hipStream_t stream, LaunchTimer* timer) {
     if (p.max_queue <= 0) return hipSuccess;
     // (read per call: the tests switch kernels inside one process)
     static const bool timing = getenv("HOPE_RS_TIMING") != nullptr;      // cycle accounting build (tools/rs_timing.py)
     const bool exact = getenv("HOPE_RS_EXACT") != nullptr;               // the all-float64 validation kernel (the float32 filter's reference)
-    const int occ = getenv("HOPE_RS_OCC") ? atoi(getenv("HOPE_RS_OCC")) : 0;   // exact kernel: 3 (168 VGPRs, default) or 4 (128, spills); filter: 4 (default), 5, 6
     const int dbg = getenv("HOPE_RS_DEBUG") ? (int)strtol(getenv("HOPE_RS_DEBUG"), nullptr, 0) : 0;   // profiling / self-check switches
     const bool stats = (dbg & 0x6000) != 0;                              // float32-filter statistics / self-check build
     size_t lds = exact ? rs_lds_bytes_exact(p.tile_cap) : rs_lds_bytes_filter(p.tile_cap);
-    if (!exact) {
-        // Waves of this kernel per CU, enforced through the LDS request (HOPE_RS_WPC1 / HOPE_RS_WPC0: large- / small-tile launch).
-        // The large-tile launch shares the GPU with the observation half of k_env_step: measured at 65 536 scenes, steady state,
-        // 0.692 ms per step with 4 .. 8 waves per CU, 0.705 with 10, 0.73 with the 13 its 9.5 KB of LDS would allow -- the step
-        // kernel's waves are the better use of the wave slots.  The small-tile launch must not be limited (8 per CU: 0.92 ms).
-        const char* w = getenv(p.tile_cap > 32 ? "HOPE_RS_WPC1" : "HOPE_RS_WPC0");
-        const int wpc = w ? atoi(w) : (p.tile_cap > 32 ? 6 : 0);       // (round 5, with the screen pass: 6 -> 0.4930 ms, 8 -> 0.4958, 12 -> 0.500, unlimited 0.503)
-        if (wpc > 0) lds = std::max(lds, (size_t)((158 * 1024 / wpc) & ~255));
-    }
+    if (!exact && p.tile_cap > 32) lds = std::max(lds, (size_t)((158 * 1024 / RS_LARGE_TILE_WPC) & ~255));
     if (lds > 48 * 1024) {                                  // (the two-kernel form's walk kernel; k_rs_screen stays far below)
         hipError_t e = hipFuncSetAttribute((const void*)k_rs_validate_f<RSF_OCC, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const void* vk = exact ? (timing ? (const void*)k_rs_validate<3, true> : occ != 4 ? (const void*)k_rs_validate<3, false> : (const void*)k_rs_validate<4, false>)
+    const void* vk = exact ? (timing ? (const void*)k_rs_validate<3, true> : (const void*)k_rs_validate<3, false>)
                            : (timing ? (const void*)k_rs_validate_f<RSF_OCC, true, false> : stats ? (const void*)k_rs_validate_f<RSF_OCC, false, true>
-                              : occ == 5 ? (const void*)k_rs_validate_f<5, false, false>
-                              : occ == 3 ? (const void*)k_rs_validate_f<3, false, false> : (const void*)k_rs_validate_f<RSF_OCC, false, false>);
+                              : (const void*)k_rs_validate_f<RSF_OCC, false, false>);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(vk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     if (!exact) { hipError_t e = rs_init_tables(); if (e != hipSuccess) return e; }
     // grid = number of scenes in this tile class (upper bound of the queue length, which lives on the device)
-    const int stop_after = getenv("HOPE_RS_STOP") ? atoi(getenv("HOPE_RS_STOP")) : 0;   // (debugging: 1 = no RS kernel, 2 = words only, 3 = words + segs; results invalid)
-    if (stop_after == 1) return hipSuccess;
     if (timer) timer->begin(HOPE_K_RS_WORDS, stream);
     hipLaunchKernelGGL(k_rs_words, dim3((p.max_queue + RSA_SCENES - 1) / RSA_SCENES, RSA_GROUPS), dim3(WAVE), 0, stream, p);
     if (timer) timer->end(stream);
-    if (stop_after == 2) return hipGetLastError();
     if (timer) timer->begin(HOPE_K_RS_SEGS, stream);
     hipLaunchKernelGGL(k_rs_segs, dim3((p.max_queue + 7) / 8), dim3(WAVE), 0, stream, p);
     if (timer) timer->end(stream);
-    if (after_segs) { hipError_t e = hipEventRecord(after_segs, stream); if (e != hipSuccess) return e; }   // (pipelined steps: the next motion launch waits here)
-    if (stop_after == 3) return hipGetLastError();
     // two-kernel validation (HOPE_RS_SPLIT=1; measured and NOT adopted): k_rs_screen at 8 waves per SIMD, then the walk only for the
     // searches it left a word of.  65 536 scenes, steady state, same box: 0.531 ms per step against 0.514 for the one-kernel form
     // (profiles/r05_ab_two_kernel_validation.txt) -- the second launch over the whole queue, the survivors' second prologue and the
@@ -1855,27 +1850,18 @@ hipError_t launch_rs_search(const RsParams& p, hipStream_t stream, LaunchTimer* 
                        getenv("HOPE_RS_SPLIT") && atoi(getenv("HOPE_RS_SPLIT")) == 1;
     if (split) {
         if (timer) timer->begin(HOPE_K_RS_SCREEN, stream);
-        static const int socc = getenv("HOPE_RS_SCREEN_OCC") ? atoi(getenv("HOPE_RS_SCREEN_OCC")) : 8;      // (A/B: 7 = 72 registers, no spills)
-        if (socc == 7) hipLaunchKernelGGL((k_rs_screen<false, 7>), dim3(p.max_queue), dim3(WAVE), rs_screen_lds_bytes(p.tile_cap), stream, p);
-        else if (socc == 6) hipLaunchKernelGGL((k_rs_screen<false, 6>), dim3(p.max_queue), dim3(WAVE), rs_screen_lds_bytes(p.tile_cap), stream, p);
-        else hipLaunchKernelGGL((k_rs_screen<false, 8>), dim3(p.max_queue), dim3(WAVE), rs_screen_lds_bytes(p.tile_cap), stream, p);
+        hipLaunchKernelGGL((k_rs_screen<false, 8>), dim3(p.max_queue), dim3(WAVE), rs_screen_lds_bytes(p.tile_cap), stream, p);
         if (timer) timer->end(stream);
     }
     if (timer) timer->begin(HOPE_K_RS_VALIDATE, stream);
-    static const bool no_prio = getenv("HOPE_RS_PRIO") && atoi(getenv("HOPE_RS_PRIO")) == 0;
-    // only for the launch of the class with more scenes, i.e. the longer chain (both launches: 0.657 ms / steady 0.688; only the
-    // longer chain's: 0.657 / 0.678; only the shorter chain's: 0.672 / 0.696); below 32 768 scenes neutral to -1.6 %: off
     const bool longer_chain = 2 * (long long)p.max_queue >= p.n;
-    const int flags = (p.obs_f64 ? 1 : 0) | dbg | ((no_prio || p.n < 32768 || !longer_chain) ? 0x10000 : 0);
+    const int flags = (p.obs_f64 ? 1 : 0) | dbg | ((p.n < RS_PRIO_MIN_SCENES || !longer_chain) ? 0x10000 : 0);
     if (exact) {
         if (timing) hipLaunchKernelGGL((k_rs_validate<3, true>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
-        else if (occ != 4) hipLaunchKernelGGL((k_rs_validate<3, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
-        else hipLaunchKernelGGL((k_rs_validate<4, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
+        else hipLaunchKernelGGL((k_rs_validate<3, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
     } else if (split) hipLaunchKernelGGL((k_rs_validate_f<RSF_OCC, false, false, true>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
     else if (timing) hipLaunchKernelGGL((k_rs_validate_f<RSF_OCC, true, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
     else if (stats) hipLaunchKernelGGL((k_rs_validate_f<RSF_OCC, false, true>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
-    else if (occ == 5) hipLaunchKernelGGL((k_rs_validate_f<5, false, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
-    else if (occ == 3) hipLaunchKernelGGL((k_rs_validate_f<3, false, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
     else hipLaunchKernelGGL((k_rs_validate_f<RSF_OCC, false, false>), dim3(p.max_queue), dim3(WAVE), lds, stream, p, flags);
     if (timer) timer->end(stream);
     return hipGetLastError();

@@ -28,6 +28,7 @@
 #define HOPE_MASK_MG 4      // action-mask rows probed together (A/B builds: -DHOPE_MASK_MG=8 measured 1.3 % slower)
 #endif
 #include "hope_env.h"
+#include "hope_internal.h"
 #ifndef HOPE_STEP_SYNC_FULL
 #define HOPE_STEP_SYNC_FULL 0   // 1: every LDS synchronisation point of the step kernel is a __syncthreads() (rounds 1-5)
 #endif
@@ -1353,7 +1354,7 @@ __global__ __launch_bounds__(64, (PART == 0 && !TIMING) ? HOPE_PART0_OCC : 4) vo
     // direction flip) is paired with all 120 beams.
     {
         const float PITCH = 6.283185307179586f / NBEAM, MARGIN = 2e-3f;
-        for (int base = 0; base < n_kslots && !(p.stages & 0x1000); base += WAVE) {   // 0x1000: profiling switch
+        for (int base = 0; base < n_kslots && !(p.stages & STAGE_NO_BEAMS); base += WAVE) {   // profiling switch
             const int i = base + lane;
             const int e = i < n_kslots ? 4 * llist[i >> 2] + (i & 3) : 0;
             int lo = 0, cnt = 0;
@@ -1414,7 +1415,7 @@ __global__ __launch_bounds__(64, (PART == 0 && !TIMING) ? HOPE_PART0_OCC : 4) vo
                 const unsigned long long rb = __ballot(risky), fb = __ballot(front), bb = __ballot(back);
                 const int sh = lane & ~3;
                 const bool ring_ok = ((rb >> sh) & 0xF) == 0 && ((fb >> sh) & 0xF) != 0 && ((bb >> sh) & 0xF) != 0;
-                if (ring_ok && back && !(p.stages & 0x4000)) cnt = 0;          // (0x4000: profiling / A-B switch, no cull)
+                if (ring_ok && back && !(p.stages & STAGE_NO_CULL)) cnt = 0;   // (profiling / A-B switch)
             }
             // Append the pairs to the queue EDGE BY EDGE: for every edge with beams (a scalar walk over the ballot) its range
             // [lo, lo + cnt) is written by the lanes 0 .. cnt-1 in one store -- no per-beam ballots / prefix counts at all
@@ -1477,7 +1478,7 @@ __global__ __launch_bounds__(64, (PART == 0 && !TIMING) ? HOPE_PART0_OCC : 4) vo
         if (has1) lo[i1] = (OT)lid1;
     }
     ST_T(5);
-    if (!p.action_mask || (p.stages & 0x2000)) { ST_FLUSH(); return; }    // 0x2000: internal profiling switch
+    if (!p.action_mask || (p.stages & STAGE_NO_MASK)) { ST_FLUSH(); return; }    // (internal profiling switch)
 
     // ---- action mask (action_mask.py:166-196) ----------------------------------------------------------
     ssync();                                                      // region A: best[]/queue[] are dead from here

@@ -79,17 +79,18 @@ extern "C" {
  * queues than the streams it was captured from.  hope_env_create rejects the bit. */
 
 /* Environment variables read by the library (tuning / diagnostics only; results never depend on them):
- *   HOPE_SPLIT_MIN   scenes per handle from which HOPE_F_OVERLAP launches k_env_step as a motion and an observation
- *                    launch (default 16384); HOPE_NO_SPLIT: never
- *   HOPE_CLS1_FRAC   share of the scenes the large-tile launch chain should hold after the small-tile class has handed
- *                    scenes over (default 0.42 below 32768 scenes, else 0 = no hand-over); read by hope_env_set_scenes
+ *   HOPE_SPLIT_MIN   scenes per handle from which HOPE_F_OVERLAP launches k_env_step as a motion and an observation launch
+ *   HOPE_AUTO_CHAINS lo0:hi0:lo1:hi1 -- scene-count ranges in which a one-class batch is stepped as two sub-chains of that class
  *   HOPE_RS_EXACT    validate Reeds-Shepp words with the all-float64 kernel (the reference of the default kernel's float32 filter)
- *   HOPE_AUTO_CHAINS lo0:hi0:lo1:hi1 -- scene-count ranges in which a batch whose scenes all sit in ONE tile class (0: <= 32 obstacles,
- *                    1: larger) is stepped as two sub-chains of that class, so that the two-stream pipelined form of deferred steps
- *                    applies (default 32768:2^30:4096:32768, measured: profiles/r04_single_class_chains.txt); HOPE_CHAINS=n fixes
- *                    the number of sub-chains per class instead (1 = never)
- *   HOPE_BALANCE, HOPE_PRIO, HOPE_RS_OCC   rejected launch / build variants kept for experiments
- *   HOPE_STEP_TIMING, HOPE_RS_TIMING, HOPE_RS_DEBUG      instrumented kernel builds and profiling switches (tools/) */
+ *   HOPE_RS_SPLIT    1: the two-kernel Reeds-Shepp validation (k_rs_screen, then the walk; measured and not adopted)
+ *   HOPE_RS_DEBUG    Reeds-Shepp profiling and self-check switches (hope_rs.hip)
+ *   HOPE_STEP_TIMING cycle-accounting build of the step kernel (tools/step_timing.py)
+ *   HOPE_RS_TIMING   cycle-accounting build of the validation kernel (tools/rs_timing.py)
+ *   HOPE_BEV_LEGACY  image: the per-tile raster of the moving boxes instead of the trajectory layer
+ *   HOPE_BEV_DEBUG   image: profiling switches of the image kernels (hope_bev.hip)
+ *   HOPE_CLS1_FRAC   share of the scenes the large-tile launch chain holds after the small-tile class hands scenes over
+ *   HOPE_HOST_THREADS  CPU threads of the scene generator (hope_scenegen_generate)
+ * Defaults and the measurements behind them: hope_amd/csrc/hope_env.hip (plan_step). */
 
 /* hope_env_step stage mask */
 #define HOPE_STAGE_MOTION 0x1   /* kinematics + arrival + collision sub-step loop (CarParking.step :255-277) */
@@ -97,6 +98,7 @@ extern "C" {
 #define HOPE_STAGE_REWARD 0x4   /* status + reward (:279-289) + wrapper reward_shaping                     */
 #define HOPE_STAGE_RS 0x8       /* Reeds-Shepp feasibility search (:293-297, find_rs_path :413)           */
 #define HOPE_STAGE_ALL 0xF
+/* Bits 0x1000, 0x2000, 0x4000 and 0x8000 are reserved for the library's internal test and profiling switches. */
 /* bird's-eye image observation obs['img'] (_render :301-320, _get_img_observation :322-350, Obs_Processor
  * observation_processor.py:11-23, transpose env_wrapper.py:53-54).  Not part of HOPE_STAGE_ALL (the reference's
  * USE_IMG switch, configs.py:100); needs a handle created with HOPE_F_IMAGE and out->img. */
@@ -297,12 +299,18 @@ int hope_env_restore_maps(hope_env_t *h, const uint8_t *drawn /*[N]*/, const uin
  * default) in creation order, and launches of streams that share one serialise: which library stream plays which role of the step's
  * launch structure decides 0.52 vs 0.6+ ms per 65 536-scene step.  Up to round 4 the assignment was a table found by search on one
  * box; since round 5 hope_env_create MEASURES it (pairs of ~100 us spin kernels: two streams on one queue take twice as long; < 5 ms
- * once, HOPE_QUEUE_CHECK=0 skips it) and assigns the roles so that the streams a deferred / joined / sub-chain step keeps busy at
- * the same time sit on different queues, whatever other streams the process created first.  queue_of_role[r]: hardware-queue class
- * (0, 1, ...) of role r's stream, r = 1 .. 7 ([0]: the NULL stream, the usual caller's stream); -1 = not measured.
- * Roles: 1 search chain of the small-tile class, 2 image side, 3 / 4 observation half of the large- / small-tile class, 5 chain of
- * the large-tile class (deferred), 6 spare, 7 second sub-chain's observation.  *n_queues = distinct classes seen; *ms = what the
- * measurement took.  Any pointer may be NULL. */
+ * once) and assigns the roles so that the streams a deferred / joined / sub-chain step keeps busy at the same time sit on different
+ * queues, whatever other streams the process created first.  queue_of_role[r]: hardware-queue class (0, 1, ...) of role r's stream,
+ * -1 = not measured.  Roles (enum Role in hope_amd/csrc/hope_env.hip):
+ *   0 caller      the caller's stream (the NULL stream for the usual caller)
+ *   1 chain       the second chain (small-tile class): all of it, or its search launches in a pipelined (deferred) step
+ *   2 image       the image beside the chains (joined steps) / the static-layer rebuild beside it (pipelined steps)
+ *   3 obs large   observation half of the first chain (large-tile class)
+ *   4 obs small   observation half of the second chain (small-tile class)
+ *   5 search 0    search launches of the first chain in a pipelined step
+ *   6 spare       created, not used
+ *   7 obs sub     observation half of the second sub-chain of a one-class batch
+ * *n_queues = distinct classes seen; *ms = what the measurement took.  Any pointer may be NULL. */
 int hope_env_queue_check(hope_env_t *h, int32_t *queue_of_role /*[8]*/, int32_t *n_queues, double *ms);
 
 /* With HOPE_F_PROFILE every kernel launch is bracketed by its own HIP event pair on the launch stream.

@@ -1274,7 +1274,7 @@ def test_tie_census_no_decision_of_the_geos_slice_comes_near_a_tie():
 def test_lidar_back_face_cull_changes_no_bit():
     """Round 4: the lidar drops the (beam, edge) pairs of the BACK edges of convex obstacles seen from outside (hope_step_kernel.h:
     the nearer front-edge hit is certain to pass the reference's tests, so the back edge can never be the beam's minimum,
-    lidar_simulator.py:116-131).  With the cull switched off (stage bit 0x4000) every lidar value and every mask entry must be the
+    lidar_simulator.py:116-131).  With the cull switched off (stage bit 0x4000, STAGE_NO_CULL) every lidar value and every mask entry must be the
     same bit, in both launch forms, over mixed and Dragon-Lake scenes with turnover (besides the oracle comparisons of this file,
     which all run with the cull on)."""
     import os
@@ -1294,7 +1294,7 @@ def test_lidar_back_face_cull_changes_no_bit():
             for it in range(40):
                 a = torch.rand((n, 2), device='cuda', generator=g) * 2 - 1
                 envs[0].step(a, auto_reset=True)
-                envs[1].step(a, stages=L.STAGE_ALL | 0x4000, auto_reset=True)
+                envs[1].step(a, stages=L.STAGE_ALL | L.STAGE_NO_CULL, auto_reset=True)
                 torch.cuda.synchronize()
                 for k in ('lidar', 'action_mask', 'status', 'pose', 'reward', 'rs_word'):
                     assert torch.equal(getattr(envs[0], k), getattr(envs[1], k)), (split, it, k)
@@ -1307,7 +1307,7 @@ def test_lidar_back_face_cull_changes_no_bit():
 @pytest.mark.parametrize('f64', [True, False])
 def test_two_scenes_per_wave_observation_equals_the_one_scene_kernel(f64):
     """Round 6: the motion and the observation launch of the small-tile class run TWO scenes per wavefront (k_motion_pair,
-    hope_motion_pair.h; k_obs_pair, hope_obs_pair.h).  Against the one-scene kernels (stage bit 0x8000 selects them) every output
+    hope_motion_pair.h; k_obs_pair, hope_obs_pair.h).  Against the one-scene kernels (stage bit 0x8000, STAGE_ONE_SCENE, selects them) every output
     and the episode state must be the same bit: an odd number
     of small-tile scenes (the last wave's second half is empty), lots of every level incl. Dragon-Lake lots that fit the small
     tile, episode turnover on new maps, a caller's `active` mask that silences one scene of many pairs, float64 and float32
@@ -1342,7 +1342,7 @@ def test_two_scenes_per_wave_observation_equals_the_one_scene_kernel(f64):
                 act = torch.from_numpy(m.astype(np.uint8)).cuda()
                 masked += int((~m).sum())
             envs[0].step(a, active=act, auto_reset=True, fresh=True, defer_rs=bool(it % 2))
-            envs[1].step(a, active=act, stages=L.STAGE_ALL | 0x8000, auto_reset=True, fresh=True, defer_rs=bool(it % 2))
+            envs[1].step(a, active=act, stages=L.STAGE_ALL | L.STAGE_ONE_SCENE, auto_reset=True, fresh=True, defer_rs=bool(it % 2))
             for e in envs:
                 e.wait_rs()
             torch.cuda.synchronize()

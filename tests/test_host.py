@@ -55,6 +55,22 @@ def test_library_exports_every_declared_symbol():
     assert L.hope_abi_version() == _lib.ABI_VERSION == 8
 
 
+def test_environment_variables_are_the_documented_ones():
+    """the library reads exactly the environment variables that include/hope_env.h documents, each by a literal name."""
+    csrc = os.path.join(ROOT, 'hope_amd', 'csrc')
+    src = ''.join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)))
+    calls = re.findall(r'\bgetenv\s*\(([^)]*)\)', src)
+    assert calls
+    bad = [c for c in calls if not re.fullmatch(r'"HOPE_[A-Z0-9_]+"', c.strip())]
+    assert not bad, bad                        # a name built at run time escapes this test
+    read = {c.strip().strip('"') for c in calls}
+    hdr = open(os.path.join(ROOT, 'include', 'hope_env.h')).read()
+    block = re.search(r'/\* Environment variables read by the library.*?\*/', hdr, flags=re.S).group(0)
+    documented = re.findall(r'^ \*   (HOPE_[A-Z0-9_]+)\s', block, flags=re.M)
+    assert len(documented) == len(set(documented)), documented
+    assert read == set(documented), read ^ set(documented)
+
+
 def test_no_cpu_fallback():
     """without a HIP device the product path must fail loudly (never route through the oracle)."""
     import torch

@@ -20,9 +20,11 @@ for mix in (('dlp',), ('Normal', 'Complex', 'Extrem')):
     torch.cuda.synchronize()
     for name, dbg in (('full', 0), ('no raster', 1), ('no obstacles', 2), ('no boxes', 4), ('no gather', 8), ('setup only', 9)):
         env.kernel_ms(reset=True)
+        os.environ['HOPE_BEV_DEBUG'] = str(dbg)          # (read per call)
         for i in range(3):
-            env.reset_obs(stages=L.STAGE_IMG | (dbg << 12))
+            env.reset_obs(stages=L.STAGE_IMG)
         torch.cuda.synchronize()
         ms, cnt = env.kernel_ms(reset=True)['k_bev_image']
         print(f'{"/".join(mix):22s} {name:14s} {ms / cnt * 1e3:8.1f} us per {N} scenes', flush=True)
+    os.environ.pop('HOPE_BEV_DEBUG', None)
     env.close()

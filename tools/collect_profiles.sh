@@ -49,10 +49,8 @@ py $R/tools/bev_probe.py > $O/${TAG}_image_stage_times.txt
   echo "== --same-map"; py $R/bench.py --full --same-map --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 0 | tail -1
   echo "== --refresh-every 0 (static pool)"; py $R/bench.py --full --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
   echo "== HOPE_RS_DEBUG=0x20000 (no screen pass: round 4's validation kernel)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --full --refresh-every 0 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
-  echo "== HOPE_PIPE=0 (steps not pipelined: the round-3 launch structure with this round's kernels)"; HOPE_PIPE=0 $T python $R/bench.py --full --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
   for NS in 4096 8192 16384; do echo "== --scenes $NS HOPE_RS_DEBUG=0x20000 (no screen pass)"; HOPE_RS_DEBUG=0x20000 $T python $R/bench.py --full --scenes $NS --no-cpu-baseline --witness 0 --repeat-passes 2 --steps 40 --warmup 10 2>/dev/null | tail -1; done
   echo "== --action-bank 16 (rounds 1-5: each scene repeats a 16-step action pattern)"; py $R/bench.py --full --action-bank 16 --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 | tail -1
-  echo "== HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 (one scene per wave in both launches of the small-tile class)"; HOPE_MOTION_PAIR=0 HOPE_OBS_PAIR=0 $T python $R/bench.py --full --no-cpu-baseline --steps 40 --warmup 10 --repeat-passes 2 --witness 0 2>/dev/null | tail -1
   echo "== the driver's exact form: --steps 20 --warmup 5"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1
   echo "== the driver's exact form, second run"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1
   echo "== the driver's exact form, third run"; py $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel times of the step with SEQUENTIAL launches (no stream overlap) on the bench workload: a stable number per kernel for
-A/B experiments on one kernel (environment variables select variants, e.g. HOPE_RS_EXACT=1, HOPE_RS_OCC=5, HOPE_RS_DEBUG=0x8000).
+A/B experiments on one kernel (environment variables select variants, e.g. HOPE_RS_EXACT=1, HOPE_RS_SPLIT=1, HOPE_RS_DEBUG=0x8000).
 Usage (GPU box):  python tools/rs_bench.py [--scenes 65536] [--steps 30]"""
 import argparse
 import os
