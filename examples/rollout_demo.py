@@ -22,6 +22,9 @@ def main():
     ap.add_argument('--scenes', type=int, default=16384)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--unique', type=int, default=1024)
+    ap.add_argument('--device-pool', type=int, default=0, metavar='LOTS',
+                    help='also run a short PPO loop whose finished episodes draw new maps from a pool of LOTS generated lots that is '
+                         'refilled ON THE DEVICE after every update (scene_gen.DevicePoolRefresher: no host generator thread, no upload)')
     args = ap.parse_args()
     rank, world, local = D.init_from_env()
     dev = f'cuda:{local}'
@@ -42,6 +45,22 @@ def main():
     if rank == 0:
         print(f'{world} rank(s) x {args.scenes} scenes: {args.scenes * world * args.steps / dt / 1e6:.2f} M env+agent steps/s, '
               f'{s["episodes"]} episodes on rank 0, success rate {s["success_rate"]:.3f}, RS replay active {s["executing_rs"]:.3f}')
+    if args.device_pool > 0:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        from hope_amd.scene_gen import DevicePoolRefresher
+        levels = ('Normal', 'Complex', 'Extrem')
+        env.generate_pool(args.device_pool, levels, seed=7 + rank)            # the first pool, drawn by the HIP generator as well
+        ref = DevicePoolRefresher(env, args.device_pool, levels, seed=7 + rank, relaxed=True)
+        ref.batch = 1
+        tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
+                        seed=rank, fresh_scenes=True, pool_refresher=ref)
+        for _ in range(16):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f'  device pool: {tr.updates} PPO updates, {ref.commits} refills of {args.device_pool} lots generated on the device, '
+                  f'pool generation {env.pool_generation():#x}')
     # evaluation as eval_utils.py does it (one episode per slot, per-level table), records gathered over the ranks
     from hope_amd import agents as A
     from hope_amd import evaluate as E

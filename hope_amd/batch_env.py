@@ -149,6 +149,18 @@ class ParkingBatch:
         self.pool_size = int(n_pool)
         return self
 
+    def generate_pool(self, n_pool, levels=('Normal', 'Complex', 'Extrem'), seed=0, batch=0, relaxed=False):
+        """refill the pool on the device (hope_env_generate_pool): n_pool lots of the listed levels (split as PoolRefresher splits
+        them), drawn by the HIP generator into the pool set the kernels are not reading and swapped in as commit_pool(relaxed=)
+        does.  Lot k of a level is lot batch * n_pool + k of scene_gen.generate_arrays_det(level, seed=seed * 1000003 + level id).
+        No host thread, staging or upload; asynchronous."""
+        from .scene_gen import pool_level_counts
+        counts = (C.c_int32 * 3)(*pool_level_counts(n_pool, levels))
+        L.check(self.lib.hope_env_generate_pool(self.h, int(n_pool), counts, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                C.c_int64(int(batch) * int(n_pool)), 1 if relaxed else 0), 'hope_env_generate_pool')
+        self.pool_size = int(n_pool)
+        return self
+
     def set_dlp_cases(self, pool=None):
         """make the Dragon-Lake-Parking cases (a `DlpScenePool`, default data/dlp_scenes.npz) drawable on the device: at episode
         turnover a large-tile scene then gets a case with a freshly drawn start candidate, jitter, flips and obstacle cull

@@ -17,6 +17,7 @@
 #include "hope_step_kernel.h"
 #include "hope_obs_pair.h"
 #include "hope_motion_pair.h"
+#include "hope_scenegen_kernel.h"
 
 using namespace hope;
 
@@ -125,15 +126,23 @@ struct hope_env {
     PoolSet pset[2];
     int pactive = -1;
     struct PoolStage { double* start = nullptr; double* dest = nullptr; double* bbox = nullptr; double* verts = nullptr; int32_t* nobst = nullptr;
-                       int32_t* list = nullptr; int cap = 0; bool busy = false; };
+                       int32_t* list = nullptr; int cap = 0; bool busy = false;
+                       bool staged = false; };   // staged: handed out by hope_env_pool_staging, not committed yet
     PoolStage pstage;                            // pinned host memory
     double* pstage_dev = nullptr;                // device staging of start | dest | bbox
+    // hope_env_generate_pool: n_obst of a generated set travels back through the set's own pinned array, asynchronously on pool_stream;
+    // pool_nobst_host takes it over lazily, when somebody needs it (settle_gen_nobst: refresh_pool_lists_sync), so that no call
+    // waits for the generator.  gen_host_set: the ACTIVE set if its host copy is still outstanding, else -1.
+    int32_t* gen_nobst[2] = {nullptr, nullptr};
+    int gen_nobst_cap[2] = {0, 0}, gen_nobst_n[2] = {0, 0};
+    hipEvent_t ev_gen_copied[2] = {nullptr, nullptr};
+    int gen_host_set = -1;
     int pstage_dev_cap = 0;
     hipStream_t pool_stream = nullptr;
     hipEvent_t ev_pool_ready = nullptr, ev_pool_copied = nullptr, ev_last_step = nullptr;
     bool pool_wait_pending = false;
     // hope_env_commit_pool_relaxed: the uploaded set takes over once ev_pool_ready has passed (apply_pending_pool)
-    struct PendingPool { bool on = false; int set = 0, n_pool = 0, cls_n[2] = {0, 0}; uint64_t content = 0; std::vector<int32_t> nobst_host; } pend;
+    struct PendingPool { bool on = false, generated = false; int set = 0, n_pool = 0, cls_n[2] = {0, 0}; uint64_t content = 0; std::vector<int32_t> nobst_host; } pend;
     int32_t* pool_cls[2] = {nullptr, nullptr};   // pool entries of each tile class
     int pool_cls_n[2] = {0, 0};
     std::vector<int32_t> pool_nobst_host;        // n_obst of the pool's complete scenes (class lists are rebuilt from it)
@@ -806,6 +815,7 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     if (h->cold_host) hipHostFree(h->cold_host);
     for (hipEvent_t e : {h->ev_pool_ready, h->ev_pool_copied, h->ev_last_step}) if (e) hipEventDestroy(e);
     for (void* q : {(void*)h->pstage.start, (void*)h->pstage.dest, (void*)h->pstage.bbox, (void*)h->pstage.verts, (void*)h->pstage.nobst, (void*)h->pstage.list}) if (q) hipHostFree(q);
+    for (int i = 0; i < 2; i++) { if (h->gen_nobst[i]) hipHostFree(h->gen_nobst[i]); if (h->ev_gen_copied[i]) hipEventDestroy(h->ev_gen_copied[i]); }
     for (hipEvent_t e : h->free_events) hipEventDestroy(e);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
@@ -1518,6 +1528,7 @@ int hope_env_pool_staging(hope_env_t* h, int n_pool, double** start, double** de
         if (e_ != hipSuccess) return fail(HOPE_ENOMEM, std::string("hipHostMalloc pool staging: ") + hipGetErrorString(e_));
         h->pstage.cap = n_pool;
     }
+    h->pstage.staged = true;
     *start = h->pstage.start; *dest = h->pstage.dest; *bbox = h->pstage.bbox; *verts = h->pstage.verts; *n_obst = h->pstage.nobst;
     return HOPE_OK;
 }
@@ -1540,6 +1551,16 @@ int hope_env_pool_generation(hope_env_t* h, uint64_t* generation) {
     return HOPE_OK;
 }
 
+// the host copy of a generated pool's obstacle counts (hope_env_generate_pool), once its kernel and copy have finished
+static int settle_gen_nobst(hope_env_t* h) {
+    const int g = h->gen_host_set;
+    if (g < 0) return HOPE_OK;
+    HIPCHK(hipEventSynchronize(h->ev_gen_copied[g]));
+    h->pool_nobst_host.assign(h->gen_nobst[g], h->gen_nobst[g] + h->gen_nobst_n[g]);
+    h->gen_host_set = -1;
+    return HOPE_OK;
+}
+
 // the swap of hope_env_commit_pool_relaxed, once its upload is complete (wait: block until it is)
 static int apply_pending_pool(hope_env_t* h, bool wait) {
     if (!h->pend.on) return HOPE_OK;
@@ -1558,6 +1579,7 @@ static int apply_pending_pool(hope_env_t* h, bool wait) {
     h->pactive = h->pend.set;
     h->pend.on = false;
     bump_pool_generation(h, h->pend.content);
+    h->gen_host_set = h->pend.generated ? h->pend.set : -1; // (a generated pool: its counts are fetched when somebody asks)
     return HOPE_OK;
 }
 
@@ -1619,6 +1641,7 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
     if (!l1.empty()) HIPCHK(hipMemcpyAsync(ps.list[1], h->pstage.list + l0.size(), l1.size() * sizeof(int32_t), hipMemcpyHostToDevice, us));
     HIPCHK(hipEventRecord(h->ev_pool_copied, us));          // the pinned staging may be refilled once this has passed
     h->pstage.busy = true;
+    h->pstage.staged = false;
     hipLaunchKernelGGL(k_set_scene_consts, dim3((n_pool + 127) / 128), dim3(128), 0, us, n_pool, (const int32_t*)nullptr,
                        (const double*)dv, (const double*)(dv + P * 24), (const double*)(dv + P * 48), (const int32_t*)nullptr, ps.c,
                        (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
@@ -1646,6 +1669,7 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
         h->pend.on = true; h->pend.set = t; h->pend.n_pool = n_pool;
         h->pend.cls_n[0] = (int)l0.size(); h->pend.cls_n[1] = (int)l1.size(); h->pend.content = content;
         h->pend.nobst_host.assign(h->pstage.nobst, h->pstage.nobst + n_pool);
+        h->pend.generated = false;
         return HOPE_OK;
     }
     // swap: every launch enqueued from now on reads the new set, after waiting (on its own stream) for the upload
@@ -1654,6 +1678,7 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
     h->pool_cls_n[0] = (int)l0.size(); h->pool_cls_n[1] = (int)l1.size();
     h->pool_n = n_pool;
     h->pool_nobst_host.assign(h->pstage.nobst, h->pstage.nobst + n_pool);
+    h->gen_host_set = -1;
     h->pactive = t;
     h->pool_wait_pending = true;
     bump_pool_generation(h, content);
@@ -1680,11 +1705,108 @@ int hope_env_set_pool(hope_env_t* h, int n_pool, const double* start, const doub
     return HOPE_OK;
 }
 
+// ---- lots generated on the device (k_scenegen, hope_scenegen_kernel.h) ---------------------------------------------------------
+int hope_scenegen_generate_device(int device_id, int level, int bay_mode, int n, uint64_t seed, int64_t first_index, int max_obstacles,
+                                  double* start, double* dest, double* bbox, double* verts, int32_t* n_obst, int32_t* case_id, void* stream) {
+    if (level < 0 || level > 2 || n < 0) return fail(HOPE_EINVAL, "hope_scenegen_generate_device: bad argument");
+    if (max_obstacles < SG_MAX_RINGS + 1) return fail(HOPE_EINVAL, "hope_scenegen_generate_device: max_obstacles < 18 (a generated lot holds up to 17 obstacles)");
+    if (n == 0) return HOPE_OK;
+    if (!start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_scenegen_generate_device: null output buffer");
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(HOPE_ENODEV, "hope_scenegen_generate_device: hipSetDevice failed");
+    SgJob job{};
+    for (int l = 0; l < 4; l++) job.off[l] = l > level ? n : 0;
+    for (int l = 0; l < 3; l++) job.seed[l] = seed;
+    job.first_index = first_index; job.bay_mode = bay_mode;
+    hipLaunchKernelGGL(k_scenegen, dim3((n + SG_BLOCK - 1) / SG_BLOCK), dim3(SG_BLOCK), 0, (hipStream_t)stream, job, max_obstacles, start, dest,
+                       bbox, verts, n_obst, case_id, (double*)nullptr);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_generate_pool(hope_env_t* h, int n_pool, const int32_t* n_per_level, uint64_t seed, int64_t first_index, int relaxed) {
+    if (!h || n_pool <= 0 || !n_per_level) return fail(HOPE_EINVAL, "hope_env_generate_pool: bad argument");
+    {
+        int64_t sum = 0;
+        for (int l = 0; l < 3; l++) {
+            if (n_per_level[l] < 0) return fail(HOPE_EINVAL, "hope_env_generate_pool: negative lot count");
+            sum += n_per_level[l];
+        }
+        if (sum != n_pool) return fail(HOPE_EINVAL, "hope_env_generate_pool: n_per_level does not sum to n_pool");
+    }
+    if (h->max_obst < SG_MAX_RINGS + 1) return fail(HOPE_EINVAL, "hope_env_generate_pool: max_obstacles < 18 (a generated lot holds up to 17 obstacles)");
+    if (h->pstage.staged) return fail(HOPE_ESTATE, "hope_env_generate_pool: a hope_env_pool_staging fill has not been committed (hope_env_commit_pool first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    int rc = pool_init_streams(h);
+    if (rc != HOPE_OK) return rc;
+    { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }     // (a relaxed swap still in flight: it comes first)
+    const bool two = h->max_obst > SMALL_TILE;
+    const int n_cases = h->dlp.n_cases;
+    const int n_l0 = two ? n_pool : n_pool + n_cases, n_l1 = two ? n_cases : 0;
+    const int t = h->pactive < 0 ? 0 : 1 - h->pactive;
+    hope_env::PoolSet& ps = h->pset[t];
+    rc = pool_set_reserve(h, ps, n_pool, std::max(n_l0, n_l1) + 1);
+    if (rc != HOPE_OK) return rc;
+    // (set t is not the active one, so nobody is waiting for gen_nobst[t]; an earlier copy into it is ordered before this one on us)
+    if (!h->ev_gen_copied[t]) HIPCHK(hipEventCreateWithFlags(&h->ev_gen_copied[t], hipEventDisableTiming));
+    if (n_pool > h->gen_nobst_cap[t]) {
+        if (h->gen_nobst[t]) { HIPCHK(hipEventSynchronize(h->ev_gen_copied[t])); hipHostFree(h->gen_nobst[t]); }   // (a larger pool than before: rare)
+        h->gen_nobst[t] = nullptr; h->gen_nobst_cap[t] = 0;
+        hipError_t e_ = hipHostMalloc((void**)&h->gen_nobst[t], (size_t)n_pool * sizeof(int32_t));
+        if (e_ != hipSuccess) return fail(HOPE_ENOMEM, std::string("hipHostMalloc generated n_obst: ") + hipGetErrorString(e_));
+        h->gen_nobst_cap[t] = n_pool;
+    }
+    hipStream_t us = h->pool_stream;
+    // the target set was the active one until the previous swap: steps enqueued before that swap may still be reading it
+    if (h->pactive >= 0) {
+        HIPCHK(hipStreamWaitEvent(us, h->ev_last_step, 0));
+        if (h->last_via_steps) for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(us, h->ev_step[i], 0));   // (the motion launches of the last step)
+    }
+    SgJob job{};
+    job.off[0] = 0;
+    for (int l = 0; l < 3; l++) {
+        job.off[l + 1] = job.off[l] + n_per_level[l];
+        job.seed[l] = seed * 1000003ull + (uint64_t)l;          // PoolRefresher._fill's convention: level l draws from seed * 1000003 + l
+    }
+    job.first_index = first_index; job.bay_mode = -1;
+    hipLaunchKernelGGL(k_scenegen, dim3((n_pool + SG_BLOCK - 1) / SG_BLOCK), dim3(SG_BLOCK), 0, us, job, h->max_obst, (double*)nullptr, (double*)nullptr,
+                       (double*)nullptr, ps.verts, ps.nobst, (int32_t*)nullptr, ps.c);
+    hipLaunchKernelGGL(k_pool_lists_generated, dim3((n_pool + n_cases + 255) / 256), dim3(256), 0, us, n_pool, n_cases, two ? 1 : 0, ps.list[0], ps.list[1]);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->gen_nobst[t], ps.nobst, (size_t)n_pool * sizeof(int32_t), hipMemcpyDeviceToHost, us));
+    HIPCHK(hipEventRecord(h->ev_gen_copied[t], us));
+    HIPCHK(hipEventRecord(h->ev_pool_ready, us));
+    h->gen_nobst_n[t] = n_pool;
+    // identity of the new pool: a pure function of the arguments (the lots are a pure function of them)
+    uint64_t content = 0x67656e706f6f6cull;
+    content = fold64(content, (uint64_t)(uint32_t)n_pool);
+    for (int l = 0; l < 3; l++) content = fold64(content, (uint64_t)(uint32_t)n_per_level[l]);
+    content = fold64(content, seed);
+    content = fold64(content, (uint64_t)first_index);
+    if (relaxed && h->pactive >= 0) {
+        h->pend.on = true; h->pend.set = t; h->pend.n_pool = n_pool;
+        h->pend.cls_n[0] = n_l0; h->pend.cls_n[1] = n_l1; h->pend.content = content;
+        h->pend.nobst_host.clear(); h->pend.generated = true;  // (pool_nobst_host: settle_gen_nobst, after the swap has been applied)
+        return HOPE_OK;
+    }
+    h->pool_verts = ps.verts; h->pool_c = ps.c; h->pool_nobst = ps.nobst;
+    h->pool_cls[0] = ps.list[0]; h->pool_cls[1] = ps.list[1];
+    h->pool_cls_n[0] = n_l0; h->pool_cls_n[1] = n_l1;
+    h->pool_n = n_pool;
+    h->pactive = t;
+    h->gen_host_set = t;
+    h->pool_wait_pending = true;
+    bump_pool_generation(h, content);
+    return HOPE_OK;
+}
+
 // the class lists of the ACTIVE set after the Dragon-Lake cases changed (rare; host-synchronous)
 static int refresh_pool_lists_sync(hope_env_t* h) {
     int rc = pool_init_streams(h);
     if (rc != HOPE_OK) return rc;
     HIPCHK(hipDeviceSynchronize());
+    { int rcg = settle_gen_nobst(h); if (rcg != HOPE_OK) return rcg; }
     std::vector<int32_t> l0, l1;
     build_pool_lists(h, h->pool_nobst_host.data(), h->pool_n, l0, l1);
     if (h->pactive < 0) h->pactive = 0;

@@ -31,6 +31,10 @@
 #include <vector>
 
 #include "hope_env.h"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>                  // (hipcc compiles this file as HIP: the shared core's functions are __host__ __device__)
+#endif
+#include "hope_scenegen_core.h"
 
 namespace {
 
@@ -420,6 +424,46 @@ int hope_scenegen_generate(int level, int bay_mode, int n, uint64_t seed, int64_
     if (nt == 1) work();
     else pool().run(nt, work);
     return err.load();
+}
+
+// The deterministic twin of hope_scenegen_generate: same signature and semantics, the recipe of hope_scenegen_core.h (exact
+// operations only), so that k_scenegen on the device gives the same bits.  Its lots are NOT those of hope_scenegen_generate (other
+// sin / cos / log), only equally distributed.  max_obstacles < 18 is refused up front: a lot holds up to 17 rings.
+int hope_scenegen_generate_det(int level, int bay_mode, int n, uint64_t seed, int64_t first_index, int max_obstacles, double* start,
+                               double* dest, double* bbox, double* verts, int32_t* n_obst, int32_t* case_id, int n_threads) {
+    if (level_index(level) < 0 || n < 0 || max_obstacles < SG_MAX_RINGS + 1 || !start || !dest || !bbox || !verts || !n_obst) return HOPE_EINVAL;
+    if (n == 0) return HOPE_OK;
+    int nt = n_threads > 0 ? n_threads : std::min(default_threads(), getenv("HOPE_HOST_THREADS") ? (1 << 20) : 64);
+    nt = std::max(1, std::min(nt, n / 64));
+    const int chunk = std::max(8, std::min(32, n / std::max(1, 8 * nt)));
+    nt = std::max(1, std::min(nt, (n + chunk - 1) / chunk));
+    std::atomic<int> next{0};
+    const std::function<void()> work = [&]() {
+        double ring_words[SG_MAX_RINGS * 8];
+        const SgRings R = {ring_words, 1};
+        for (;;) {
+            const int a = next.fetch_add(chunk);
+            if (a >= n) break;
+            for (int i = a; i < std::min(n, a + chunk); i++) {
+                int cid = 0;
+                const int nr = sg_generate_lot(level, bay_mode, seed, first_index + i, R, start + 3 * (size_t)i, dest + 3 * (size_t)i,
+                                               bbox + 4 * (size_t)i, &cid);
+                memcpy(verts + (size_t)i * max_obstacles * 8, ring_words, (size_t)nr * 8 * sizeof(double));
+                n_obst[i] = (int32_t)nr;
+                if (case_id) case_id[i] = cid;
+            }
+        }
+    };
+    if (nt == 1) work();
+    else pool().run(nt, work);
+    return HOPE_OK;
+}
+
+// y[i] = the generator core's log (sg_log) of x[i] > 0: what the tests measure against the platform's log
+int hope_scenegen_log_det(int n, const double* x, double* y) {
+    if (n < 0 || (n > 0 && (!x || !y))) return HOPE_EINVAL;
+    for (int i = 0; i < n; i++) y[i] = sg_log(x[i]);
+    return HOPE_OK;
 }
 
 }  // extern "C"

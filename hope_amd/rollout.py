@@ -141,7 +141,8 @@ class HopeRollout:
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
         fresh_scenes: finished episodes continue on a NEW map drawn from the env's device-resident scene pool
         (ParkingBatch.set_pool / set_dlp_cases), as the reference's loop does with `env.reset(...)`; otherwise on the same map.
-        pool_refresher: a `scene_gen.PoolRefresher`; the trainers poll it after every update, so the pool of generated lots is
+        pool_refresher: a `scene_gen.PoolRefresher` (host generator + upload) or `scene_gen.DevicePoolRefresher` (lots drawn on the
+        device); the trainers poll it after every update, so the pool of generated lots is
         replaced by new ones in the background (asynchronous upload, no synchronisation with the step loop)."""
         self.env, self.agent, self.use_mask, self.fresh = env, agent, use_mask, fresh_scenes
         self.refresher = pool_refresher

@@ -30,6 +30,54 @@ def generate_arrays(level, n, seed=0, max_obst=128, first_index=0, bay_mode=-1, 
     return start, dest, bbox, verts, nob, np.full((n, max_obst), 4, np.int32), cid
 
 
+def generate_arrays_det(level, n, seed=0, max_obst=128, first_index=0, bay_mode=-1, threads=0):
+    """generate_arrays from the deterministic recipe (hope_scenegen_generate_det, hope_amd/csrc/hope_scenegen_core.h): the host
+    twin of the device generator.  Same distributions as generate_arrays, other lots (exact arithmetic instead of glibc's
+    sin / cos / log); the result depends on (level, seed, first_index + i, bay_mode) only.  max_obst >= 18."""
+    lib = L.load_library()
+    start, dest, bbox = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
+    verts = np.zeros((n, max_obst, 4, 2))
+    nob, cid = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    L.check(lib.hope_scenegen_generate_det(LEVEL_ID[level], int(bay_mode), int(n), int(seed) & (2 ** 64 - 1), int(first_index), int(max_obst),
+                                           start.ctypes.data, dest.ctypes.data, bbox.ctypes.data, verts.ctypes.data, nob.ctypes.data,
+                                           cid.ctypes.data, int(threads)), 'hope_scenegen_generate_det')
+    return start, dest, bbox, verts, nob, np.full((n, max_obst), 4, np.int32), cid
+
+
+def generate_arrays_device(level, n, seed=0, max_obst=128, first_index=0, bay_mode=-1, device='cuda:0', out=None):
+    """the lots of generate_arrays_det, bit for bit, drawn by the HIP kernel k_scenegen on `device` (asynchronous on the current
+    stream) -> torch tensors (start[n,3], dest[n,3], bbox[n,4], verts[n,max_obst,4,2], n_obst[n], case_id[n]).  `out`: such a
+    tuple to write into (rows of verts beyond n_obst are left untouched; fresh tensors are zero-filled)."""
+    import torch
+    lib = L.load_library()
+    device = torch.device(device)
+    if out is None:
+        f64 = dict(dtype=torch.float64, device=device)
+        out = (torch.zeros((n, 3), **f64), torch.zeros((n, 3), **f64), torch.zeros((n, 4), **f64), torch.zeros((n, max_obst, 4, 2), **f64),
+               torch.zeros(n, dtype=torch.int32, device=device), torch.zeros(n, dtype=torch.int32, device=device))
+    start, dest, bbox, verts, nob, cid = out
+    for t, shp, dt in zip(out, ((n, 3), (n, 3), (n, 4), (n, max_obst, 4, 2), (n,), (n,)), (torch.float64,) * 4 + (torch.int32,) * 2):
+        assert tuple(t.shape) == shp and t.dtype == dt and t.is_contiguous() and t.device == device, 'generate_arrays_device: bad output tensor'
+    stream = torch.cuda.current_stream(device).cuda_stream
+    L.check(lib.hope_scenegen_generate_device(device.index or 0, LEVEL_ID[level], int(bay_mode), int(n), int(seed) & (2 ** 64 - 1),
+                                              int(first_index), int(max_obst), start.data_ptr(), dest.data_ptr(), bbox.data_ptr(),
+                                              verts.data_ptr(), nob.data_ptr(), cid.data_ptr(), stream), 'hope_scenegen_generate_device')
+    return start, dest, bbox, verts, nob, cid
+
+
+def pool_level_counts(n_pool, levels):
+    """lots per level id (Normal, Complex, Extrem) of a pool split as PoolRefresher splits it: n_pool // len(levels) each, the
+    last level takes the remainder.  The levels must come in the order Normal < Complex < Extrem, each at most once."""
+    ids = [LEVEL_ID[lv] for lv in levels]
+    if not ids or ids != sorted(set(ids)):
+        raise ValueError(f'levels must be a non-empty, increasing selection of Normal, Complex, Extrem: {levels}')
+    per = int(n_pool) // len(ids)
+    counts = [0, 0, 0]
+    for j, i in enumerate(ids):
+        counts[i] = int(n_pool) - per * (len(ids) - 1) if j == len(ids) - 1 else per
+    return counts
+
+
 def mixed_arrays(n, levels=('Normal', 'Complex', 'Extrem', 'dlp'), seed=0, max_obst=128, threads=0, dlp_pool=None):
     """n scenes, scene k of level levels[k % len(levels)] -> (start, dest, bbox, verts, n_obst, nvert) like pack_scenes"""
     start, dest, bbox = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
@@ -127,3 +175,28 @@ class PoolRefresher:
             self.thread.join()
             self.thread = None
         self.env._refresher_filling = False
+
+
+class DevicePoolRefresher:
+    """PoolRefresher without the host: every poll() issues one hope_env_generate_pool -- the HIP generator k_scenegen fills the
+    pool set the step kernels are not reading, on the handle's pool stream, and the sets are swapped as commit_pool does (relaxed:
+    as commit_pool(relaxed=True)).  No generator thread, pinned staging or upload.  Batch b of the run draws lots
+    first_index = b * n_pool of every level, the convention of PoolRefresher; the lots are those of generate_arrays_det.
+    Same surface as PoolRefresher where the trainers use it (poll, commits, batch, close)."""
+
+    def __init__(self, env, n_pool, levels=('Normal', 'Complex', 'Extrem'), seed=0, relaxed=False):
+        self.env, self.n, self.levels, self.seed, self.relaxed = env, int(n_pool), tuple(levels), int(seed), bool(relaxed)
+        pool_level_counts(self.n, self.levels)          # (refuses a bad level list here, not at the first poll)
+        self.batch = 0
+        self.commits = 0
+        self.gen_seconds = 0.0                           # host seconds spent generating: none
+
+    def poll(self, wait=False):
+        """enqueue the next batch's generation + swap and return (True: a new pool was committed); never blocks"""
+        self.env.generate_pool(self.n, self.levels, seed=self.seed, batch=self.batch, relaxed=self.relaxed)
+        self.batch += 1
+        self.commits += 1
+        return True
+
+    def close(self):
+        pass

@@ -402,6 +402,33 @@ int hope_scenegen_generate(int level, int bay_mode, int n, uint64_t seed, int64_
 /* the fan-out hope_scenegen_generate uses for n_threads <= 0 in this process, now */
 int hope_scenegen_default_threads(void);
 
+/* ---- the deterministic generator: one recipe for host and device (hope_amd/csrc/hope_scenegen_core.h) ----------------------------
+ * hope_scenegen_generate calls the platform's sin / cos / log, which no device kernel can reproduce bit for bit.  The entry points
+ * below draw the SAME recipe (same draws in the same order from the same (seed, index) stream, same rejection rules) with
+ * operations IEEE-754 defines exactly, so host and device agree on every bit.  Their lots are distributed as those of
+ * hope_scenegen_generate, but are not the same lots.  A lot holds up to 17 obstacles: max_obstacles < 18 is HOPE_EINVAL.
+ * (Additive to ABI 8.) */
+/* the host twin: signature and semantics of hope_scenegen_generate (the result does not depend on n_threads) */
+int hope_scenegen_generate_det(int level, int bay_mode, int n, uint64_t seed, int64_t first_index, int max_obstacles, double *start,
+                               double *dest, double *bbox, double *verts, int32_t *n_obst, int32_t *case_id, int n_threads);
+/* the same lots drawn by the kernel k_scenegen on device `device_id`, asynchronously on `stream`, into caller-owned DEVICE buffers
+ * of the same layout (case_id may be NULL); no handle involved.  Bit-equal to hope_scenegen_generate_det. */
+int hope_scenegen_generate_device(int device_id, int level, int bay_mode, int n, uint64_t seed, int64_t first_index, int max_obstacles,
+                                  double *start, double *dest, double *bbox, double *verts, int32_t *n_obst, int32_t *case_id, void *stream);
+/* y[i] = the generator's own log of x[i] > 0 (exact operations only; what the tests measure against the platform's log) */
+int hope_scenegen_log_det(int n, const double *x, double *y);
+/* A pool refill that never leaves the device: fills the pool set the kernels are NOT reading with n_per_level[0] Normal, then
+ * n_per_level[1] Complex, then n_per_level[2] Extrem lots (sum = n_pool; lot k of level l is lot first_index + k of
+ * hope_scenegen_generate_det for seed * 1000003 + l, bay_mode -1) and swaps it in exactly as hope_env_commit_pool (relaxed == 0:
+ * launches enqueued afterwards wait in stream order for the generator and draw from the new pool) or hope_env_commit_pool_relaxed
+ * (relaxed != 0: the new pool takes over at the first step enqueued after the generator has finished) does.  The kernel writes the
+ * pool's own formats (obstacle tiles, counts, constant records) on the handle's pool stream; no host thread, pinned staging or
+ * upload is involved, and the call never synchronises with the step kernels.  Dragon-Lake cases stay drawable.
+ * hope_env_pool_generation folds in a hash of (n_pool, n_per_level, seed, first_index).  HOPE_EINVAL: n_pool <= 0, a negative
+ * count, counts that do not sum to n_pool, a handle with max_obstacles < 18; HOPE_ESTATE: a hope_env_pool_staging fill that has
+ * not been committed. */
+int hope_env_generate_pool(hope_env_t *h, int n_pool, const int32_t *n_per_level /*[3]*/, uint64_t seed, int64_t first_index, int relaxed);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
