@@ -25,6 +25,9 @@ def main():
     ap.add_argument('--device-pool', type=int, default=0, metavar='LOTS',
                     help='also run a short PPO loop whose finished episodes draw new maps from a pool of LOTS generated lots that is '
                          'refilled ON THE DEVICE after every update (scene_gen.DevicePoolRefresher: no host generator thread, no upload)')
+    ap.add_argument('--curriculum', action='store_true',
+                    help='with --device-pool: pick the new maps with the device-side curriculum (SceneChoose / DlpCaseChoose of '
+                         'train_HOPE_sac.py: outcomes tallied per scene type, draw weights rebuilt after every PPO update)')
     args = ap.parse_args()
     rank, world, local = D.init_from_env()
     dev = f'cuda:{local}'
@@ -54,13 +57,20 @@ def main():
         ref = DevicePoolRefresher(env, args.device_pool, levels, seed=7 + rank, relaxed=True)
         ref.batch = 1
         tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
-                        seed=rank, fresh_scenes=True, pool_refresher=ref)
+                        seed=rank, fresh_scenes=True, pool_refresher=ref, curriculum={} if args.curriculum else None)
         for _ in range(16):
             tr.step()
         torch.cuda.synchronize()
         if rank == 0:
             print(f'  device pool: {tr.updates} PPO updates, {ref.commits} refills of {args.device_pool} lots generated on the device, '
                   f'pool generation {env.pool_generation():#x}')
+            if args.curriculum:
+                st = tr.stats()
+                cs = env.curriculum_state()
+                print('  curriculum: ' + ', '.join(f'{k} {v:.3f}' for k, v in st.items() if k.startswith('success_rate_')) +
+                      f'; q = {np.round(cs["q"], 3).tolist()} after {cs["updates"]} updates')
+        if args.curriculum:
+            env.disable_curriculum()
     # evaluation as eval_utils.py does it (one episode per slot, per-level table), records gathered over the ranks
     from hope_amd import agents as A
     from hope_amd import evaluate as E

@@ -5,6 +5,7 @@ Public surface:
   hope_amd.CarParking / CarParkingWrapper   N=1 look-alikes of the reference env classes
   hope_amd.scenes                    DLP scene pool + Normal/Complex/Extrem generator (host side)
   hope_amd.tables                    ActionMask / lidar tables (host side, numpy)
+  hope_amd.curriculum                the map curriculum's rule in numpy + its host twin (SceneChoose / DlpCaseChoose)
 """
 from .build import build_extension, lib_path  # noqa: F401
 from ._lib import load_library, HopeError  # noqa: F401

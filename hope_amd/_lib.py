@@ -21,7 +21,11 @@ ABI_VERSION = 8
 
 EXPORTS = ['hope_env_create', 'hope_env_destroy', 'hope_last_error', 'hope_abi_version', 'hope_env_upload_tables',
            'hope_env_set_scenes', 'hope_env_step', 'hope_env_wait_rs', 'hope_env_last_step', 'hope_env_wait_rs_step', 'hope_env_download_n_obst', 'hope_env_queue_check', 'hope_env_reset_obs', 'hope_env_download_state',
-           'hope_env_upload_state', 'hope_env_restart', 'hope_env_set_pool', 'hope_env_pool_staging', 'hope_env_commit_pool', 'hope_env_commit_pool_relaxed', 'hope_env_pool_staging_ready', 'hope_env_pool_generation', 'hope_env_redraw', 'hope_env_set_redraw_seed', 'hope_env_download_pool_index', 'hope_env_set_dlp_cases', 'hope_env_pool_overflow', 'hope_env_set_draw_class', 'hope_env_download_scenes', 'hope_env_download_pool_state', 'hope_env_restore_maps', 'hope_env_kernel_ms', 'hope_env_kernel_union_ms', 'hope_env_profile_kernels', 'hope_debug_math', 'hope_debug_traffic', 'hope_debug_mask_lut', 'hope_debug_rs_prof', 'hope_debug_rs_log', 'hope_debug_rs_filter_stats', 'hope_debug_rs_filter_dump', 'hope_debug_step_prof', 'hope_debug_census', 'hope_scenegen_generate', 'hope_scenegen_default_threads', 'hope_scenegen_generate_det', 'hope_scenegen_generate_device', 'hope_scenegen_log_det', 'hope_env_generate_pool', 'hope_env_num_scenes', 'hope_env_max_obstacles', 'hope_env_device_arch']
+           'hope_env_upload_state', 'hope_env_restart', 'hope_env_set_pool', 'hope_env_pool_staging', 'hope_env_commit_pool', 'hope_env_commit_pool_relaxed', 'hope_env_pool_staging_ready', 'hope_env_pool_generation', 'hope_env_redraw', 'hope_env_set_redraw_seed', 'hope_env_download_pool_index', 'hope_env_set_dlp_cases', 'hope_env_pool_overflow', 'hope_env_set_draw_class', 'hope_env_download_scenes', 'hope_env_download_pool_state', 'hope_env_restore_maps', 'hope_env_kernel_ms', 'hope_env_kernel_union_ms', 'hope_env_profile_kernels', 'hope_debug_math', 'hope_debug_traffic', 'hope_debug_mask_lut', 'hope_debug_rs_prof', 'hope_debug_rs_log', 'hope_debug_rs_filter_stats', 'hope_debug_rs_filter_dump', 'hope_debug_step_prof', 'hope_debug_census', 'hope_scenegen_generate', 'hope_scenegen_default_threads', 'hope_scenegen_generate_det', 'hope_scenegen_generate_device', 'hope_scenegen_log_det', 'hope_env_generate_pool', 'hope_env_curriculum_enable', 'hope_env_curriculum_disable', 'hope_env_set_pool_buckets', 'hope_env_curriculum_tally', 'hope_env_curriculum_update', 'hope_env_curriculum_state', 'hope_env_curriculum_set_windows', 'hope_env_curriculum_download_lists', 'hope_curriculum_lists_host', 'hope_curriculum_fold_host', 'hope_env_num_scenes', 'hope_env_max_obstacles', 'hope_env_device_arch']
+
+
+CURRICULUM_LIST_LEN = 1 << 20
+BUCKET_UNLABELLED = 255
 
 
 class HopeError(RuntimeError):
@@ -32,6 +36,18 @@ class StepOut(C.Structure):
     _fields_ = [('lidar', C.c_void_p), ('action_mask', C.c_void_p), ('target', C.c_void_p), ('reward', C.c_void_p),
                 ('reward_info', C.c_void_p), ('status', C.c_void_p), ('done', C.c_void_p), ('pose', C.c_void_p),
                 ('rs_word', C.c_void_p), ('rs_lengths', C.c_void_p), ('img', C.c_void_p)]
+
+
+class CurriculumParams(C.Structure):
+    """hope_curriculum_params; the defaults are the reference's constants (train_HOPE_sac.py:30, :35, :63, :66, :77, :80, :88, :91)"""
+    _fields_ = [('target', C.c_double * 4), ('type_window', C.c_double), ('case_window', C.c_double), ('type_fail_min', C.c_double),
+                ('case_fail_min', C.c_double), ('worst_share', C.c_double), ('case_uniform', C.c_double), ('type_horizon', C.c_int64),
+                ('case_horizon', C.c_int64)]
+
+    def __init__(self, target=(0.95, 0.95, 0.9, 0.99), type_window=250.0, case_window=10.0, type_fail_min=0.01, case_fail_min=0.005,
+                 worst_share=0.5, case_uniform=0.2, type_horizon=200, case_horizon=500):
+        super().__init__((C.c_double * 4)(*target), type_window, case_window, type_fail_min, case_fail_min, worst_share, case_uniform,
+                         type_horizon, case_horizon)
 
 
 _lib = None
@@ -103,6 +119,16 @@ def load_library():
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hope_scenegen_log_det.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.hope_env_generate_pool.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_int]
+    L.hope_env_curriculum_enable.argtypes = [C.c_void_p, C.c_void_p]
+    L.hope_env_curriculum_disable.argtypes = [C.c_void_p]
+    L.hope_env_set_pool_buckets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.hope_env_curriculum_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hope_env_curriculum_update.argtypes = [C.c_void_p, C.c_void_p]
+    L.hope_env_curriculum_state.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+    L.hope_env_curriculum_set_windows.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.hope_env_curriculum_download_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hope_curriculum_lists_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+    L.hope_curriculum_fold_host.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]
     L.hope_env_num_scenes.argtypes = [C.c_void_p]
     L.hope_env_max_obstacles.argtypes = [C.c_void_p]
     if L.hope_abi_version() != ABI_VERSION:

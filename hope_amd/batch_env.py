@@ -161,6 +161,74 @@ class ParkingBatch:
         self.pool_size = int(n_pool)
         return self
 
+    # -- curriculum for new-map draws (hope_env.h; rule: hope_amd/curriculum.py) --------------------------------------
+    def enable_curriculum(self, **params):
+        """tally episode outcomes per bucket on the device and draw new maps from weighted lists rebuilt from them (SceneChoose /
+        DlpCaseChoose of train_HOPE_sac.py:23-97).  params: fields of _lib.CurriculumParams (default: the reference's constants).
+        Needs a pool or Dragon-Lake cases; off by default."""
+        p = L.CurriculumParams(**params)
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_curriculum_enable(self.h, C.byref(p)), 'hope_env_curriculum_enable')
+        return self
+
+    def disable_curriculum(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_curriculum_disable(self.h), 'hope_env_curriculum_disable')
+        return self
+
+    def set_pool_buckets(self, buckets):
+        """level (0 Normal, 1 Complex, 2 Extrem; 255 unlabelled) of every entry of the resident pool (generate_pool labels its own)"""
+        b = np.ascontiguousarray(buckets, dtype=np.uint8)
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_set_pool_buckets(self.h, len(b), b.ctypes.data), 'hope_env_set_pool_buckets')
+        return self
+
+    def curriculum_tally(self):
+        """count the episodes the last step finished (its own status / done buffers), asynchronously on the current stream"""
+        L.check(self.lib.hope_env_curriculum_tally(self.h, C.c_void_p(self.status.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                                   self._stream()), 'hope_env_curriculum_tally')
+        return self
+
+    def curriculum_update(self):
+        """fold the tallies into the windows and rebuild the weighted draw lists (asynchronous; applied at the next step)"""
+        L.check(self.lib.hope_env_curriculum_update(self.h, self._stream()), 'hope_env_curriculum_update')
+        return self
+
+    def curriculum_state(self):
+        """{'episodes', 'successes' (cumulative), 'win_n', 'win_s', 'prob' (q_0..q_3, then p_c): [4 + n_cases]; 'q', 'pw': [4];
+        'updates', 'unlabelled_episodes', 'unlabelled_successes', 'on'} -- host-synchronous"""
+        nb = C.c_int32(0)
+        misc = np.zeros(4, np.uint64)
+        L.check(self.lib.hope_env_curriculum_state(self.h, C.byref(nb), None, None, None, None, None, None, misc.ctypes.data), 'hope_env_curriculum_state')
+        out = {'on': bool(misc[3]), 'updates': int(misc[0]), 'n_buckets': int(nb.value)}
+        if not out['on']:
+            return out
+        n = nb.value
+        e, s = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        wn, ws, prob, pw = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(4)
+        L.check(self.lib.hope_env_curriculum_state(self.h, None, e.ctypes.data, s.ctypes.data, wn.ctypes.data, ws.ctypes.data, prob.ctypes.data,
+                                                   pw.ctypes.data, misc.ctypes.data), 'hope_env_curriculum_state')
+        out.update(episodes=e, successes=s, win_n=wn, win_s=ws, prob=prob, q=prob[:4].copy(), pw=pw, updates=int(misc[0]),
+                   unlabelled_episodes=int(misc[1]), unlabelled_successes=int(misc[2]))
+        return out
+
+    def curriculum_set_windows(self, win_n, win_s, episodes, successes):
+        """set the windows and cumulative counters by hand (checkpoint restore, tests) and rebuild the lists from them"""
+        a = [np.ascontiguousarray(win_n, dtype=np.float64), np.ascontiguousarray(win_s, dtype=np.float64),
+             np.ascontiguousarray(episodes, dtype=np.uint64), np.ascontiguousarray(successes, dtype=np.uint64)]
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_curriculum_set_windows(self.h, len(a[0]), *[x.ctypes.data for x in a]), 'hope_env_curriculum_set_windows')
+        return self
+
+    def curriculum_lists(self):
+        """(list of class 0, list of class 1, positions [2, n_buckets]) as the next step reads them; a class without entries: all -1"""
+        nb = C.c_int32(0)
+        L.check(self.lib.hope_env_curriculum_state(self.h, C.byref(nb), None, None, None, None, None, None, None), 'hope_env_curriculum_state')
+        l0, l1 = np.full(L.CURRICULUM_LIST_LEN, -1, np.int32), np.full(L.CURRICULUM_LIST_LEN, -1, np.int32)
+        pos = np.zeros((2, nb.value), np.int32)
+        L.check(self.lib.hope_env_curriculum_download_lists(self.h, l0.ctypes.data, l1.ctypes.data, pos.ctypes.data), 'hope_env_curriculum_download_lists')
+        return l0, l1, pos
+
     def set_dlp_cases(self, pool=None):
         """make the Dragon-Lake-Parking cases (a `DlpScenePool`, default data/dlp_scenes.npz) drawable on the device: at episode
         turnover a large-tile scene then gets a case with a freshly drawn start candidate, jitter, flips and obstacle cull

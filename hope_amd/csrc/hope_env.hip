@@ -18,6 +18,7 @@
 #include "hope_obs_pair.h"
 #include "hope_motion_pair.h"
 #include "hope_scenegen_kernel.h"
+#include "hope_curriculum_kernel.h"
 
 using namespace hope;
 
@@ -122,7 +123,14 @@ struct hope_env {
     int32_t* pool_nobst = nullptr;  // [pool_n]
     // double-buffered storage behind the pointers above: a new pool is uploaded (asynchronously, from pinned staging) into the
     // set the step kernels are NOT reading and swapped in by stream order (hope_env_pool_staging / hope_env_commit_pool)
-    struct PoolSet { double* verts = nullptr; double* c = nullptr; int32_t* nobst = nullptr; int32_t* list[2] = {nullptr, nullptr}; int cap = 0, list_cap = 0; };
+    struct PoolSet { double* verts = nullptr; double* c = nullptr; int32_t* nobst = nullptr; int32_t* list[2] = {nullptr, nullptr}; int cap = 0, list_cap = 0;
+                     // curriculum labels of the set's entries (device table: written while the curriculum is on)
+                     uint8_t* label = nullptr;
+                     int n_pool = 0, npool_cls[2] = {0, 0};    // entries, and the pool entries (without the cases) at the head of list[c]
+                     int lab_kind = 0;                         // 0: all unlabelled, 1: generated (gen_counts lots per level, in order), 2: lab_host
+                     int gen_counts[3] = {0, 0, 0};
+                     std::vector<uint8_t> lab_host;            // hope_env_set_pool_buckets
+                     int32_t* sorted_own[2] = {nullptr, nullptr}; int sorted_own_cap = 0; };   // lab_kind 2: list[c]'s pool entries ordered by label
     PoolSet pset[2];
     int pactive = -1;
     struct PoolStage { double* start = nullptr; double* dest = nullptr; double* bbox = nullptr; double* verts = nullptr; int32_t* nobst = nullptr;
@@ -164,6 +172,23 @@ struct hope_env {
     int queue_of_role[N_ROLES] = {-1, -1, -1, -1, -1, -1, -1, -1};   // measured hardware-queue class of role r's stream ([0]: the NULL stream)
     int n_queues = 0;
     double queue_check_ms = 0.0;
+    // curriculum for new-map draws (hope_curriculum_kernel.h): device tally + weighted draw lists, double-buffered like the pool sets
+    struct Curriculum {
+        bool on = false;
+        hope_curriculum_params P = {};
+        int n_cases = 0, nb = 0;
+        void* mem = nullptr;                                // the arrays of `dev`
+        CwDev dev = {};
+        uint8_t* scene_bucket = nullptr;                    // [n] bucket of the map a scene holds
+        uint32_t* noted_ep = nullptr;                       // [n] the scene's redraw counter when that bucket was noted
+        int32_t* wl[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [buffer][class][CW_LIST_LEN]
+        int32_t* prefix[2] = {nullptr, nullptr};            // [buffer][2][CW_MAX_GROUPS + 1]
+        int wactive = -1;                                   // buffer the next step reads
+        CwClass cls[2] = {};                                // what the active buffer's lists are made of
+        uint64_t updates = 0;
+        hipEvent_t ev_order = nullptr;
+    } cur;
+    int draw_set = -1;                                      // pool set the last step / hope_env_redraw drew from
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -555,6 +580,7 @@ const char* hope_last_error(void) { return g_err.c_str(); }
 int hope_abi_version(void) { return HOPE_ABI_VERSION; }
 
 static int destroy_impl(hope_env_t* h);
+static void cur_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -817,6 +843,8 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     for (void* q : {(void*)h->pstage.start, (void*)h->pstage.dest, (void*)h->pstage.bbox, (void*)h->pstage.verts, (void*)h->pstage.nobst, (void*)h->pstage.list}) if (q) hipHostFree(q);
     for (int i = 0; i < 2; i++) { if (h->gen_nobst[i]) hipHostFree(h->gen_nobst[i]); if (h->ev_gen_copied[i]) hipEventDestroy(h->ev_gen_copied[i]); }
     for (hipEvent_t e : h->free_events) hipEventDestroy(e);
+    cur_free(h);
+    for (auto& ps : h->pset) for (void* q : {(void*)ps.label, (void*)ps.sorted_own[0], (void*)ps.sorted_own[1]}) if (q) hipFree(q);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
     for (void* q : ptrs)
@@ -982,6 +1010,7 @@ static int upload_scenes(hope_env_t* h, const int32_t* ids, int n, const double*
                          int32_t* d_nobst, double* d_verts, float4* d_obb, double* d_traj, int32_t* d_traj_len, int32_t* d_traj_valid,
                          int32_t* d_layer_valid);
 static int apply_pending_pool(hope_env_t* h, bool wait);
+static int cur_on_swap(hope_env_t* h);
 
 // The dense per-class scene lists of the launch chains and the per-slot class byte (host mirror; reset-time only).  A slot's class
 // decides which launch chain steps it (LDS tile of 32 or max_obstacles obstacles) AND which pool entries it draws at episode
@@ -1038,6 +1067,11 @@ int hope_env_set_scenes(hope_env_t* h, const int32_t* scene_ids, int n, const do
         h->slot_cls_host[scene_ids[k]] = (h->max_obst > SMALL_TILE && n_obst[k] > SMALL_TILE) ? 1 : 0;
     }
     { int rc = rebuild_class_lists(h); if (rc != HOPE_OK) return rc; }
+    if (h->cur.on) {                                        // the curriculum: an uploaded map is unlabelled (ids: head of the staging)
+        hipLaunchKernelGGL(k_curriculum_forget, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const int32_t*)h->stage, h->cur.scene_bucket,
+                           h->episode, h->cur.noted_ep);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipDeviceSynchronize());
     h->have_scenes = true;
     return HOPE_OK;
@@ -1047,12 +1081,20 @@ int hope_env_set_scenes(hope_env_t* h, const int32_t* scene_ids, int n, const do
 // uploaded last, the next ring slot is filled and copied on the caller's stream -- ahead of every launch of the step, whose chains
 // fork from that stream.  A slot is immutable while launches may read it: it comes round again after COLD_RING changes, and its
 // event (the copy that last filled it) is waited for before the pinned source is rewritten.
+// the lists a draw indexes: the uniform base lists of the active pool set, or the curriculum's weighted lists of the same entries
+static void draw_lists(const hope_env_t* h, const int32_t** lists, int* counts) {
+    for (int c = 0; c < 2; c++) {
+        const bool weighted = h->cur.on && h->cur.wactive >= 0 && h->pool_cls_n[c] > 0;
+        lists[c] = weighted ? h->cur.wl[h->cur.wactive][c] : h->pool_cls[c];
+        counts[c] = weighted ? CW_LIST_LEN : h->pool_cls_n[c];
+    }
+}
 static int sync_cold(hope_env_t* h, hipStream_t s) {
     StepCold c;
     memset(&c, 0, sizeof(c));
     c.traj = h->traj; c.traj_len = h->traj_len; c.traj_valid = h->traj_valid; c.layer_valid = h->layer_valid;
     c.pool_verts = h->pool_verts; c.pool_c = h->pool_c; c.pool_nobst = h->pool_nobst;
-    c.pool_cls[0] = h->pool_cls[0]; c.pool_cls[1] = h->pool_cls[1]; c.pool_cls_n[0] = h->pool_cls_n[0]; c.pool_cls_n[1] = h->pool_cls_n[1];
+    draw_lists(h, c.pool_cls, c.pool_cls_n);
     c.cur_pool = h->cur_pool; c.episode = h->episode; c.redraw_seed = h->redraw_seed;
     c.dlp = h->dlp; c.pool_overflow = h->pool_overflow; c.slot_cls = h->slot_cls;
     c.fverts = h->fverts; c.fbox = h->fbox; c.eflag = h->eflag;
@@ -1394,6 +1436,7 @@ static int launch_step(hope_env_t* h, const void* actions, const uint8_t* active
         h->pool_wait_pending = false;
     }
     { int rcc = sync_cold(h, s); if (rcc != HOPE_OK) return rcc; }
+    h->draw_set = h->pactive;
     struct LastStep {                                       // (the next pool upload must not overwrite a set this step still reads)
         hope_env_t* h; hipStream_t s;
         ~LastStep() { if (h->pactive >= 0 && h->ev_last_step && !h->last_via_steps) hipEventRecord(h->ev_last_step, s); }
@@ -1487,12 +1530,13 @@ static void build_pool_lists(hope_env_t* h, const int32_t* n_obst, int n_pool, s
 
 static int pool_set_reserve(hope_env_t* h, hope_env::PoolSet& ps, int n_pool, int n_list) {
     if (n_pool > ps.cap) {
-        for (void* q : {(void*)ps.verts, (void*)ps.c, (void*)ps.nobst}) if (q) hipFree(q);
-        ps.verts = ps.c = nullptr; ps.nobst = nullptr; ps.cap = 0;
+        for (void* q : {(void*)ps.verts, (void*)ps.c, (void*)ps.nobst, (void*)ps.label}) if (q) hipFree(q);
+        ps.verts = ps.c = nullptr; ps.nobst = nullptr; ps.label = nullptr; ps.cap = 0;
         const size_t P = (size_t)n_pool;
         hipError_t e_ = hipMalloc((void**)&ps.verts, P * h->max_obst * 8 * sizeof(double));
         if (e_ == hipSuccess) e_ = hipMalloc((void**)&ps.c, P * SC_WORDS * sizeof(double));
         if (e_ == hipSuccess) e_ = hipMalloc((void**)&ps.nobst, P * sizeof(int32_t));
+        if (e_ == hipSuccess) e_ = hipMalloc((void**)&ps.label, P);
         if (e_ != hipSuccess) return fail(HOPE_ENOMEM, std::string("hipMalloc pool: ") + hipGetErrorString(e_));
         ps.cap = n_pool;
     }
@@ -1544,11 +1588,11 @@ int hope_env_pool_staging_ready(hope_env_t* h) {
     return fail(HOPE_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
 }
 
+static int effective_generation(hope_env_t* h, uint64_t* generation);
 int hope_env_pool_generation(hope_env_t* h, uint64_t* generation) {
     if (!h || !generation) return fail(HOPE_EINVAL, "hope_env_pool_generation: null argument");
     { DeviceGuard guard(h->device); int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
-    *generation = h->pool_generation;
-    return HOPE_OK;
+    return effective_generation(h, generation);
 }
 
 // the host copy of a generated pool's obstacle counts (hope_env_generate_pool), once its kernel and copy have finished
@@ -1580,7 +1624,7 @@ static int apply_pending_pool(hope_env_t* h, bool wait) {
     h->pend.on = false;
     bump_pool_generation(h, h->pend.content);
     h->gen_host_set = h->pend.generated ? h->pend.set : -1; // (a generated pool: its counts are fetched when somebody asks)
-    return HOPE_OK;
+    return cur_on_swap(h);
 }
 
 static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed);
@@ -1640,6 +1684,11 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
     if (!l0.empty()) HIPCHK(hipMemcpyAsync(ps.list[0], h->pstage.list, l0.size() * sizeof(int32_t), hipMemcpyHostToDevice, us));
     if (!l1.empty()) HIPCHK(hipMemcpyAsync(ps.list[1], h->pstage.list + l0.size(), l1.size() * sizeof(int32_t), hipMemcpyHostToDevice, us));
     HIPCHK(hipEventRecord(h->ev_pool_copied, us));          // the pinned staging may be refilled once this has passed
+    {
+        const int nc = h->dlp.n_cases, two = h->max_obst > SMALL_TILE;
+        ps.n_pool = n_pool; ps.npool_cls[0] = (int)l0.size() - (two ? 0 : nc); ps.npool_cls[1] = (int)l1.size() - (two ? nc : 0);
+        ps.lab_kind = 0; ps.lab_host.clear();
+    }
     h->pstage.busy = true;
     h->pstage.staged = false;
     hipLaunchKernelGGL(k_set_scene_consts, dim3((n_pool + 127) / 128), dim3(128), 0, us, n_pool, (const int32_t*)nullptr,
@@ -1682,7 +1731,7 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
     h->pactive = t;
     h->pool_wait_pending = true;
     bump_pool_generation(h, content);
-    return HOPE_OK;
+    return cur_on_swap(h);
 }
 
 int hope_env_set_pool(hope_env_t* h, int n_pool, const double* start, const double* dest, const double* bbox,
@@ -1778,6 +1827,9 @@ int hope_env_generate_pool(hope_env_t* h, int n_pool, const int32_t* n_per_level
     HIPCHK(hipEventRecord(h->ev_gen_copied[t], us));
     HIPCHK(hipEventRecord(h->ev_pool_ready, us));
     h->gen_nobst_n[t] = n_pool;
+    ps.n_pool = n_pool; ps.npool_cls[0] = n_pool; ps.npool_cls[1] = 0;
+    ps.lab_kind = 1; ps.lab_host.clear();
+    for (int l = 0; l < 3; l++) ps.gen_counts[l] = n_per_level[l];
     // identity of the new pool: a pure function of the arguments (the lots are a pure function of them)
     uint64_t content = 0x67656e706f6f6cull;
     content = fold64(content, (uint64_t)(uint32_t)n_pool);
@@ -1798,7 +1850,7 @@ int hope_env_generate_pool(hope_env_t* h, int n_pool, const int32_t* n_per_level
     h->gen_host_set = t;
     h->pool_wait_pending = true;
     bump_pool_generation(h, content);
-    return HOPE_OK;
+    return cur_on_swap(h);
 }
 
 // the class lists of the ACTIVE set after the Dragon-Lake cases changed (rare; host-synchronous)
@@ -1817,6 +1869,10 @@ static int refresh_pool_lists_sync(hope_env_t* h) {
     if (!l1.empty()) HIPCHK(hipMemcpy(ps.list[1], l1.data(), l1.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     h->pool_cls[0] = ps.list[0]; h->pool_cls[1] = ps.list[1];
     h->pool_cls_n[0] = (int)l0.size(); h->pool_cls_n[1] = (int)l1.size();
+    {
+        const int nc = h->dlp.n_cases, two = h->max_obst > SMALL_TILE;
+        ps.n_pool = h->pool_n; ps.npool_cls[0] = (int)l0.size() - (two ? 0 : nc); ps.npool_cls[1] = (int)l1.size() - (two ? nc : 0);
+    }
     return HOPE_OK;
 }
 
@@ -1825,6 +1881,7 @@ int hope_env_set_dlp_cases(hope_env_t* h, int n_cases, const double* dest, const
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
     if (!h || n_cases < 0 || (n_cases > 0 && (!dest || !cand_off || !cand || !case_set || n_sets <= 0 || !set_off || !set_verts)))
         return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: bad argument");
+    if (h->cur.on) return fail(HOPE_ESTATE, "hope_env_set_dlp_cases: the curriculum is on and its buckets are sized by the cases (hope_env_curriculum_disable first)");
     for (int c = 0; c < n_cases; c++) {
         if (cand_off[c + 1] <= cand_off[c]) return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: a case without start candidates");
         if (case_set[c] < 0 || case_set[c] >= n_sets) return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: case_set out of range");
@@ -1928,11 +1985,20 @@ int hope_env_redraw(hope_env_t* h, const uint8_t* mask, uint64_t seed, void* str
     if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
     { int rcp = apply_pending_pool(h, false); if (rcp != HOPE_OK) return rcp; }
     if (h->pool_wait_pending) { HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_pool_ready, 0)); h->pool_wait_pending = false; }
-    hipLaunchKernelGGL(k_redraw, dim3(h->n), dim3(WAVE), 0, (hipStream_t)stream, h->max_obst, mask, seed, h->pool_cls[0],
-                       h->pool_cls_n[0], h->pool_cls[1], h->pool_cls_n[1], h->pool_verts, h->pool_c, h->pool_nobst, h->verts,
+    const int32_t* dl[2]; int dn[2];
+    draw_lists(h, dl, dn);
+    h->draw_set = h->pactive;
+    hipLaunchKernelGGL(k_redraw, dim3(h->n), dim3(WAVE), 0, (hipStream_t)stream, h->max_obst, mask, seed, dl[0],
+                       dn[0], dl[1], dn[1], h->pool_verts, h->pool_c, h->pool_nobst, h->verts,
                        h->scene_c, h->n_obst, h->state, h->tstep, h->traj, h->traj_len, h->traj_valid, h->cur_pool, h->episode, h->obb,
                        h->dlp, h->pool_overflow, h->slot_cls, h->layer_valid, h->fverts, h->fbox, h->eflag);
     HIPCHK(hipGetLastError());
+    if (h->cur.on && h->pactive >= 0) {                     // the curriculum notes the buckets of the maps just drawn
+        const hope_env::PoolSet& ps = h->pset[h->pactive];
+        hipLaunchKernelGGL(k_curriculum_tally, dim3((h->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->n, (const int32_t*)nullptr,
+                           (const uint8_t*)nullptr, mask, h->cur_pool, ps.label, ps.n_pool, h->cur.n_cases, h->cur.scene_bucket, h->episode, h->cur.noted_ep, h->cur.dev);
+        HIPCHK(hipGetLastError());
+    }
     if (h->pactive >= 0 && h->ev_last_step) HIPCHK(hipEventRecord(h->ev_last_step, (hipStream_t)stream));
     return HOPE_OK;
 }
@@ -1958,9 +2024,11 @@ int hope_env_restore_maps(hope_env_t* h, const uint8_t* drawn /* host [N]: the s
     if (!h || !drawn || !episode) return fail(HOPE_EINVAL, "hope_env_restore_maps: null argument");
     { DeviceGuard guard0(h->device); int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }   // (compare generations after a pending swap)
     if (h->pool_n <= 0 && h->dlp.n_cases <= 0) return fail(HOPE_ESTATE, "hope_env_restore_maps: no scene pool");
-    if (pool_generation != 0 && pool_generation != h->pool_generation)
-        return fail(HOPE_ESTATE, "hope_env_restore_maps: the scene pool has been replaced since the snapshot (pool generation " +
-                                 std::to_string(h->pool_generation) + " now, " + std::to_string(pool_generation) + " in the snapshot): repeating the draws "
+    uint64_t gen_now = 0;
+    if (pool_generation != 0) { int rcg = effective_generation(h, &gen_now); if (rcg != HOPE_OK) return rcg; }
+    if (pool_generation != 0 && pool_generation != gen_now)
+        return fail(HOPE_ESTATE, "hope_env_restore_maps: the scene pool or the curriculum's draw lists have been replaced since the snapshot (pool generation " +
+                                 std::to_string(gen_now) + " now, " + std::to_string(pool_generation) + " in the snapshot): repeating the draws "
                                  "would give other maps -- snapshot refreshed runs with hope_env_download_scenes / hope_env_set_scenes");
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
@@ -1984,6 +2052,394 @@ int hope_env_download_pool_index(hope_env_t* h, int32_t* out) {
     if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, h->cur_pool, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+// ---- curriculum for new-map draws (include/hope_env.h; kernels: hope_curriculum_kernel.h, arithmetic: hope_curriculum_core.h) ----
+// The weighted lists live in two buffers like the pool sets: a rebuild fills the buffer the kernels are not reading on the pool
+// stream and publishes it through draw_lists / sync_cold; the next step waits for it in stream order (pool_wait_pending).
+static const hope_curriculum_params CW_DEFAULTS = {{0.95, 0.95, 0.9, 0.99}, 250.0, 10.0, 0.01, 0.005, 0.5, 0.2, 200, 500};
+
+static void cur_free(hope_env_t* h) {
+    hope_env::Curriculum& cu = h->cur;
+    for (void* q : {cu.mem, (void*)cu.scene_bucket, (void*)cu.noted_ep, (void*)cu.wl[0][0], (void*)cu.prefix[0]}) if (q) hipFree(q);
+    if (cu.ev_order) hipEventDestroy(cu.ev_order);
+    cu = hope_env::Curriculum{};
+}
+
+// what the class lists of pool set t are made of, and the order of their pool entries
+static void cur_set_groups(const hope_env_t* h, int t, CwClass cls[2], const int32_t* sorted[2]) {
+    const hope_env::PoolSet& ps = h->pset[t];
+    const bool two = h->max_obst > SMALL_TILE;
+    for (int c = 0; c < 2; c++) {
+        cls[c] = CwClass{};
+        cls[c].n_cases = c == (two ? 1 : 0) ? h->dlp.n_cases : 0;
+        sorted[c] = ps.list[c];
+        if (ps.lab_kind == 0) cls[c].cnt[3] = ps.npool_cls[c];
+        else if (ps.lab_kind == 1) { if (c == 0) for (int l = 0; l < 3; l++) cls[c].cnt[l] = ps.gen_counts[l]; }
+        else {
+            sorted[c] = ps.sorted_own[c];
+            // (counted again from the labels: cheap, and the only place that needs them)
+        }
+    }
+    if (ps.lab_kind == 2) {
+        for (int k = 0; k < ps.n_pool; k++) {
+            const int c = two && h->pool_nobst_host[k] > SMALL_TILE ? 1 : 0;
+            const int b = ps.lab_host[k];
+            cls[c].cnt[b < 3 ? b : 3]++;
+        }
+    }
+}
+
+// the device label table of set t (tally) on stream s
+static int cur_write_labels(hope_env_t* h, int t, hipStream_t s) {
+    hope_env::PoolSet& ps = h->pset[t];
+    if (ps.n_pool <= 0 || !ps.label) return HOPE_OK;
+    if (ps.lab_kind == 1) {
+        size_t off = 0;
+        for (int l = 0; l < 3; l++) { if (ps.gen_counts[l] > 0) HIPCHK(hipMemsetAsync(ps.label + off, l, (size_t)ps.gen_counts[l], s)); off += (size_t)ps.gen_counts[l]; }
+    } else if (ps.lab_kind == 2) HIPCHK(hipMemcpyAsync(ps.label, ps.lab_host.data(), (size_t)ps.n_pool, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemsetAsync(ps.label, CW_UNLABELLED, (size_t)ps.n_pool, s));
+    return HOPE_OK;
+}
+
+// weights + fill for the ACTIVE pool set into the buffer the kernels are not reading, on the pool stream; published at once
+static int cur_build_lists(hope_env_t* h, bool fold, hipStream_t after) {
+    hope_env::Curriculum& cu = h->cur;
+    int rc = pool_init_streams(h);
+    if (rc != HOPE_OK) return rc;
+    hipStream_t us = h->pool_stream;
+    if (fold) {                                              // the tallies enqueued so far come first
+        HIPCHK(hipEventRecord(cu.ev_order, after));
+        HIPCHK(hipStreamWaitEvent(us, cu.ev_order, 0));
+    }
+    // the target buffer was the active one until the previous swap: steps enqueued before that swap may still be reading it
+    if (h->pactive >= 0) {
+        HIPCHK(hipStreamWaitEvent(us, h->ev_last_step, 0));
+        if (h->last_via_steps) for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(us, h->ev_step[i], 0));
+    }
+    const int w = cu.wactive < 0 ? 0 : 1 - cu.wactive;
+    CwJob job{};
+    CwFill fl{};
+    job.P = cu.P; job.n_cases = cu.n_cases; job.fold = fold ? 1 : 0; job.prefix = cu.prefix[w];
+    cur_set_groups(h, h->pactive, job.cls, fl.sorted);
+    for (int c = 0; c < 2; c++) { fl.cls[c] = job.cls[c]; fl.out[c] = cu.wl[w][c]; cu.cls[c] = job.cls[c]; }
+    fl.G = cu.nb; fl.prefix = cu.prefix[w];
+    hipLaunchKernelGGL(k_curriculum_weights, dim3(1), dim3(64), 0, us, job, cu.dev);
+    hipLaunchKernelGGL(k_curriculum_fill, dim3(256, 2), dim3(256), 0, us, fl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_pool_ready, us));
+    cu.wactive = w;
+    h->pool_wait_pending = true;
+    return HOPE_OK;
+}
+
+// a pool set has just become the active one: its labels and weighted lists, before anything draws from it
+static int cur_on_swap(hope_env_t* h) {
+    if (!h->cur.on) return HOPE_OK;
+    int rc = pool_init_streams(h);
+    if (rc != HOPE_OK) return rc;
+    for (int c = 0; c < 2; c++)
+        if (h->pool_cls_n[c] > CW_LIST_LEN) return fail(HOPE_EINVAL, "curriculum: a draw list longer than HOPE_CURRICULUM_LIST_LEN entries");
+    rc = cur_write_labels(h, h->pactive, h->pool_stream);
+    if (rc != HOPE_OK) return rc;
+    return cur_build_lists(h, false, nullptr);
+}
+
+static int cur_init_scene_buckets(hope_env_t* h, hipStream_t s) {
+    const hope_env::PoolSet& ps = h->pset[h->pactive];
+    hipLaunchKernelGGL(k_curriculum_tally, dim3((h->n + 255) / 256), dim3(256), 0, s, h->n, (const int32_t*)nullptr, (const uint8_t*)nullptr,
+                       (const uint8_t*)nullptr, h->cur_pool, ps.label, ps.n_pool, h->cur.n_cases, h->cur.scene_bucket, h->episode, h->cur.noted_ep, h->cur.dev);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+static void cur_layout(hope_env::Curriculum& cu) {
+    const size_t nb = (size_t)cu.nb;
+    char* p = (char*)cu.mem;
+    cu.dev.episodes = (unsigned long long*)p; p += (nb + 1) * 8;
+    cu.dev.successes = (unsigned long long*)p; p += (nb + 1) * 8;
+    cu.dev.folded_e = (unsigned long long*)p; p += nb * 8;
+    cu.dev.folded_s = (unsigned long long*)p; p += nb * 8;
+    cu.dev.win_n = (double*)p; p += nb * 8;
+    cu.dev.win_s = (double*)p; p += nb * 8;
+    cu.dev.prob = (double*)p; p += nb * 8;
+    cu.dev.pw = (double*)p;
+}
+static size_t cur_mem_bytes(int nb) { return ((size_t)nb * 7 + 2 + 4) * 8; }
+
+int hope_env_curriculum_enable(hope_env_t* h, const hope_curriculum_params* params) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_enable: null handle");
+    const hope_curriculum_params P = params ? *params : CW_DEFAULTS;
+    if (!(P.type_window > 0.0) || !(P.case_window > 0.0) || !(P.type_fail_min > 0.0) || !(P.case_fail_min > 0.0) ||
+        !(P.worst_share >= 0.0 && P.worst_share <= 1.0) || !(P.case_uniform >= 0.0 && P.case_uniform <= 1.0))
+        return fail(HOPE_EINVAL, "hope_env_curriculum_enable: windows and failure floors must be positive, shares in [0, 1]");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
+    if ((h->pool_n <= 0 && h->dlp.n_cases <= 0) || h->pactive < 0)
+        return fail(HOPE_ESTATE, "hope_env_curriculum_enable: no scene pool and no Dragon-Lake cases (hope_env_set_pool / hope_env_generate_pool / hope_env_set_dlp_cases first)");
+    if (4 + h->dlp.n_cases > CW_MAX_GROUPS) return fail(HOPE_EINVAL, "hope_env_curriculum_enable: more than 250 Dragon-Lake cases (a bucket id is one byte)");
+    for (int c = 0; c < 2; c++)
+        if (h->pool_cls_n[c] > CW_LIST_LEN) return fail(HOPE_EINVAL, "hope_env_curriculum_enable: a draw list longer than HOPE_CURRICULUM_LIST_LEN entries");
+    HIPCHK(hipDeviceSynchronize());
+    { int rcg = settle_gen_nobst(h); if (rcg != HOPE_OK) return rcg; }
+    cur_free(h);
+    hope_env::Curriculum& cu = h->cur;
+    cu.P = P; cu.n_cases = h->dlp.n_cases; cu.nb = 4 + cu.n_cases;
+    hipError_t e_ = hipMalloc(&cu.mem, cur_mem_bytes(cu.nb));
+    if (e_ == hipSuccess) e_ = hipMalloc((void**)&cu.scene_bucket, (size_t)h->n);
+    if (e_ == hipSuccess) e_ = hipMalloc((void**)&cu.noted_ep, (size_t)h->n * sizeof(uint32_t));
+    if (e_ == hipSuccess) e_ = hipMalloc((void**)&cu.wl[0][0], (size_t)4 * CW_LIST_LEN * sizeof(int32_t));
+    if (e_ == hipSuccess) e_ = hipMalloc((void**)&cu.prefix[0], (size_t)4 * (CW_MAX_GROUPS + 1) * sizeof(int32_t));
+    if (e_ == hipSuccess) e_ = hipEventCreateWithFlags(&cu.ev_order, hipEventDisableTiming);
+    if (e_ != hipSuccess) { cur_free(h); return fail(HOPE_ENOMEM, std::string("hope_env_curriculum_enable: ") + hipGetErrorString(e_)); }
+    cu.wl[0][1] = cu.wl[0][0] + CW_LIST_LEN; cu.wl[1][0] = cu.wl[0][0] + 2 * (size_t)CW_LIST_LEN; cu.wl[1][1] = cu.wl[0][0] + 3 * (size_t)CW_LIST_LEN;
+    cu.prefix[1] = cu.prefix[0] + 2 * (CW_MAX_GROUPS + 1);
+    cur_layout(cu);
+    HIPCHK(hipMemset(cu.mem, 0, cur_mem_bytes(cu.nb)));
+    HIPCHK(hipMemset(cu.scene_bucket, CW_UNLABELLED, (size_t)h->n));
+    HIPCHK(hipMemset(cu.noted_ep, 0, (size_t)h->n * sizeof(uint32_t)));
+    HIPCHK(hipMemset(cu.wl[0][0], 0xFF, (size_t)4 * CW_LIST_LEN * sizeof(int32_t)));
+    HIPCHK(hipMemset(cu.prefix[0], 0, (size_t)4 * (CW_MAX_GROUPS + 1) * sizeof(int32_t)));
+    cu.on = true;
+    int rc = cur_on_swap(h);
+    if (rc == HOPE_OK) rc = cur_init_scene_buckets(h, h->pool_stream);
+    if (rc != HOPE_OK) { cur_free(h); return rc; }
+    HIPCHK(hipDeviceSynchronize());
+    return HOPE_OK;
+}
+
+int hope_env_curriculum_disable(hope_env_t* h) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_disable: null handle");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());                         // steps in flight read the weighted lists
+    cur_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_set_pool_buckets(hope_env_t* h, int n_pool, const uint8_t* bucket) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h || !bucket) return fail(HOPE_EINVAL, "hope_env_set_pool_buckets: null argument");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
+    if (h->pool_n <= 0 || h->pactive < 0) return fail(HOPE_ESTATE, "hope_env_set_pool_buckets: no scene pool");
+    if (n_pool != h->pool_n)
+        return fail(HOPE_EINVAL, "hope_env_set_pool_buckets: " + std::to_string(n_pool) + " labels for a resident pool of " + std::to_string(h->pool_n) + " entries");
+    for (int k = 0; k < n_pool; k++)
+        if (bucket[k] > 2 && bucket[k] != CW_UNLABELLED)
+            return fail(HOPE_EINVAL, "hope_env_set_pool_buckets: bucket id " + std::to_string((int)bucket[k]) + " of entry " + std::to_string(k) + " is out of range (0, 1, 2 or 255)");
+    HIPCHK(hipDeviceSynchronize());
+    { int rcg = settle_gen_nobst(h); if (rcg != HOPE_OK) return rcg; }
+    hope_env::PoolSet& ps = h->pset[h->pactive];
+    // the class lists' pool entries ordered by label (stable): what a weighted list cycles through per group
+    const bool two = h->max_obst > SMALL_TILE;
+    std::vector<int32_t> srt[2];
+    for (int g = 0; g < 4; g++)
+        for (int k = 0; k < n_pool; k++) {
+            const int b = bucket[k] < 3 ? bucket[k] : 3;
+            if (b == g) srt[two && h->pool_nobst_host[k] > SMALL_TILE ? 1 : 0].push_back(k);
+        }
+    if (n_pool > ps.sorted_own_cap) {
+        for (int c = 0; c < 2; c++) { if (ps.sorted_own[c]) hipFree(ps.sorted_own[c]); ps.sorted_own[c] = nullptr; }
+        ps.sorted_own_cap = 0;
+        for (int c = 0; c < 2; c++) {
+            hipError_t e_ = hipMalloc((void**)&ps.sorted_own[c], (size_t)n_pool * sizeof(int32_t));
+            if (e_ != hipSuccess) return fail(HOPE_ENOMEM, std::string("hipMalloc pool labels: ") + hipGetErrorString(e_));
+        }
+        ps.sorted_own_cap = n_pool;
+    }
+    for (int c = 0; c < 2; c++)
+        if (!srt[c].empty()) HIPCHK(hipMemcpy(ps.sorted_own[c], srt[c].data(), srt[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    ps.lab_host.assign(bucket, bucket + n_pool);
+    ps.lab_kind = 2;
+    if (h->cur.on) {
+        int rc = cur_on_swap(h);
+        if (rc == HOPE_OK) rc = cur_init_scene_buckets(h, h->pool_stream);
+        if (rc != HOPE_OK) return rc;
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return HOPE_OK;
+}
+
+int hope_env_curriculum_tally(hope_env_t* h, const int32_t* status, const uint8_t* done, void* stream) {
+    if (!h || !status || !done) return fail(HOPE_EINVAL, "hope_env_curriculum_tally: null argument");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_curriculum_tally: not a live handle (destroyed?)");
+    if (!h->cur.on) return fail(HOPE_ESTATE, "hope_env_curriculum_tally: the curriculum is off (hope_env_curriculum_enable first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    // the labels of the set the step just drew from: a relaxed commit may have swapped sets at that step, never after it
+    const int t = h->draw_set >= 0 ? h->draw_set : h->pactive;
+    const hope_env::PoolSet& ps = h->pset[t];
+    hipLaunchKernelGGL(k_curriculum_tally, dim3((h->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->n, status, done, (const uint8_t*)nullptr,
+                       h->cur_pool,
+                       ps.label, ps.n_pool, h->cur.n_cases, h->cur.scene_bucket, h->episode, h->cur.noted_ep, h->cur.dev);
+    HIPCHK(hipGetLastError());
+    // the tally reads the label table of set t: a later swap that rewrites that table on the pool stream waits for this event
+    if (h->pactive >= 0 && h->ev_last_step) HIPCHK(hipEventRecord(h->ev_last_step, (hipStream_t)stream));
+    return HOPE_OK;
+}
+
+int hope_env_curriculum_update(hope_env_t* h, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_update: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_curriculum_update: not a live handle (destroyed?)");
+    if (!h->cur.on) return fail(HOPE_ESTATE, "hope_env_curriculum_update: the curriculum is off (hope_env_curriculum_enable first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcp = apply_pending_pool(h, false); if (rcp != HOPE_OK) return rcp; }   // (lists are built for the set the next step draws from)
+    int rc = cur_build_lists(h, true, (hipStream_t)stream);
+    if (rc == HOPE_OK) h->cur.updates++;
+    return rc;
+}
+
+int hope_env_curriculum_state(hope_env_t* h, int32_t* n_buckets, uint64_t* episodes, uint64_t* successes, double* win_n, double* win_s,
+                              double* prob, double* pw, uint64_t* misc) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_state: null handle");
+    const hope_env::Curriculum& cu = h->cur;
+    if (n_buckets) *n_buckets = cu.on ? cu.nb : 4 + h->dlp.n_cases;
+    if (!cu.on) {
+        if (episodes || successes || win_n || win_s || prob || pw) return fail(HOPE_ESTATE, "hope_env_curriculum_state: the curriculum is off");
+        if (misc) misc[0] = misc[1] = misc[2] = misc[3] = 0;
+        return HOPE_OK;
+    }
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    const size_t nb = (size_t)cu.nb;
+    std::vector<uint64_t> e(nb + 1), s(nb + 1);
+    HIPCHK(hipMemcpy(e.data(), cu.dev.episodes, (nb + 1) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s.data(), cu.dev.successes, (nb + 1) * 8, hipMemcpyDeviceToHost));
+    if (episodes) memcpy(episodes, e.data(), nb * 8);
+    if (successes) memcpy(successes, s.data(), nb * 8);
+    if (win_n) HIPCHK(hipMemcpy(win_n, cu.dev.win_n, nb * 8, hipMemcpyDeviceToHost));
+    if (win_s) HIPCHK(hipMemcpy(win_s, cu.dev.win_s, nb * 8, hipMemcpyDeviceToHost));
+    if (prob) HIPCHK(hipMemcpy(prob, cu.dev.prob, nb * 8, hipMemcpyDeviceToHost));
+    if (pw) HIPCHK(hipMemcpy(pw, cu.dev.pw, 4 * 8, hipMemcpyDeviceToHost));
+    if (misc) { misc[0] = cu.updates; misc[1] = e[nb]; misc[2] = s[nb]; misc[3] = 1; }
+    return HOPE_OK;
+}
+
+int hope_env_curriculum_set_windows(hope_env_t* h, int n_buckets, const double* win_n, const double* win_s, const uint64_t* episodes,
+                                    const uint64_t* successes) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h || !win_n || !win_s || !episodes || !successes) return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: null argument");
+    hope_env::Curriculum& cu = h->cur;
+    if (!cu.on) return fail(HOPE_ESTATE, "hope_env_curriculum_set_windows: the curriculum is off (hope_env_curriculum_enable first)");
+    if (n_buckets != cu.nb) return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: " + std::to_string(n_buckets) + " buckets given, the handle has " + std::to_string(cu.nb));
+    for (int b = 0; b < n_buckets; b++)
+        if (!(win_n[b] >= 0.0) || !(win_s[b] >= 0.0) || win_s[b] > win_n[b] || successes[b] > episodes[b])
+            return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: bucket " + std::to_string(b) + " needs 0 <= s <= n");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
+    HIPCHK(hipDeviceSynchronize());
+    const size_t nb = (size_t)cu.nb;
+    HIPCHK(hipMemcpy(cu.dev.win_n, win_n, nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cu.dev.win_s, win_s, nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cu.dev.episodes, episodes, nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cu.dev.successes, successes, nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cu.dev.folded_e, episodes, nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cu.dev.folded_s, successes, nb * 8, hipMemcpyHostToDevice));
+    int rc = cur_build_lists(h, false, nullptr);
+    if (rc != HOPE_OK) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    return HOPE_OK;
+}
+
+int hope_env_curriculum_download_lists(hope_env_t* h, int32_t* list0, int32_t* list1, int32_t* positions) {
+    { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
+    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_download_lists: null handle");
+    const hope_env::Curriculum& cu = h->cur;
+    if (!cu.on || cu.wactive < 0) return fail(HOPE_ESTATE, "hope_env_curriculum_download_lists: the curriculum is off");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
+    HIPCHK(hipDeviceSynchronize());
+    int32_t* out[2] = {list0, list1};
+    for (int c = 0; c < 2; c++)
+        if (out[c] && h->pool_cls_n[c] > 0) HIPCHK(hipMemcpy(out[c], cu.wl[cu.wactive][c], (size_t)CW_LIST_LEN * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (positions) {
+        std::vector<int32_t> pf(2 * (CW_MAX_GROUPS + 1));
+        HIPCHK(hipMemcpy(pf.data(), cu.prefix[cu.wactive], pf.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int c = 0; c < 2; c++)
+            for (int g = 0; g < cu.nb; g++) positions[c * cu.nb + g] = pf[c * (CW_MAX_GROUPS + 1) + g + 1] - pf[c * (CW_MAX_GROUPS + 1) + g];
+    }
+    return HOPE_OK;
+}
+
+// the identity of what a draw can return: the pool's hash chain and, with the curriculum on, what the applied weighted lists are made
+// of (they are a pure function of the groups' entries and positions)
+static int effective_generation(hope_env_t* h, uint64_t* generation) {
+    *generation = h->pool_generation;
+    const hope_env::Curriculum& cu = h->cur;
+    if (!cu.on || cu.wactive < 0 || h->pactive < 0) return HOPE_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipStreamSynchronize(h->pool_stream));
+    std::vector<int32_t> pf(2 * (CW_MAX_GROUPS + 1));
+    HIPCHK(hipMemcpy(pf.data(), cu.prefix[cu.wactive], pf.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    uint64_t c = hash_bytes(0x637572726963ull, pf.data(), pf.size() * sizeof(int32_t));
+    c = hash_bytes(c, cu.cls, sizeof(cu.cls));
+    const hope_env::PoolSet& ps = h->pset[h->pactive];
+    if (ps.lab_kind == 2) c = hash_bytes(c, ps.lab_host.data(), ps.lab_host.size());
+    uint64_t g = fold64(h->pool_generation, c);
+    *generation = g ? g : 1;
+    return HOPE_OK;
+}
+
+int hope_curriculum_fold_host(double* n, double* s, double dn, double ds, double window) {
+    if (!n || !s || !(window > 0.0)) return fail(HOPE_EINVAL, "hope_curriculum_fold_host: bad argument");
+    cw_fold(n, s, dn, ds, window);
+    return HOPE_OK;
+}
+
+int hope_curriculum_lists_host(const hope_curriculum_params* params, int n_pool, const int32_t* n_obst, const uint8_t* bucket, int n_cases,
+                               int max_obstacles, const uint64_t* episodes, const double* win_n, const double* win_s, int32_t* list0,
+                               int32_t* list1, double* prob, double* pw, int32_t* positions) {
+    if (n_pool < 0 || n_cases < 0 || (n_pool > 0 && !n_obst) || !episodes || !win_n || !win_s || max_obstacles <= 0)
+        return fail(HOPE_EINVAL, "hope_curriculum_lists_host: bad argument");
+    if (4 + n_cases > CW_MAX_GROUPS) return fail(HOPE_EINVAL, "hope_curriculum_lists_host: more than 250 Dragon-Lake cases");
+    if (n_pool + n_cases <= 0) return fail(HOPE_EINVAL, "hope_curriculum_lists_host: nothing to draw from");
+    if (n_pool + n_cases > CW_LIST_LEN) return fail(HOPE_EINVAL, "hope_curriculum_lists_host: a draw list longer than HOPE_CURRICULUM_LIST_LEN entries");
+    const hope_curriculum_params P = params ? *params : CW_DEFAULTS;
+    const int G = 4 + n_cases;
+    const bool two = max_obstacles > SMALL_TILE;
+    CwClass cls[2] = {};
+    std::vector<int32_t> srt[2];
+    for (int k = 0; k < n_pool; k++)
+        if (bucket && bucket[k] > 2 && bucket[k] != CW_UNLABELLED) return fail(HOPE_EINVAL, "hope_curriculum_lists_host: bucket id out of range (0, 1, 2 or 255)");
+    for (int g = 0; g < 4; g++)
+        for (int k = 0; k < n_pool; k++) {
+            const int b = bucket && bucket[k] < 3 ? bucket[k] : 3;
+            if (b != g) continue;
+            const int c = two && n_obst[k] > SMALL_TILE ? 1 : 0;
+            srt[c].push_back(k); cls[c].cnt[g]++;
+        }
+    cls[two ? 1 : 0].n_cases = n_cases;
+    std::vector<double> pr(G, 0.0), w(G), r(G);
+    std::vector<int32_t> f(G), pos(G), prefix(G + 1);
+    double pw4[4], q[4];
+    cw_type_probs(win_n, win_s, &P, episodes[0] + episodes[1] + episodes[2] + episodes[3], pw4, q);
+    for (int t = 0; t < 4; t++) pr[t] = q[t];
+    cw_case_fail_phase(win_n, win_s, n_cases, &P, w.data(), 0, 1);
+    cw_case_prob_phase(n_cases, &P, episodes[3], w.data(), pr.data(), 0, 1);
+    if (prob) memcpy(prob, pr.data(), (size_t)G * 8);
+    if (pw) memcpy(pw, pw4, 32);
+    int32_t* out[2] = {list0, list1};
+    const CwWork k = {w.data(), r.data(), f.data(), pos.data(), prefix.data()};
+    for (int c = 0; c < 2; c++) {
+        if (cw_n_base(cls[c]) <= 0) { if (positions) for (int g = 0; g < G; g++) positions[c * G + g] = 0; continue; }
+        cw_weight_phase(cls[c], G, pr.data(), k, 0, 1);
+        cw_remainder_phase(G, k, 0, 1);
+        cw_prefix_phase(G, k);
+        if (positions) for (int g = 0; g < G; g++) positions[c * G + g] = pos[g];
+        if (out[c]) for (int p = 0; p < CW_LIST_LEN; p++) out[c][p] = cw_entry(cls[c], G, prefix.data(), srt[c].data(), p);
+    }
     return HOPE_OK;
 }
 

@@ -135,7 +135,7 @@ class TransitionRing:
 
 class HopeRollout:
     def __init__(self, env, agent, horizon, use_mask=True, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None,
-                 defer_rs=True):
+                 defer_rs=True, curriculum=None):
         """defer_rs: step the env with two completion points (HOPE_DEFER_RS): the next policy forward is enqueued as soon as the
         observation is written, the planner reads rs_word / rs_lengths (after ParkingBatch.wait_rs) just before its override --
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
@@ -143,7 +143,18 @@ class HopeRollout:
         (ParkingBatch.set_pool / set_dlp_cases), as the reference's loop does with `env.reset(...)`; otherwise on the same map.
         pool_refresher: a `scene_gen.PoolRefresher` (host generator + upload) or `scene_gen.DevicePoolRefresher` (lots drawn on the
         device); the trainers poll it after every update, so the pool of generated lots is
-        replaced by new ones in the background (asynchronous upload, no synchronisation with the step loop)."""
+        replaced by new ones in the background (asynchronous upload, no synchronisation with the step loop).
+        curriculum: None, or dict(update_every=K, **rule parameters) -- the reference's SceneChoose / DlpCaseChoose
+        (train_HOPE_sac.py:23-97) on the device: the env tallies every finished episode's outcome per scene type / Dragon-Lake case
+        after each step and rebuilds its weighted draw lists every K steps (hope_amd.curriculum.CurriculumDriver); needs
+        fresh_scenes (ValueError without).  Measured cost at 65 536 scenes: ~8 % per step.  None: no call at all."""
+        self.curriculum = None
+        if curriculum is not None:
+            if not fresh_scenes:
+                raise ValueError('curriculum needs fresh_scenes=True: it reweights the draws of new maps, and without them nothing '
+                                 'reads its lists')
+            from .curriculum import CurriculumDriver
+            self.curriculum = CurriculumDriver(env, **dict(curriculum))
         self.env, self.agent, self.use_mask, self.fresh = env, agent, use_mask, fresh_scenes
         self.refresher = pool_refresher
         self.seed = seed
@@ -207,6 +218,8 @@ class HopeRollout:
             env.step(action.to(env.action_dtype).contiguous(), auto_reset=True, fresh=True, **kw)
         else:
             env.step(action.to(env.action_dtype).contiguous(), auto_reset=True, **kw)
+        if self.curriculum is not None:               # update_success_record (:215-225), and every K steps the new draw weights
+            self.curriculum.after_step()
         self.ring.write_after(env.reward, env.done)
         agent.observe(self._raw_obs())                              # push_memory: state_norm(next_obs, update=True)
         done = env.done.bool()
@@ -223,17 +236,25 @@ class HopeRollout:
 
     def stats(self):
         ep = int(self.episodes.item())
-        return {'steps': self.steps, 'episodes': ep, 'success_rate': float(self.successes.item()) / max(ep, 1),
-                'mean_reward': float(self.reward_sum.item()) / max(self.steps * self.env.n, 1)}
+        out = {'steps': self.steps, 'episodes': ep, 'success_rate': float(self.successes.item()) / max(ep, 1),
+               'mean_reward': float(self.reward_sum.item()) / max(self.steps * self.env.n, 1)}
+        if self.curriculum is not None:               # success_rate_<type>, as the reference logs them (:233-235)
+            out.update(self.curriculum.stats())
+        return out
 
 
 class PPOTrainer(HopeRollout):
     """train_HOPE_ppo.py:177-213: act -> step -> push; when the buffer is full (`horizon` steps of all scenes,
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
-    def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True):
+    def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
+                 curriculum=None):
+        """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update"""
+        self._curriculum_per_update = curriculum is not None and 'update_every' not in curriculum
+        if self._curriculum_per_update:
+            curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum)
         self.updates = 0
 
     def step(self):
@@ -243,6 +264,8 @@ class PPOTrainer(HopeRollout):
             losses = self.agent.update(obs, action, reward, done, log_prob, self.last_obs(), generator=self.gen)
             self.ring.clear()
             self.updates += 1
+            if self._curriculum_per_update:
+                self.env.curriculum_update()
             if self.refresher is not None:
                 self.refresher.poll()
             return losses
@@ -254,9 +277,9 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True):
+                 pool_refresher=None, defer_rs=True, curriculum=None):
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

@@ -328,7 +328,7 @@ def generate_scene(level, rng=None, case_id=None):
 
 class SceneSource:
     """uniform mix over difficulty levels, as the reference's SceneChoose does before its curriculum kicks
-    in (src/train/train_HOPE_sac.py:23-29)."""
+    in (src/train/train_HOPE_sac.py:23-29); the curriculum itself reweights the device-side draws (hope_amd/curriculum.py)."""
 
     def __init__(self, levels=('Normal', 'Complex', 'Extrem', 'dlp'), seed=42, dlp_path=DEFAULT_DLP):
         self.levels = tuple(levels)

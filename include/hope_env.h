@@ -243,7 +243,9 @@ int hope_env_commit_pool(hope_env_t *h, int n_pool, void *stream);
  * upload has COMPLETED -- no step ever waits for an upload.  (hope_env_commit_pool swaps at once, so the next step's launch waits on
  * its stream for the 67 MB of an 8 192-lot pool: 2-3 ms, five 65 536-scene steps.)  Which step that is depends on timing, like the
  * moment a background refresher's fill finishes; a later commit of either kind, hope_env_set_pool and hope_env_pool_generation first
- * wait for and apply a swap still pending.  What a rollout's background refresher should use (hope_amd.scene_gen.PoolRefresher). */
+ * wait for and apply a swap still pending.  What a rollout's background refresher should use (hope_amd.scene_gen.PoolRefresher).
+ * With the curriculum on (below) the step that applies the swap is not wait-free: it enqueues the incoming set's labels and weighted
+ * lists on the pool stream and waits for them in stream order (~0.15 ms for 252 buckets), so that no draw falls back to uniform. */
 int hope_env_commit_pool_relaxed(hope_env_t *h, int n_pool);
 /* 1 when hope_env_pool_staging would return without waiting (the previous commit's copies have left the pinned arrays), 0 when not
  * yet, < 0 on error: a background refresher polls this instead of blocking the thread that drives the step loop */
@@ -253,7 +255,9 @@ int hope_env_pool_staging_ready(hope_env_t *h);
  * ABI 8: the value is a HASH CHAIN over the contents of every upload since hope_env_create (pool entries' start / dest / box /
  * obstacle counts and a strided sample of their vertices; the Dragon-Lake case table), not a per-handle counter -- a snapshot taken
  * in one process is refused by another process whose pool holds other maps even if both uploaded "one pool".  0 is never
- * returned for a handle with a pool (0 = "no pool yet" / "skip the check" in hope_env_restore_maps). */
+ * returned for a handle with a pool (0 = "no pool yet" / "skip the check" in hope_env_restore_maps).
+ * With the curriculum on the value also folds in what the applied weighted lists are made of (groups and positions): the call then
+ * synchronises with the handle's pool stream and downloads ~2 KB. */
 int hope_env_pool_generation(hope_env_t *h, uint64_t *generation);
 /* seed of HOPE_AUTO_REDRAW's draws (default 0) */
 int hope_env_set_redraw_seed(hope_env_t *h, uint64_t seed);
@@ -428,6 +432,94 @@ int hope_scenegen_log_det(int n, const double *x, double *y);
  * count, counts that do not sum to n_pool, a handle with max_obstacles < 18; HOPE_ESTATE: a hope_env_pool_staging fill that has
  * not been committed. */
 int hope_env_generate_pool(hope_env_t *h, int n_pool, const int32_t *n_per_level /*[3]*/, uint64_t seed, int64_t first_index, int relaxed);
+
+/* ---- curriculum for new-map draws (additive to ABI 8) -----------------------------------------------------------------
+ * The reference's training loops never draw a uniform scene mix: SceneChoose sends half of the choices to the scene type whose
+ * recent success rate is furthest below its target and balances the counts with the other half, DlpCaseChoose prefers the
+ * Dragon-Lake cases that failed recently, and every finished episode is fed back (src/train/train_HOPE_sac.py:23-97, :215-225).
+ * Here the outcome of an episode and the map it ran on exist on the device only, so the curriculum lives there too: a tally of
+ * episode outcomes per BUCKET and weighted draw lists rebuilt from it.  Off by default; with it off nothing differs.
+ *
+ * Buckets: 0 / 1 / 2 generated lots of level Normal / Complex / Extrem (hope_env_generate_pool labels its lots itself; a
+ * host-filled pool is labelled with hope_env_set_pool_buckets), 3 "dlp" as a scene type (every Dragon-Lake episode), 4 + c
+ * Dragon-Lake case c.  n_buckets = 4 + n_cases <= 254.  Unlabelled pool entries and maps uploaded with hope_env_set_scenes are
+ * counted in one extra counter and keep the share of the draws they have without a curriculum.
+ *
+ * The draw stays `list[key % n]` inside the step kernels; the list becomes a WEIGHTED list of HOPE_CURRICULUM_LIST_LEN positions
+ * in which a bucket owns p_b * HOPE_CURRICULUM_LIST_LEN positions (largest remainder, at least one per bucket with entries), so a
+ * draw follows p_b to within 1 / HOPE_CURRICULUM_LIST_LEN.  The rule (hope_amd/csrc/hope_curriculum_core.h):
+ *   window     per bucket (n, s): an update with (dn, ds) new episodes / successes does n += dn, s += ds and, if n > W,
+ *              s *= W / n, n = W (W = type_window for buckets 0 - 3, case_window for the cases);
+ *   types      fail_t = clip(target_t - s_t / n_t, type_fail_min, 1), pw = fail / sum(fail) (_choose_case_worst_perform);
+ *              q_t = max(worst_share * pw_t, h), h such that sum(q) = 1: the long-run type frequencies of SceneChoose.choose_case;
+ *              uniform before type_horizon episodes.  The small-tile class draws level l with q_l / (q_0 + q_1 + q_2) over the
+ *              levels its pool holds.  LIMIT: which scene slots are Dragon-Lake slots is fixed (tile class 1), so q_3 cannot move
+ *              scenes between the classes: it is reported and otherwise unused;
+ *   cases      rate_c = 0 if n_c <= 1 else s_c / n_c, fail_c = clip(1 - rate_c, case_fail_min, 1),
+ *              p_c = case_uniform / n_cases + (1 - case_uniform) * fail_c / sum(fail); uniform before case_horizon Dragon-Lake
+ *              episodes.  Unlabelled lots in the same list keep their share n_lots / (n_lots + n_cases).
+ * Misuse returns HOPE_EINVAL / HOPE_ESTATE with a message: tally before enable, labels of the wrong length, a bucket id out of
+ * range, hope_env_set_dlp_cases while the curriculum is on. */
+#define HOPE_CURRICULUM_LIST_LEN (1 << 20)
+typedef struct hope_curriculum_params {
+    double target[4];        /* target success rate of Normal / Complex / Extrem / dlp: 0.95 0.95 0.9 0.99 */
+    double type_window;      /* 250 */
+    double case_window;      /* 10 */
+    double type_fail_min;    /* 0.01 */
+    double case_fail_min;    /* 0.005 */
+    double worst_share;      /* 0.5: share of the choices that go to the worst-performing type */
+    double case_uniform;     /* 0.2: share of the case choices that stay uniform */
+    int64_t type_horizon;    /* 200 */
+    int64_t case_horizon;    /* 500 */
+} hope_curriculum_params;
+/* Switches the curriculum on (params NULL: the reference's constants above) with empty counters and windows, builds the weighted
+ * lists of the resident pool (uniform within each kind at this point) and notes the bucket of the map every scene holds now.
+ * HOPE_ESTATE without a pool or Dragon-Lake cases; HOPE_EINVAL for more than 250 cases or non-positive windows.  Host-synchronous. */
+int hope_env_curriculum_enable(hope_env_t *h, const hope_curriculum_params *params);
+/* back to the uniform base lists; counters and windows are dropped.  Host-synchronous. */
+int hope_env_curriculum_disable(hope_env_t *h);
+/* labels the RESIDENT pool set: bucket[k] in {0, 1, 2} = level of pool entry k, 255 = unlabelled; n_pool must be the resident
+ * pool's size.  Host array, host-synchronous; the labels last until that set is replaced. */
+int hope_env_set_pool_buckets(hope_env_t *h, int n_pool, const uint8_t *bucket);
+/* k_curriculum_tally, asynchronous on `stream` (the stream of the steps), right after a step: for every scene with done[i] != 0 the
+ * bucket of the map the FINISHED episode ran on gets one episode and, if status[i] == HOPE_STATUS_ARRIVED, one success (a
+ * Dragon-Lake episode counts in bucket 3 and in 4 + c); then the bucket of the map the scene holds now (after the fused redraw) is
+ * noted for the next time, if the scene drew a new map (a scene that restarts on the same map keeps its bucket; hope_env_redraw notes
+ * the buckets of the maps it draws; a map uploaded with hope_env_set_scenes is unlabelled).  status / done: the DEVICE buffers of that
+ * step's hope_step_out.  Every scene with done[i] != 0 is counted: call it once per step. */
+int hope_env_curriculum_tally(hope_env_t *h, const int32_t *status, const uint8_t *done, void *stream);
+/* k_curriculum_weights + k_curriculum_fill: folds the counters since the last update into the windows, recomputes the
+ * probabilities and fills the weighted lists the kernels are NOT reading, on the handle's pool stream, ordered after everything
+ * enqueued on `stream` so far; the swap is applied at the next step enqueued, which waits in stream order (as hope_env_commit_pool).
+ * No host synchronisation.  A pool swap of any kind while the curriculum is on rebuilds the lists for the incoming set with the
+ * current windows before that set is drawn from.  Counters that a tally enqueued behind the update adds while the fold reads them
+ * are folded by the next update (never more successes than episodes in one fold). */
+int hope_env_curriculum_update(hope_env_t *h, void *stream);
+/* Download (host-synchronous; any pointer may be NULL): *n_buckets = 4 + n_cases; episodes / successes [n_buckets] cumulative since
+ * enable; win_n / win_s [n_buckets] the windows; prob [n_buckets]: q_0 .. q_3, then p_c per case; pw [4]; misc [4]: updates
+ * applied, episodes and successes on unlabelled maps, 1 when the curriculum is on. */
+int hope_env_curriculum_state(hope_env_t *h, int32_t *n_buckets, uint64_t *episodes, uint64_t *successes, double *win_n, double *win_s,
+                              double *prob, double *pw, uint64_t *misc);
+/* Test hook: sets the windows (and the cumulative episode counters the two horizons look at) by hand and rebuilds the lists from them,
+ * as an update without counters would.  It carries the curriculum's own state over to another handle, NOT the per-scene part: the
+ * bucket noted for the map each scene holds is whatever the handle has (hope_env_curriculum_enable notes it from the scenes' current
+ * pool indices).  Host arrays [n_buckets]; host-synchronous. */
+int hope_env_curriculum_set_windows(hope_env_t *h, int n_buckets, const double *win_n, const double *win_s, const uint64_t *episodes,
+                                    const uint64_t *successes);
+/* the two weighted lists as the next step will read them (host arrays [HOPE_CURRICULUM_LIST_LEN] int32 each, either may be NULL; a
+ * class without entries is left untouched) and the positions every group owns in them (positions [2][n_buckets], may be NULL: per
+ * class, groups 0 - 2 the levels, 3 the unlabelled lots, 4 + c case c).  Host-synchronous. */
+int hope_env_curriculum_download_lists(hope_env_t *h, int32_t *list0, int32_t *list1, int32_t *positions);
+/* Test hooks, pure host code, no device needed.  hope_curriculum_lists_host: the lists hope_env_curriculum_update builds for a pool
+ * of n_pool entries with obstacle counts n_obst and labels bucket (NULL: all unlabelled), n_cases Dragon-Lake cases and a handle
+ * with max_obstacles, from the windows win_n / win_s and the cumulative episode counters episodes (all [4 + n_cases]) -- the same
+ * source compiled for the host (hope_amd/csrc/hope_curriculum_core.h), bit-equal to the device's.  Outputs (any may be NULL):
+ * list0 / list1 [HOPE_CURRICULUM_LIST_LEN], prob [4 + n_cases], pw [4], positions [2][4 + n_cases].
+ * hope_curriculum_fold_host: the window rule for one bucket. */
+int hope_curriculum_lists_host(const hope_curriculum_params *params, int n_pool, const int32_t *n_obst, const uint8_t *bucket, int n_cases,
+                               int max_obstacles, const uint64_t *episodes, const double *win_n, const double *win_s, int32_t *list0,
+                               int32_t *list1, double *prob, double *pw, int32_t *positions);
+int hope_curriculum_fold_host(double *n, double *s, double dn, double ds, double window);
 
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
