@@ -28,6 +28,9 @@ def main():
     ap.add_argument('--curriculum', action='store_true',
                     help='with --device-pool: pick the new maps with the device-side curriculum (SceneChoose / DlpCaseChoose of '
                          'train_HOPE_sac.py: outcomes tallied per scene type, draw weights rebuilt after every PPO update)')
+    ap.add_argument('--eval-levels', action='store_true',
+                    help='one more batched evaluation over Dragon-Lake lots DRAWN ON THE DEVICE (jitter, cull, flips per slot), labelled by '
+                         'the HIP kernel k_map_level: the per-level block of result.txt for maps that exist on the device only')
     args = ap.parse_args()
     rank, world, local = D.init_from_env()
     dev = f'cuda:{local}'
@@ -82,6 +85,19 @@ def main():
         for k, v in E.summarize(rec, levels).items():
             print(f'  eval {k:8s}: {v["episodes"]} episodes, success {v["success_rate"]:.3f}, steps {v["step_num_mean"]:.1f} +- {v["step_num_std"]:.1f}, '
                   f'path {v["path_length_mean"]:.2f} m')
+    if args.eval_levels:
+        n = min(args.scenes, 4096)
+        env.close()
+        env = ParkingBatch(n, 128, device=dev)
+        env.set_scenes(np.arange(n), [uniq[i % len(uniq)] for i in range(n)])
+        env.set_draw_class(np.arange(n), 1)                                   # every slot draws Dragon-Lake lots
+        env.set_dlp_cases()
+        env.redraw(torch.ones(n, dtype=torch.uint8, device=dev), seed=1 + rank)
+        rec = E.BatchedEvaluator(env, ag, seed=rank).run(levels=True)         # [n_total, 5]: the fifth column is the level
+        if rank == 0:
+            for k, v in E.summarize(rec).items():
+                print(f'  eval-levels {k:8s}: {v["episodes"]} episodes, success {v["success_rate"]:.3f}, steps {v["step_num_mean"]:.1f}, '
+                      f'path {v["path_length_mean"]:.2f} m')
 
 
 if __name__ == '__main__':

@@ -386,6 +386,26 @@ class ParkingBatch:
         L.check(self.lib.hope_env_download_n_obst(self.h, out.ctypes.data), 'hope_env_download_n_obst')
         return out
 
+    def map_levels(self, active=None, out=None, detail=False):
+        """`map.map_level` of the maps the scenes hold NOW (pool draws, Dragon-Lake draws and uploads alike), labelled on the device
+        by k_map_level (asynchronous on the current stream) -> torch.uint8 [N], 0 Normal / 1 Complex / 2 Extrem
+        (hope_amd.map_level.LEVEL_NAMES) [, int32 [N, 8] detail].  active: u8 [N]; scenes with active[i] == 0 keep out[i] (pass the
+        last step's `done` and the previous labels as `out` to relabel only the scenes that drew a new map)."""
+        if out is None:
+            out = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.shape == (self.n,) and out.device == self.device and out.is_contiguous()
+        ap = None
+        if active is not None:
+            assert active.dtype == torch.uint8 and active.shape == (self.n,) and active.device == self.device and active.is_contiguous()
+            ap = C.c_void_p(active.data_ptr())
+        det = None
+        if detail is not False and detail is not None:
+            det = detail if torch.is_tensor(detail) else torch.zeros((self.n, 8), dtype=torch.int32, device=self.device)
+            assert det.dtype == torch.int32 and det.shape == (self.n, 8) and det.device == self.device and det.is_contiguous()
+        L.check(self.lib.hope_env_map_level(self.h, ap, C.c_void_p(out.data_ptr()), C.c_void_p(det.data_ptr()) if det is not None else None,
+                                            self._stream()), 'hope_env_map_level')
+        return (out, det) if det is not None else out
+
     def restart(self, mask):
         """episodes flagged in mask (u8 [N]) go back to their start pose, t = 0 (same map)."""
         assert mask.dtype == torch.uint8 and mask.shape == (self.n,) and mask.device == self.device

@@ -19,6 +19,7 @@
 #include "hope_motion_pair.h"
 #include "hope_scenegen_kernel.h"
 #include "hope_curriculum_kernel.h"
+#include "hope_maplevel_kernel.h"
 
 using namespace hope;
 
@@ -1769,6 +1770,36 @@ int hope_scenegen_generate_device(int device_id, int level, int bay_mode, int n,
     job.first_index = first_index; job.bay_mode = bay_mode;
     hipLaunchKernelGGL(k_scenegen, dim3((n + SG_BLOCK - 1) / SG_BLOCK), dim3(SG_BLOCK), 0, (hipStream_t)stream, job, max_obstacles, start, dest,
                        bbox, verts, n_obst, case_id, (double*)nullptr);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+// ---- map difficulty labels on the device (k_map_level, hope_maplevel_kernel.h) --------------------------------------------------
+int hope_map_level_device(int device_id, int n, int max_obstacles, const double* start, const double* dest, const double* verts,
+                          const int32_t* n_obst, uint8_t* level, int32_t* detail, void* stream) {
+    if (n <= 0) return fail(HOPE_EINVAL, "hope_map_level_device: n <= 0");
+    if (max_obstacles <= 0 || max_obstacles > HOPE_MAX_OBSTACLES) return fail(HOPE_EINVAL, "hope_map_level_device: max_obstacles out of range (1 .. 255)");
+    if (!level) return fail(HOPE_EINVAL, "hope_map_level_device: null level buffer");
+    if (!start || !dest || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_map_level_device: null input buffer");
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return fail(HOPE_ENODEV, "hope_map_level_device: hipSetDevice failed");
+    hipLaunchKernelGGL(k_map_level, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, n, max_obstacles, start, 3, dest, 3, verts, n_obst,
+                       (const uint8_t*)nullptr, level, detail);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_map_level(hope_env_t* h, const uint8_t* active, uint8_t* level, int32_t* detail, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_map_level: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_map_level: not a live handle (destroyed?)");
+    if (!level) return fail(HOPE_EINVAL, "hope_env_map_level: null level buffer");
+    if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_map_level: hope_env_set_scenes has not been called");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    { int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }   // ordered like every entry that reads the handle's state
+    hipLaunchKernelGGL(k_map_level, dim3(h->n), dim3(WAVE), 0, (hipStream_t)stream, h->n, h->max_obst, (const double*)(h->scene_c + SC_START),
+                       (int)SC_WORDS, (const double*)(h->scene_c + SC_DEST), (int)SC_WORDS, (const double*)h->verts, (const int32_t*)h->n_obst, active,
+                       level, detail);
     HIPCHK(hipGetLastError());
     return HOPE_OK;
 }

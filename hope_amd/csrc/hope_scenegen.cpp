@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>                  // (hipcc compiles this file as HIP: the shared core's functions are __host__ __device__)
 #endif
 #include "hope_scenegen_core.h"
+#include "hope_maplevel_core.h"
 
 namespace {
 
@@ -451,6 +452,33 @@ int hope_scenegen_generate_det(int level, int bay_mode, int n, uint64_t seed, in
                 memcpy(verts + (size_t)i * max_obstacles * 8, ring_words, (size_t)nr * 8 * sizeof(double));
                 n_obst[i] = (int32_t)nr;
                 if (case_id) case_id[i] = cid;
+            }
+        }
+    };
+    if (nt == 1) work();
+    else pool().run(nt, work);
+    return HOPE_OK;
+}
+
+// get_map_level for n scenes on the host (hope_maplevel_core.h run serially per scene; no device involved): level [n] (0 Normal,
+// 1 Complex, 2 Extrem) and, if detail != NULL, the record [n][8] of include/hope_env.h.  Scene i depends only on its own inputs: the
+// result does not depend on n_threads (<= 0: as hope_scenegen_generate).
+int hope_map_level_host(int n, int max_obstacles, const double* start, const double* dest, const double* verts, const int32_t* n_obst,
+                        uint8_t* level, int32_t* detail, int n_threads) {
+    if (n <= 0 || max_obstacles <= 0 || max_obstacles > HOPE_MAX_OBSTACLES || !start || !dest || !verts || !n_obst || !level) return HOPE_EINVAL;
+    int nt = n_threads > 0 ? n_threads : std::min(default_threads(), getenv("HOPE_HOST_THREADS") ? (1 << 20) : 64);
+    nt = std::max(1, std::min(nt, n / 64));
+    const int chunk = std::max(8, std::min(32, n / std::max(1, 8 * nt)));
+    nt = std::max(1, std::min(nt, (n + chunk - 1) / chunk));
+    std::atomic<int> next{0};
+    const std::function<void()> work = [&]() {
+        for (;;) {
+            const int a = next.fetch_add(chunk);
+            if (a >= n) break;
+            for (int i = a; i < std::min(n, a + chunk); i++) {
+                const int no = std::max(0, std::min(max_obstacles, (int)n_obst[i]));
+                level[i] = (uint8_t)ml_scene_host(start + 3 * (size_t)i, dest + 3 * (size_t)i, verts + (size_t)i * max_obstacles * 8, no,
+                                                  detail ? detail + (size_t)i * ML_DETAIL_WORDS : nullptr);
             }
         }
     };

@@ -141,6 +141,27 @@ def gather_eval_stats(status, steps, reward, path_len, group=None):
     return torch.cat([o[:int(s.item())] for o, s in zip(out, sizes)], dim=0)
 
 
+def gather_eval_levels(records, levels, group=None):
+    """gather_eval_stats' records with the map level of every episode as a fifth column: `records` float32 [n_total, 4] as
+    gather_eval_stats returned them (already gathered), `levels` this rank's labels [n_local] (any integer dtype), gathered in
+    the same rank order -> float32 [n_total, 5]"""
+    lv = levels.to(torch.float32).reshape(-1, 1).contiguous()
+    if not _single(group):
+        world = dist.get_world_size(group)
+        n = torch.tensor([lv.shape[0]], device=lv.device, dtype=torch.int64)
+        sizes = [torch.zeros_like(n) for _ in range(world)]
+        dist.all_gather(sizes, n, group=group)
+        nmax = int(max(int(s.item()) for s in sizes))
+        pad = torch.zeros((nmax, 1), device=lv.device, dtype=lv.dtype)
+        pad[:lv.shape[0]] = lv
+        out = [torch.zeros_like(pad) for _ in range(world)]
+        dist.all_gather(out, pad, group=group)
+        lv = torch.cat([o[:int(s.item())] for o, s in zip(out, sizes)], dim=0)
+    if lv.shape[0] != records.shape[0]:
+        raise ValueError(f'gather_eval_levels: {lv.shape[0]} labels for {records.shape[0]} records')
+    return torch.cat([records, lv.to(records.device)], dim=1)
+
+
 def success_rate(records):
     """fraction of ARRIVED (status 2) episodes, as eval_utils.py:75-77 reports."""
     return float((records[:, 0] == 2).float().mean().item()) if len(records) else 0.0

@@ -8,7 +8,9 @@ the PHYSICAL action box that the wrapper then clips to [-1, 1]) and hands found 
 `summarize` produces the numbers result.txt holds (:131-149): success rate, steps of the successful episodes, and per map level
 (`env.map.map_level`, :69) success rate, steps and the path length of the episodes shorter than 200 steps; OUTBOUND episodes
 count 200 steps in the per-case step record (:73-76).  `BatchedEvaluator.run` returns one record per episode; with
-torch.distributed initialised the records of all ranks are gathered (hope_amd.dist.gather_eval_stats: one all-gather)."""
+torch.distributed initialised the records of all ranks are gathered (hope_amd.dist.gather_eval_stats: one all-gather).
+`run(levels=True)` adds the map level of every episode's lot, labelled on the device (`ParkingBatch.map_levels`, k_map_level), so
+that the per-level blocks exist for device-drawn Dragon-Lake lots too."""
 import numpy as np
 import torch
 
@@ -40,12 +42,17 @@ class BatchedEvaluator:
         return o
 
     @torch.no_grad()
-    def run(self, max_steps=TOLERANT_TIME + 2, gather=True):
+    def run(self, max_steps=TOLERANT_TIME + 2, gather=True, levels=False):
         """one episode per scene slot from the slots' current maps (the caller has uploaded / drawn them and not stepped yet).
-        -> float32 [n_total, 4]: status, steps, reward, path length."""
+        -> float32 [n_total, 4]: status, steps, reward, path length.
+        levels=True: the slots' maps are labelled right after the first observation (`env.map_levels()`: get_map_level on the
+        device, eval_utils.py:69) -> [n_total, 5] with the level (0 Normal, 1 Complex, 2 Extrem) as the fifth column, gathered
+        over the ranks like the rest; `self.levels` keeps this rank's labels (uint8 [n])."""
         env, agent = self.env, self.agent
         n, dev = env.n, env.device
         env.reset_obs()                                               # env.reset(i + 1) -> first observation (:32)
+        if levels:
+            self.levels = env.map_levels().clone()                    # env.map.map_level (:69), before the first step
         if self.planner is not None:
             self.planner.reset()                                      # agent.reset() (:33)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
@@ -83,14 +90,19 @@ class BatchedEvaluator:
             alive = alive & ~done
         rec = torch.stack([status.float(), steps.float(), total.float(), path.float()], dim=1)
         if gather:
-            return D.gather_eval_stats(status, steps, total.float(), path.float())
-        return rec
+            rec = D.gather_eval_stats(status, steps, total.float(), path.float())
+            return D.gather_eval_levels(rec, self.levels) if levels else rec
+        return torch.cat([rec, self.levels.to(torch.float32).reshape(-1, 1)], dim=1) if levels else rec
 
 
 def summarize(records, levels=None):
     """records [n, 4] (status, steps, reward, path length) [+ levels: sequence of n map-level labels] -> the numbers of
-    result.txt (eval_utils.py:131-149)"""
+    result.txt (eval_utils.py:131-149).  Records with a fifth column (`BatchedEvaluator.run(levels=True)`) carry their labels:
+    without `levels` the blocks are named after it ('Normal' / 'Complex' / 'Extrem')."""
     r = records.detach().cpu().numpy() if torch.is_tensor(records) else np.asarray(records)
+    if levels is None and r.ndim == 2 and r.shape[1] >= 5:
+        from .map_level import LEVEL_NAMES
+        levels = [LEVEL_NAMES[int(v)] for v in r[:, 4]]
     status, steps, reward, plen = r[:, 0].astype(int), r[:, 1], r[:, 2], r[:, 3]
     succ = status == 2
 

@@ -10,7 +10,13 @@ reference's own source by tests/test_map_level.py):
   LinearRing.equals(LinearRing)     -> identity of the obstacle (the reference compares members of one list)
   MultiPoint.minimum_rotated_rectangle -> min_area_rectangle   (shapely 1.8: smallest-AREA rectangle over the hull edges)
   Polygon.intersects(LinearRing)    -> polygon_meets_ring      (boundary crossing, or the ring inside the polygon)
+
+Batches: hope_amd/csrc/hope_maplevel_core.h restates this file in exact-arithmetic C++, compiled for the host
+(`get_map_levels_host`) and as the kernel k_map_level (`get_map_levels_device`, `ParkingBatch.map_levels`); the two are bit-equal
+to each other and differ from this file only where it calls the platform's cos / sin / hypot.  `get_map_level_detail` is the
+pure-Python twin of the detail record those entries return.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -218,3 +224,120 @@ def get_map_level(start, dest, obstacles):
     if (left is None or right is None) and (front is None or back is None):
         return LEVEL_NORMAL
     return LEVEL_COMPLEX
+
+
+# ---- batches: the native core (include/hope_env.h "map difficulty label") -----------------------------------------------------
+LEVEL_NAMES = (LEVEL_NORMAL, LEVEL_COMPLEX, LEVEL_EXTREM)
+# detail word 4: which `return` fired (ML_B_* of hope_maplevel_core.h)
+B_FEW, B_EXTREM_FAR_LEN, B_EXTREM_FAR_WID, B_EXTREM_LEN, B_BAY_EARLY, B_BAY_FREE, B_BAY_BLOCKED, B_PAR_EARLY, B_PAR_FREE, \
+    B_PAR_BLOCKED, B_OPEN, B_OTHER = range(1, 13)
+DETAIL_WORDS = 8
+
+
+def get_map_level_detail(start, dest, obstacles):
+    """`get_map_level` with its reasons -> (label, [left, right, front, back (index or -1), branch, far, count, 0]): the four
+    surrounding obstacles, which return fired (B_*), whether the start is further than MAX_DRIVE_DISTANCE away, and how many
+    obstacles meet the free rectangle (all of them: `get_map_level` itself stops at the first)."""
+    rings = [[(float(x), float(y)) for x, y in np.asarray(r, dtype=np.float64)] for r in obstacles]
+    if len(rings) <= 1:
+        return LEVEL_NORMAL, [-1, -1, -1, -1, B_FEW, 0, 0, 0]
+    left, right, front, back = _surrounding(dest, rings)
+    gap = math.hypot(start[0] - dest[0], start[1] - dest[1])
+    far = gap > MAX_DRIVE_DISTANCE
+    det = [-1 if v is None else v for v in (left, right, front, back)] + [0, int(far), 0, 0]
+
+    def ret(label, branch, count=0):
+        det[4], det[6] = branch, count
+        return label, det
+    lr, fb = left is not None and right is not None, front is not None and back is not None
+    if gap > 30.0:
+        if fb and not _has_enough_space(dest, rings, length=MIN_LOT_LEN_NORMAL):
+            return ret(LEVEL_EXTREM, B_EXTREM_FAR_LEN)
+        if lr and not _has_enough_space(dest, rings, width=MIN_LOT_WID_NORMAL):
+            return ret(LEVEL_EXTREM, B_EXTREM_FAR_WID)
+    if fb and not _has_enough_space(dest, rings, length=EXTREM_PARK_LOT_LENGTH):
+        return ret(LEVEL_EXTREM, B_EXTREM_LEN)
+    rb, rf, lf, lb = _create_box(dest)
+    if lr and front is None:
+        if far or not _has_enough_space(dest, rings, width=MIN_LOT_WID_NORMAL):
+            return ret(LEVEL_COMPLEX, B_BAY_EARLY)
+        h = dest[2]
+        pts = [_translate(lf, h, 0.2), _translate(rf, h, 0.2), _translate(lf, h, BAY_WALL_NORMAL - 0.5),
+               _translate(rf, h, BAY_WALL_NORMAL - 0.5), (start[0], start[1])]
+        free = min_area_rectangle(pts)
+        cnt = sum(polygon_meets_ring(free, r) for i, r in enumerate(rings) if i not in (left, right))
+        return ret(LEVEL_NORMAL, B_BAY_FREE) if cnt == 0 else ret(LEVEL_COMPLEX, B_BAY_BLOCKED, cnt)
+    if fb:
+        if far or not _has_enough_space(dest, rings, length=MIN_LOT_LEN_NORMAL):
+            return ret(LEVEL_COMPLEX, B_PAR_EARLY)
+        out = dest[2] + math.pi / 2
+        if math.cos(out) * (start[0] - dest[0]) + math.sin(out) * (start[1] - dest[1]) < 0:
+            out += math.pi
+            kf, kb = rf, rb
+        else:
+            kf, kb = lf, lb
+        pts = [_translate(kf, out, 0.2), _translate(kb, out, 0.2), _translate(kf, out, PARA_WALL_NORMAL - 0.5),
+               _translate(kb, out, PARA_WALL_NORMAL - 0.5)] + _create_box(start) + [(start[0], start[1])]
+        free = min_area_rectangle(pts)
+        cnt = sum(polygon_meets_ring(free, r) for i, r in enumerate(rings) if i not in (back, front))
+        return ret(LEVEL_NORMAL, B_PAR_FREE) if cnt == 0 else ret(LEVEL_COMPLEX, B_PAR_BLOCKED, cnt)
+    if not lr and not fb:
+        return ret(LEVEL_NORMAL, B_OPEN)
+    return ret(LEVEL_COMPLEX, B_OTHER)
+
+
+def pack_rings(scenes, max_obstacles):
+    """[(start, dest, [ring (3|4, 2), ...]), ...] -> start [n, 3], dest [n, 3], verts [n, max_obstacles, 4, 2], n_obst [n] in the
+    library's scene layout (a triangle repeats its last vertex in slot 3)"""
+    n = len(scenes)
+    start, dest = np.zeros((n, 3)), np.zeros((n, 3))
+    verts, nob = np.zeros((n, max_obstacles, 4, 2)), np.zeros(n, np.int32)
+    for k, (s, d, rings) in enumerate(scenes):
+        if len(rings) > max_obstacles:
+            raise ValueError(f'scene {k} has {len(rings)} obstacles > max_obstacles={max_obstacles}')
+        start[k], dest[k], nob[k] = s, d, len(rings)
+        for o, r in enumerate(rings):
+            r = np.asarray(r, dtype=np.float64)
+            verts[k, o, :len(r)] = r
+            verts[k, o, len(r):] = r[-1]
+    return start, dest, verts, nob
+
+
+def get_map_levels_host(start, dest, verts, n_obst, detail=False, n_threads=0):
+    """labels of a batch on the host (hope_map_level_host; no device): start, dest [n, 3], verts [n, max_obstacles, 4, 2], n_obst [n]
+    -> uint8 [n] (index into LEVEL_NAMES) [, int32 [n, 8] detail]"""
+    from . import _lib as L
+    lib = L.load_library()
+    start, dest = np.ascontiguousarray(start, dtype=np.float64), np.ascontiguousarray(dest, dtype=np.float64)
+    verts, n_obst = np.ascontiguousarray(verts, dtype=np.float64), np.ascontiguousarray(n_obst, dtype=np.int32)
+    n = len(n_obst)
+    if verts.ndim != 4 or verts.shape[0] != n or verts.shape[2:] != (4, 2) or start.shape != (n, 3) or dest.shape != (n, 3):
+        raise ValueError('get_map_levels_host: start / dest [n, 3], verts [n, max_obstacles, 4, 2], n_obst [n] expected')
+    level = np.zeros(n, np.uint8)
+    det = np.zeros((n, DETAIL_WORDS), np.int32) if detail else None
+    L.check(lib.hope_map_level_host(n, verts.shape[1], start.ctypes.data, dest.ctypes.data, verts.ctypes.data, n_obst.ctypes.data,
+                                    level.ctypes.data, det.ctypes.data if detail else None, int(n_threads)), 'hope_map_level_host')
+    return (level, det) if detail else level
+
+
+def get_map_levels_device(start, dest, verts, n_obst, detail=False):
+    """the same on the device the tensors live on (k_map_level, asynchronous on the current stream): float64 start, dest [n, 3],
+    verts [n, max_obstacles, 4, 2], int32 n_obst [n] -> torch.uint8 [n] [, int32 [n, 8]]"""
+    import torch
+    from . import _lib as L
+    lib = L.load_library()
+    n = n_obst.shape[0]
+    for t, dt, shape in ((start, torch.float64, (n, 3)), (dest, torch.float64, (n, 3)), (n_obst, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise ValueError('get_map_levels_device: contiguous device tensors start / dest float64 [n, 3], n_obst int32 [n] expected')
+    if verts.dtype != torch.float64 or verts.dim() != 4 or verts.shape[0] != n or tuple(verts.shape[2:]) != (4, 2) or not verts.is_cuda \
+            or not verts.is_contiguous():
+        raise ValueError('get_map_levels_device: verts must be a contiguous float64 device tensor [n, max_obstacles, 4, 2]')
+    dev = verts.device
+    level = torch.zeros(n, dtype=torch.uint8, device=dev)
+    det = torch.zeros((n, DETAIL_WORDS), dtype=torch.int32, device=dev) if detail else None
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(lib.hope_map_level_device(dev.index or 0, n, verts.shape[1], C.c_void_p(start.data_ptr()), C.c_void_p(dest.data_ptr()),
+                                      C.c_void_p(verts.data_ptr()), C.c_void_p(n_obst.data_ptr()), C.c_void_p(level.data_ptr()),
+                                      C.c_void_p(det.data_ptr()) if detail else None, stream), 'hope_map_level_device')
+    return (level, det) if detail else level

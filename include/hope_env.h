@@ -521,6 +521,33 @@ int hope_curriculum_lists_host(const hope_curriculum_params *params, int n_pool,
                                int32_t *list1, double *prob, double *pw, int32_t *positions);
 int hope_curriculum_fold_host(double *n, double *s, double dn, double ds, double window);
 
+/* ---- map difficulty label (additive to ABI 8) ----------------------------------------------------------------------------------
+ * `get_map_level` of the reference (src/env/map_level.py:27-112), which ParkingMapDLP.reset stores as map.map_level on every reset
+ * (src/env/parking_map_dlp.py:84) and the evaluation buckets its statistics by (src/evaluation/eval_utils.py:69-72, :99), for
+ * whole batches: one source (hope_amd/csrc/hope_maplevel_core.h, a restatement of hope_amd/map_level.py in exact operations) compiled
+ * for the host and as the kernel k_map_level (one wavefront per scene), bit-equal to each other.  Scene layout as
+ * hope_env_set_scenes: start [n][3], dest [n][3], verts [n][max_obstacles][4][2], n_obst [n] (clamped to 0 .. max_obstacles; <= 1
+ * gives Normal).  A triangle's slot (last vertex repeated) is read as a ring of three vertices.
+ * level [n] uint8: 0 Normal, 1 Complex, 2 Extrem.  detail [n][8] int32, may be NULL: [0..3] index of the left / right / front /
+ * back obstacle of the dest box (-1 none; each obstacle used once, the lower index wins equal distances), [4] which return fired
+ * (ML_B_* in hope_maplevel_core.h: 1 few obstacles, 2 - 4 the Extrem tests, 5 - 7 bay, 8 - 10 parallel, 11 - 12 the fall-through
+ * rules), [5] start further than 15 m from dest, [6] obstacles that meet the free rectangle (counted only with a detail buffer; the
+ * label needs the first), [7] 0.
+ * Misuse: HOPE_EINVAL (NULL level or input, n <= 0, max_obstacles outside 1 .. HOPE_MAX_OBSTACLES), HOPE_ESTATE (handle without
+ * scenes). */
+/* pure host code, no device; the result does not depend on n_threads (<= 0: as hope_scenegen_generate) */
+int hope_map_level_host(int n, int max_obstacles, const double *start, const double *dest, const double *verts, const int32_t *n_obst,
+                        uint8_t *level, int32_t *detail, int n_threads);
+/* the same from DEVICE buffers on device `device_id`, asynchronously on `stream`; no handle involved */
+int hope_map_level_device(int device_id, int n, int max_obstacles, const double *start, const double *dest, const double *verts,
+                          const int32_t *n_obst, uint8_t *level, int32_t *detail, void *stream);
+/* labels the maps the handle's scenes hold NOW (pool draws, Dragon-Lake draws and hope_env_set_scenes uploads alike), reading the
+ * handle's own tiles, start and dest: asynchronous on `stream`, ordered like every other entry that reads the handle's state (it
+ * joins a pipelined step first).  active: DEVICE u8 [N] or NULL; scenes with active[i] == 0 keep level[i] / detail[i] -- after a step
+ * with HOPE_AUTO_REDRAW pass that step's `done` to relabel only the scenes that drew a new map.  level: DEVICE u8 [N]; detail:
+ * DEVICE i32 [N][8] or NULL. */
+int hope_env_map_level(hope_env_t *h, const uint8_t *active, uint8_t *level, int32_t *detail, void *stream);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
