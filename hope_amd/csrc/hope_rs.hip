@@ -19,8 +19,11 @@
 //                  boxes overlap (the reference requires the intersection point inside both), so pairs failing that
 //                  exact pre-test skip the two float64 divisions.  The reference's obstacle cull (:482-494) and its
 //                  T x 4 x E matrix are result-neutral and are not materialised.
-// Deviation (documented in DESIGN.md): generate_local_course's "pop trailing samples whose local x is
-// exactly 0.0" (:501-505) is not replayed beyond the unused array tail (a measure-zero event).
+// Deviation (documented in DESIGN.md §4): generate_local_course's "pop trailing samples whose local x is
+// exactly 0.0" (:501-505) is not replayed beyond the unused array tail.  Exactly aligned poses do reach it (a word that
+// ends on the start's lateral axis: 288 of the 4 002 searches of tests/rs_degenerate.py lose their last sample in the
+// reference); on none of them does it change the found flag, the number of tested words, the word or its lengths
+// (tests/test_rs_degenerate.py runs the oracle both ways; tests/test_gpu_rs_degenerate.py compares the kernels with it).
 #include <stdlib.h>
 
 #include "hope_dev.h"

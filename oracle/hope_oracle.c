@@ -39,7 +39,43 @@
 #define hm_atan2 atan2
 #define hm_asin asin
 #define hm_acos acos
-#define hm_hypot hypot
+/* Python's math.hypot is not glibc's hypot: since CPython 3.10 it scales by a power of two, splits every argument into a high
+ * and a low half (Veltkamp, 2^27 + 1), sums the squares with the rounding errors kept in three side sums, takes the root and
+ * applies one differential correction -- correctly rounded far more often than glibc's, and different from it in the last bit on
+ * about 0.6 % of arguments.  `path.L` of exactly equal-length twin words is sensitive to that bit (tests/test_rs_degenerate.py),
+ * so the build that is pinned against the reference's vectors carries the same evaluation order (two arguments).  This is the
+ * routine of CPython 3.10.12 (Modules/mathmodule.c, vector_norm), the interpreter that wrote tests/golden/rs_degenerate.npz; the
+ * file records that version and 1 500 math.hypot values, and tests/test_rs_degenerate.py holds this function to both.  It
+ * replaces glibc's hypot for every user of the glibc build (math_fn 6, rs_R; tools/libm_soak.py and tests/libm_compare.py run on it): what
+ * that build stands for is the reference under this interpreter, not glibc alone. */
+static double py_hypot(double a, double b) {
+    const double T27 = 134217729.0;
+    const double v[2] = {fabs(a), fabs(b)};
+    const double mx = v[0] > v[1] ? v[0] : v[1];
+    if (isinf(a) || isinf(b)) return INFINITY;
+    if (isnan(a) || isnan(b)) return NAN;
+    if (mx == 0.0) return mx;
+    int e;
+    frexp(mx, &e);
+    if (e < -1023) return hypot(a, b);                     /* (subnormal maximum: never reached by the path solvers) */
+    const double scale = ldexp(1.0, -e);
+    double x, old, csum = 1.0, f1 = 0.0, f2 = 0.0, f3 = 0.0, t, hi, lo;
+    for (int i = 0; i < 2; i++) {
+        x = v[i] * scale;
+        t = x * T27; hi = t - (t - x); lo = x - hi;
+        x = hi * hi; old = csum; csum += x; f1 += (old - csum) + x;
+        x = 2.0 * hi * lo; old = csum; csum += x; f2 += (old - csum) + x;
+        f3 += lo * lo;
+    }
+    const double h = sqrt(csum - 1.0 + (f1 + f2 + f3));
+    t = h * T27; hi = t - (t - h); lo = h - hi;
+    x = -hi * hi; old = csum; csum += x; f1 += (old - csum) + x;
+    x = -2.0 * hi * lo; old = csum; csum += x; f2 += (old - csum) + x;
+    x = -lo * lo; old = csum; csum += x; f3 += (old - csum) + x;
+    x = csum - 1.0 + (f1 + f2 + f3);
+    return (h + x / (2.0 * h)) / scale;
+}
+#define hm_hypot py_hypot
 #define hm_fmod fmod
 #define hm_tanh tanh
 #endif
@@ -934,10 +970,28 @@ static void *arena_alloc(size_t bytes, int zero) {
     }
 }
 
+static int g_rs_tail_only;                  /* orc_rs_pop_mode: 1 = keep every sample in use (the kernels' form) */
+static __thread long g_rs_used_popped;      /* samples in use that the reference's pop removed, on this thread */
+void orc_rs_pop_mode(int tail_only) { g_rs_tail_only = tail_only; }
+long orc_rs_used_popped(int reset) { long v = g_rs_used_popped; if (reset) g_rs_used_popped = 0; return v; }
+
 /* :452-507 generate_local_course.  Returns the number of points kept; arrays from the thread's arena. */
 static int rs_local_course(double L, const double *lengths, const int *mode, int nseg, double maxc,
                            double step_size, double **opx, double **opy, double **opyaw, int **odir) {
-    int point_num = (int)(L / step_size) + nseg + 3;
+    /* The reference sizes its lists int(L / step_size) + len(lengths) + 3 (:453).  A word that opens with zero-length segments
+     * (RLRL [0.0, -0.0, -0.0, pi]: the car exactly beside the goal, heading reversed) carries "remaining length" over from them,
+     * starts the next segment at a pd of the wrong sign and writes past that size: the reference raises IndexError there
+     * (tests/test_rs_degenerate.py, `ref_error`).  The course continues here as if the lists had been long enough, which is also
+     * what the kernels compute, so the arrays are sized by what the loop below can write, whatever pd a segment starts at:
+     * its while loop adds d (|d| = step_size, sign of l) while pd stays inside [-|l|, |l|], an interval 2 |l| wide, so it runs at
+     * most floor(2 |l| / step_size) + 1 times (+ 1 for the rounding of the repeated sum), and each run advances `ind` by one; the
+     * segment's own "ind -= 1 ... ind += 1" cancel.  With ind = 1 at the start the highest index written is at most
+     * 1 + sum_i (floor(2 |l_i| / step_size) + 2) <= 1 + 2 floor(sum |l_i| / step_size) + 3 nseg.  (Entries beyond the
+     * reference's size stay 0.0 and the trailing pop below removes them, so a word that fits the reference's lists is unchanged.) */
+    double sum = 0.0;
+    for (int i = 0; i < nseg; i++) sum += fabs(lengths[i]);
+    if (sum < L) sum = L;
+    int point_num = 2 * (int)(sum / step_size) + 3 * nseg + 3;
     double *px = (double *)arena_alloc(point_num * sizeof(double), 1);
     double *py = (double *)arena_alloc(point_num * sizeof(double), 1);
     double *pyaw = (double *)arena_alloc(point_num * sizeof(double), 1);
@@ -962,8 +1016,16 @@ static int rs_local_course(double L, const double *lengths, const int *mode, int
         ind += 1;
         rs_interpolate(ind, l, m, maxc, ox, oy, oyaw, px, py, pyaw, dir);
     }
+    /* "remove unused data" (:500-505) pops every trailing entry whose local x is exactly 0.0: the unused tail of the arrays AND,
+     * on exactly aligned poses, the samples in use that end on the start's lateral axis (tests/test_rs_degenerate.py).  The
+     * kernels drop the unused tail only; g_rs_tail_only restates that form so that the two can be compared on the host. */
+    const int used = ind + 1;
     int n = point_num;
-    while (n > 0 && px[n - 1] == 0.0) n--; /* "remove unused data" */
+    while (n > 0 && px[n - 1] == 0.0) n--;
+    if (n < used) {
+        g_rs_used_popped += used - n;
+        if (g_rs_tail_only) n = used;
+    }
     *opx = px; *opy = py; *opyaw = pyaw; *odir = dir;
     return n;
 }
@@ -1157,6 +1219,10 @@ static int hd_pop(hd_t *h) {
     return top;
 }
 
+/* sample counts of the words the last orc_find_rs_path of this thread handed to is_traj_valid, in pop order (tests) */
+static __thread int32_t g_rs_tested_npts[RS_MAXP];
+void orc_rs_tested_npts(int32_t *out, int n) { for (int i = 0; i < n && i < RS_MAXP; i++) out[i] = g_rs_tested_npts[i]; }
+
 /* car_parking_base.py:413-450 find_rs_path.  Returns 1 if a collision-free path was found. */
 int orc_find_rs_path(const double *pose, const double *dest, const double *verts, const int32_t *nvert,
                      int n_obst, const double *bbox, int32_t *out_nseg, int32_t *out_ct, double *out_len,
@@ -1185,6 +1251,7 @@ int orc_find_rs_path(const double *pose, const double *dest, const double *verts
             for (int k = 0; k < T; k++) { traj[3 * k] = P[pi].x[k]; traj[3 * k + 1] = P[pi].y[k]; traj[3 * k + 2] = P[pi].yaw[k]; }
             int ok = orc_is_traj_valid(traj, T, verts, nvert, n_obst, bbox);
             arena_release(tm_);
+            g_rs_tested_npts[ntested] = T;
             ntested++;
             if (ok) {
                 found = 1;

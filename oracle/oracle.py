@@ -202,7 +202,22 @@ def find_rs_path(pose, dest, verts, nvert, bbox):
     Lr = C.c_double(0)
     found = lib().orc_find_rs_path(_p(_f64(pose)), _p(_f64(dest)), _p(v), _p(nv), C.c_int(len(nv)), _p(_f64(bbox)),
                                    C.byref(nseg), _p(ct), _p(ln), C.byref(Lr), C.byref(ntest))
-    return dict(found=bool(found), nseg=nseg.value, ctypes=ct, lengths=ln, L=Lr.value, n_tested=ntest.value)
+    npts = np.zeros(ntest.value, np.int32)
+    lib().orc_rs_tested_npts(_p(npts), C.c_int(ntest.value))
+    return dict(found=bool(found), nseg=nseg.value, ctypes=ct, lengths=ln, L=Lr.value, n_tested=ntest.value, npts=npts)
+
+
+def rs_pop_mode(tail_only):
+    """generate_local_course's trailing pop (reeds_shepp.py:500-505) in the selected single-thread library: False (default) =
+    the reference's (samples in use whose local x is exactly 0.0 go too), True = the unused array tail only, as the kernels do."""
+    lib().orc_rs_pop_mode(C.c_int(int(bool(tail_only))))
+
+
+def rs_used_popped(reset=True):
+    """samples in use that the reference's pop removed (or would have removed) since the last reset, on the calling thread"""
+    L = lib()
+    L.orc_rs_used_popped.restype = C.c_long
+    return int(L.orc_rs_used_popped(C.c_int(int(reset))))
 
 
 def target_repr(ego, dest):

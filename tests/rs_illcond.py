@@ -90,3 +90,28 @@ def allowed_results(pose, dest, verts, nvert, bbox):
     for sq in seqs:
         allowed |= walk(sq)
     return allowed
+
+
+def tie_group_results(pose, dest, verts, nvert, bbox):
+    """allowed_results swaps ADJACENT words of equal length; with the heading exactly reversed four words tie exactly (LRL / RLR,
+    each forwards and time-reversed: tests/rs_degenerate.py), so any member of a tie group (lengths chained within 1e-9) may pop
+    first.  Returns the set of words (tuples of type codes, () = no path) reachable that way."""
+    r = O.rs_all_paths(pose, dest, MAXC)
+    order = sorted(range(r['n']), key=lambda i: r['L'][i])
+    groups = []
+    for i in order:
+        if groups and abs(r['L'][i] - r['L'][groups[-1][-1]]) <= 1e-9 * max(1.0, r['L'][i]):
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+    out, popped = set(), 0
+    for grp in groups:
+        if r['L'][grp[0]] > 1.6 * r['L'][order[0]] * (1 + 1e-12) and popped + 1 > 2:
+            break
+        cls = [path_class(O.rs_path_samples(pose, dest, MAXC, int(i)), verts, nvert, bbox) for i in grp]
+        out |= {tuple(int(t) for t in r['ctypes'][i][:r['nseg'][i]]) for i, c in zip(grp, cls) if c != 'invalid'}
+        if 'valid' in cls:
+            return out
+        popped += len(grp)
+    out.add(())
+    return out
