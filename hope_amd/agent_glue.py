@@ -94,6 +94,87 @@ class BatchedRsPlanner:
         return a, ex
 
 
+class DeviceRsPlanner:
+    """BatchedRsPlanner's surface over the library's planner (include/hope_env.h "replay of found Reeds-Shepp paths"): the
+    state lives in the env's handle (48 B per scene), one k_plan launch per call, no host synchronisation, no cap on the number
+    of actions.  `step(done, rs_word, rs_lengths)` fuses reset(done) + set_paths + get_actions -- what a rollout does between
+    two env steps.  Rows of `planned` that are not executing are 0 (the torch class leaves stale values there).
+    On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same step runs on the host through
+    hope_planner_step_host: the rule is one source for both."""
+
+    def __init__(self, env, step_ratio=STEP_RATIO):
+        self.env, self.n, self.step_ratio = env, env.n, float(step_ratio)
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'planner_step')
+        if self.on_device:
+            env.enable_planner(self.step_ratio)
+            self._zero_word = torch.zeros((self.n, 8), dtype=torch.int8, device=self.device)
+            self._lens = torch.zeros((self.n, 5), dtype=env.obs_dtype, device=self.device)
+        else:
+            import numpy as np
+            from . import _lib as L
+            assert self.device.type == 'cpu', 'an env without planner_step must hold CPU tensors'
+            self._L, self._lib = L, L.load_library()
+            self._state = np.zeros((L.PLAN_STATE_WORDS, self.n), np.uint64)
+            self._planned = torch.zeros((self.n, 2), dtype=torch.float64)
+            self._exec = torch.zeros(self.n, dtype=torch.uint8)
+            self._zero_word = torch.zeros((self.n, 8), dtype=torch.int8)
+            self._lens = torch.zeros((self.n, 5), dtype=torch.float32)
+
+    @property
+    def executing(self):
+        """bool [N]: scenes currently replaying a path.  Downloads the state: host-synchronous (statistics, tests)."""
+        st = self.env.planner_state() if self.on_device else self._state
+        busy = ((st[5] >> 13) & 1).astype('uint8')
+        return torch.from_numpy(busy).to(self.device).bool()
+
+    def _host_step(self, word, lens, done, flags, step=None):
+        word = word.contiguous()
+        lens = lens.contiguous()
+        assert word.dtype == torch.int8 and word.shape == (self.n, 8) and lens.shape == (self.n, 5)
+        assert lens.dtype in (torch.float32, torch.float64)
+        dp = None
+        if done is not None:
+            done = done.to(torch.uint8).contiguous()
+            dp = done.data_ptr()
+        self._L.check(self._lib.hope_planner_step_host(self.n, self.step_ratio, self._state.ctypes.data, word.data_ptr(), lens.data_ptr(),
+                                                       int(lens.dtype == torch.float64), dp, flags, self._planned.data_ptr(),
+                                                       self._exec.data_ptr(), None, 0), 'hope_planner_step_host')
+        return self._planned, self._exec.view(torch.bool)
+
+    def reset(self, mask=None):
+        if self.on_device:
+            self.env.planner_reset(None if mask is None else mask.to(torch.uint8).contiguous())
+        elif mask is None:
+            self._state[:] = 0
+        else:
+            self._state[:, mask.bool().numpy()] = 0
+
+    def set_paths(self, rs_word, rs_lengths, forced=False):
+        """adopt newly found paths (idle scenes, or all with forced); nothing is popped.  Returns None: which scenes took a path is
+        known on the device only."""
+        if self.on_device:
+            self.env.planner_step(forced=forced, step=0, rs_word=rs_word, rs_lengths=rs_lengths, done=None, pop=False)
+        else:
+            self._host_step(rs_word, rs_lengths, None, (self._L.PLAN_FORCED if forced else 0) | self._L.PLAN_NO_POP)
+
+    def get_actions(self):
+        """pop the next planned action of every executing scene -> ([N,2] float64 actions, bool [N] which rows are valid)"""
+        if self.on_device:
+            return self.env.planner_step(step=0, rs_word=self._zero_word, rs_lengths=self._lens, done=None)
+        return self._host_step(self._zero_word, self._lens, None, 0)
+
+    def step(self, done=None, rs_word=None, rs_lengths=None, forced=False, step=None):
+        """reset(done) + set_paths(rs_word, rs_lengths, forced) + get_actions() in one call.  On the device the arguments default to
+        the env's own outputs of its last step, and step = env.last_step() of that step makes the call wait for its search."""
+        if self.on_device:
+            return self.env.planner_step(forced=forced, step=step, rs_word=rs_word, rs_lengths=rs_lengths,
+                                         done=True if done is None else done.to(torch.uint8))
+        env = self.env
+        return self._host_step(env.rs_word if rs_word is None else rs_word, env.rs_lengths if rs_lengths is None else rs_lengths,
+                               env.done if done is None else done, self._L.PLAN_FORCED if forced else 0)
+
+
 _ACTIONS = None
 
 

@@ -364,6 +364,70 @@ class ParkingBatch:
             L.check(self.lib.hope_env_wait_rs_step(self.h, C.c_uint64(int(step)), self._stream()), 'hope_env_wait_rs_step')
         return self
 
+    # -- replay of found Reeds-Shepp paths on the device (hope_env.h; rule: csrc/hope_planner_core.h) -----------------
+    def enable_planner(self, step_ratio=L.PLAN_STEP_RATIO):
+        """RsPlanner / ParkingAgent's path replay as device state of the handle (48 B per scene, every scene idle).  Off by default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_planner_enable(self.h, float(step_ratio)), 'hope_env_planner_enable')
+        if getattr(self, 'planned', None) is None:
+            self.planned = torch.zeros((self.n, 2), dtype=torch.float64, device=self.device)
+            self._plan_exec = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+            self.plan_executing = self._plan_exec.view(torch.bool)
+        return self
+
+    def disable_planner(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_planner_disable(self.h), 'hope_env_planner_disable')
+        return self
+
+    def planner_reset(self, mask=None):
+        """clear the path of the scenes flagged in mask (u8 [N]), or of all (asynchronous on the current stream)"""
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.shape == (self.n,) and mask.device == self.device and mask.is_contiguous()
+        L.check(self.lib.hope_env_planner_reset(self.h, C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()),
+                'hope_env_planner_reset')
+        return self
+
+    def planner_step(self, forced=False, step=None, actions=None, rs_word=None, rs_lengths=None, done=True, pop=True):
+        """one k_plan launch on the current stream, no host synchronisation: the scenes the last step finished drop their path,
+        found words are adopted (by idle scenes, or by all with forced), busy scenes pop their next action.
+        -> (planned f64 [N, 2], executing bool [N]): persistent tensors of this object, overwritten by the next call.
+        step = a value of last_step(): the call waits for THAT step's search (as wait_rs(step)) and raises when a newer step has
+        replaced its words; None: a plain wait_rs() first.  actions: [N, 2] of the env's action dtype, the executing rows are
+        overwritten in place.  rs_word / rs_lengths / done default to the env's own outputs (done=None: no scene is cleared);
+        pop=False: bookkeeping only."""
+        if step is None:
+            L.check(self.lib.hope_env_wait_rs(self.h, self._stream()), 'hope_env_wait_rs')
+        word = self.rs_word if rs_word is None else rs_word
+        lens = self.rs_lengths if rs_lengths is None else rs_lengths
+        dn = self.done if done is True else done
+        assert word.dtype == torch.int8 and word.shape == (self.n, 8) and word.device == self.device and word.is_contiguous()
+        assert lens.dtype == self.obs_dtype and lens.shape == (self.n, 5) and lens.device == self.device and lens.is_contiguous()
+        if dn is not None:
+            assert dn.dtype == torch.uint8 and dn.shape == (self.n,) and dn.device == self.device and dn.is_contiguous()
+        af64 = 0
+        if actions is not None:
+            assert actions.shape == (self.n, 2) and actions.dtype in (torch.float32, torch.float64) and actions.is_contiguous()
+            assert actions.device == self.device
+            af64 = int(actions.dtype == torch.float64)
+        flags = (L.PLAN_FORCED if forced else 0) | (0 if pop else L.PLAN_NO_POP)
+        if getattr(self, 'planned', None) is None:       # (the library then reports that the planner is off)
+            pp = ep = None
+        else:
+            pp, ep = C.c_void_p(self.planned.data_ptr()), C.c_void_p(self._plan_exec.data_ptr())
+        L.check(self.lib.hope_env_planner_step(self.h, C.c_void_p(word.data_ptr()), C.c_void_p(lens.data_ptr()),
+                                               C.c_void_p(dn.data_ptr()) if dn is not None else None, flags, C.c_uint64(int(step or 0)),
+                                               pp, ep, C.c_void_p(actions.data_ptr()) if actions is not None else None, af64,
+                                               self._stream()), 'hope_env_planner_step')
+        return self.planned, self.plan_executing
+
+    def planner_state(self):
+        """the planner's state block (numpy uint64 [6, N]: the five segment lengths in steps as float64 bits, the packed cursor
+        word) -- host-synchronous; tests"""
+        out = np.zeros((L.PLAN_STATE_WORDS, self.n), np.uint64)
+        L.check(self.lib.hope_env_planner_download_state(self.h, out.ctypes.data), 'hope_env_planner_download_state')
+        return out
+
     def queue_check(self):
         """hope_env_create's measurement of which library streams share a hardware queue (hope_env_queue_check):
         {'queue_of_role': [8 ints, [0] = the NULL stream], 'distinct_queues': n, 'roles_shared': pairs of roles busy in the same step

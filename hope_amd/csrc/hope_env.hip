@@ -20,6 +20,7 @@
 #include "hope_scenegen_kernel.h"
 #include "hope_curriculum_kernel.h"
 #include "hope_maplevel_kernel.h"
+#include "hope_planner_kernel.h"
 
 using namespace hope;
 
@@ -190,6 +191,8 @@ struct hope_env {
         hipEvent_t ev_order = nullptr;
     } cur;
     int draw_set = -1;                                      // pool set the last step / hope_env_redraw drew from
+    // replay of found Reeds-Shepp paths (hope_planner_kernel.h): [PL_WORDS][n] state words, nullptr while the planner is off
+    struct Planner { bool on = false; double step_ratio = HOPE_PLAN_STEP_RATIO; uint64_t* state = nullptr; } plan;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -582,6 +585,7 @@ int hope_abi_version(void) { return HOPE_ABI_VERSION; }
 
 static int destroy_impl(hope_env_t* h);
 static void cur_free(hope_env_t* h);
+static void plan_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -845,6 +849,7 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     for (int i = 0; i < 2; i++) { if (h->gen_nobst[i]) hipHostFree(h->gen_nobst[i]); if (h->ev_gen_copied[i]) hipEventDestroy(h->ev_gen_copied[i]); }
     for (hipEvent_t e : h->free_events) hipEventDestroy(e);
     cur_free(h);
+    plan_free(h);
     for (auto& ps : h->pset) for (void* q : {(void*)ps.label, (void*)ps.sorted_own[0], (void*)ps.sorted_own[1]}) if (q) hipFree(q);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
@@ -912,6 +917,102 @@ int hope_env_queue_check(hope_env_t* h, int32_t* queue_of_role, int32_t* n_queue
     if (queue_of_role) for (int r = 0; r < N_ROLES; r++) queue_of_role[r] = h->queue_of_role[r];
     if (n_queues) *n_queues = h->n_queues;
     if (ms) *ms = h->queue_check_ms;
+    return HOPE_OK;
+}
+
+// ---- replay of found Reeds-Shepp paths (include/hope_env.h; kernel: hope_planner_kernel.h, rule: hope_planner_core.h) ----
+static void plan_free(hope_env_t* h) {
+    if (h->plan.state) hipFree(h->plan.state);
+    h->plan = hope_env::Planner{};
+}
+
+int hope_env_planner_enable(hope_env_t* h, double step_ratio) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_enable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_enable: not a live handle (destroyed?)");
+    if (step_ratio != step_ratio || !pl_finite(step_ratio)) return fail(HOPE_EINVAL, "hope_env_planner_enable: step_ratio is not finite");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());                         // planner steps in flight read the state
+    const size_t bytes = (size_t)PL_WORDS * h->n * sizeof(uint64_t);
+    if (!h->plan.state) {
+        hipError_t e_ = hipMalloc((void**)&h->plan.state, bytes);
+        if (e_ != hipSuccess) { h->plan.state = nullptr; return fail(HOPE_ENOMEM, std::string("hope_env_planner_enable: ") + hipGetErrorString(e_)); }
+    }
+    HIPCHK(hipMemset(h->plan.state, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    h->plan.step_ratio = step_ratio > 0.0 ? step_ratio : HOPE_PLAN_STEP_RATIO;
+    h->plan.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_planner_disable(hope_env_t* h) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_disable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_disable: not a live handle (destroyed?)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    plan_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_planner_reset(hope_env_t* h, const uint8_t* mask, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_reset: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_reset: not a live handle (destroyed?)");
+    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_reset: the planner is off (hope_env_planner_enable first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (!mask) {
+        HIPCHK(hipMemsetAsync(h->plan.state, 0, (size_t)PL_WORDS * h->n * sizeof(uint64_t), (hipStream_t)stream));
+        return HOPE_OK;
+    }
+    hipLaunchKernelGGL(k_plan_reset, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, mask, h->plan.state);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_planner_step(hope_env_t* h, const int8_t* rs_word, const void* rs_lengths, const uint8_t* done, int forced, uint64_t step,
+                          double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_step: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_step: not a live handle (destroyed?)");
+    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_step: the planner is off (hope_env_planner_enable first)");
+    if (!rs_word || !rs_lengths) return fail(HOPE_EINVAL, "hope_env_planner_step: null rs_word / rs_lengths");
+    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_env_planner_step: unknown bit in `forced`");
+    const bool lf64 = h->flags & HOPE_F_OBS_F64;
+    if (((uintptr_t)rs_word & 7) || ((uintptr_t)rs_lengths & (lf64 ? 7 : 3)) || ((uintptr_t)planned_out & 15) ||
+        ((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)))
+        return fail(HOPE_EINVAL, "hope_env_planner_step: misaligned buffer (rs_word 8, planned_out 16, actions 8 / 16 bytes)");
+    if (step != 0) {                                        // hope_env_wait_rs_step, before anything is touched
+        if (step > h->step_seq) return fail(HOPE_EINVAL, "hope_env_planner_step: no such step (hope_env_last_step)");
+        if (step != h->step_seq)
+            return fail(HOPE_ESTATE, "hope_env_planner_step: step " + std::to_string(step) + " is not the last one (" + std::to_string(h->step_seq) +
+                                     "): a later hope_env_step / hope_env_reset_obs has replaced its Reeds-Shepp outputs -- plan before enqueuing the next step");
+    }
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (step != 0) { int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
+    hipLaunchKernelGGL(k_plan, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)rs_word, rs_lengths, lf64 ? 1 : 0, done,
+                       forced, h->plan.step_ratio, h->plan.state, (double2*)planned_out, executing_out, actions_inout, action_is_f64 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_planner_step_host(int n, double step_ratio, void* state, const int8_t* rs_word, const void* rs_lengths, int lengths_f64,
+                           const uint8_t* done, int forced, double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64) {
+    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_planner_step_host: unknown bit in `forced`");
+    const int rc = pl_step_host(n, step_ratio > 0.0 ? step_ratio : (step_ratio == 0.0 ? HOPE_PLAN_STEP_RATIO : step_ratio), state, rs_word, rs_lengths, lengths_f64,
+                                done, forced, planned_out, executing_out, actions_inout, action_is_f64);
+    if (rc != HOPE_OK) return fail(rc, "hope_planner_step_host: bad argument (n <= 0, a null state / rs_word / rs_lengths, or a step_ratio that is not positive and finite)");
+    return HOPE_OK;
+}
+
+int hope_env_planner_download_state(hope_env_t* h, void* state_out) {
+    if (!h || !state_out) return fail(HOPE_EINVAL, "hope_env_planner_download_state: null argument");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_download_state: not a live handle (destroyed?)");
+    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_download_state: the planner is off (hope_env_planner_enable first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(state_out, h->plan.state, (size_t)PL_WORDS * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return HOPE_OK;
 }
 

@@ -27,7 +27,11 @@ class BatchedEvaluator:
         """agent: a hope_amd.agents agent (`act(obs, use_mask, generator, planned, executing)`); post_proc_action: PPO's
         mask-weighted choose_action (eval_utils.py:42-43) instead of the plain sample (:44-45)."""
         self.env, self.agent, self.use_mask = env, agent, bool(post_proc_action)
-        self.planner = G.BatchedRsPlanner(env.n, device=env.device) if use_planner else None
+        if use_planner == 'device':          # the library's planner: one k_plan launch per step (agent_glue.DeviceRsPlanner)
+            self.planner = G.DeviceRsPlanner(env)
+        else:
+            self.planner = G.BatchedRsPlanner(env.n, device=env.device) if use_planner else None
+        self._device_planner = use_planner == 'device'
         self.gen = torch.Generator(device=env.device)
         self.gen.manual_seed(seed)
         lo = torch.tensor([T.VALID_STEER[0], T.VALID_SPEED[0]], dtype=torch.float64, device=env.device)
@@ -63,10 +67,14 @@ class BatchedEvaluator:
         last_xy = env.pose[:, :2].clone()
         last_target = env.target.clone()                              # last_obs = obs['target'] (:39)
         first = True
+        pending = None                                                # device planner: (done, word, lengths) of the last step
         for _ in range(max_steps):
             if not bool(alive.any()):
                 break
-            planned, executing = self.planner.get_actions() if self.planner is not None else (None, None)
+            if self._device_planner and pending is not None:       # reset(done) + set_paths + get_actions of the last step, fused
+                planned, executing = self.planner.step(*pending)
+            else:
+                planned, executing = self.planner.get_actions() if self.planner is not None else (None, None)
             action, _, _ = agent.act(self._obs(), self.use_mask, self.gen, planned, executing)
             # stuck detector (:46-47): the very first comparison is obs['target'] with itself -> always a random first action
             same = torch.ones(n, dtype=torch.bool, device=dev) if first else (env.target == last_target).all(dim=1)
@@ -83,10 +91,13 @@ class BatchedEvaluator:
             done = alive & env.done.bool()
             status = torch.where(done, env.status, status)
             if self.planner is not None:
-                self.planner.reset(done)
                 word = env.rs_word.clone()                         # info['path_to_dest'] -> agent.set_planner_path (:55-56)
                 word[~(alive & ~done), 6] = 0                      # (frozen slots keep stale outputs)
-                self.planner.set_paths(word, env.rs_lengths)
+                if self._device_planner:
+                    pending = (done, word, env.rs_lengths)
+                else:
+                    self.planner.reset(done)
+                    self.planner.set_paths(word, env.rs_lengths)
             alive = alive & ~done
         rec = torch.stack([status.float(), steps.float(), total.float(), path.float()], dim=1)
         if gather:

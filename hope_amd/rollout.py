@@ -144,6 +144,10 @@ class HopeRollout:
         pool_refresher: a `scene_gen.PoolRefresher` (host generator + upload) or `scene_gen.DevicePoolRefresher` (lots drawn on the
         device); the trainers poll it after every update, so the pool of generated lots is
         replaced by new ones in the background (asynchronous upload, no synchronisation with the step loop).
+        use_planner: True -- the torch planner (agent_glue.BatchedRsPlanner); 'device' -- the library's planner
+        (agent_glue.DeviceRsPlanner): its bookkeeping and the pop are ONE k_plan launch per step that waits for the step's search on
+        the device (`planner_step(step=...)`), with no wait_rs, no `.any()` and no boolean indexing, so the host never stops on the
+        search result; the same actions as True.  False / None: no planner.
         curriculum: None, or dict(update_every=K, **rule parameters) -- the reference's SceneChoose / DlpCaseChoose
         (train_HOPE_sac.py:23-97) on the device: the env tallies every finished episode's outcome per scene type / Dragon-Lake case
         after each step and rebuilds its weighted draw lists every K steps (hope_amd.curriculum.CurriculumDriver); needs
@@ -163,7 +167,15 @@ class HopeRollout:
         self._rs_step = None                          # hope_env_last_step() of the deferred step whose search the planner waits for
         dev = env.device
         self.ring = TransitionRing(env.n, horizon, agent.keys, dev)
-        self.planner = G.BatchedRsPlanner(env.n, device=dev) if use_planner else None
+        if use_planner == 'device':
+            self.planner = G.DeviceRsPlanner(env)
+        elif use_planner is True or use_planner == 1:
+            self.planner = G.BatchedRsPlanner(env.n, device=dev)
+        elif not use_planner:
+            self.planner = None
+        else:
+            raise ValueError(f"use_planner must be True, False or 'device', not {use_planner!r}")
+        self._device_planner = isinstance(self.planner, G.DeviceRsPlanner)
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
         self.episodes = torch.zeros((), dtype=torch.int64, device=dev)
@@ -187,6 +199,11 @@ class HopeRollout:
         the actions of the scenes that are replaying a path"""
         if self.planner is None:
             return None, None
+        if self._device_planner:
+            if not self._plan_pending:                              # before the first step: nothing to adopt, every scene idle
+                return self.planner.get_actions()
+            self._plan_pending = False
+            return self.planner.step(step=self._rs_step)            # one launch; waits for that step's search on the device
         if self._plan_pending:
             env = self.env
             if self.defer_rs:

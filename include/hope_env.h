@@ -548,6 +548,49 @@ int hope_map_level_device(int device_id, int n, int max_obstacles, const double 
  * DEVICE i32 [N][8] or NULL. */
 int hope_env_map_level(hope_env_t *h, const uint8_t *active, uint8_t *level, int32_t *detail, void *stream);
 
+/* ---- replay of found Reeds-Shepp paths (additive to ABI 8) --------------------------------------------------------------------
+ * The reference's hybrid controller: RsPlanner (src/model/agent/parking_agent.py:2-47) turns a found path into unit actions
+ * [steer in {1, 0, -1}, signed fraction of a full step] and ParkingAgent.choose_action (:78-95) replays them instead of asking the
+ * policy; a new path is adopted only while none is being replayed (set_planner_path :65-69) and the path is dropped at episode end
+ * (reset :61-63).  Here the planner is device-resident state of the handle: 48 bytes per scene (the five segment lengths in steps
+ * and a packed cursor word; nothing is expanded into a queue, so there is no cap on the number of actions) and one kernel, k_plan,
+ * per step.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule, the state
+ * layout and the bit-equal host twin: hope_amd/csrc/hope_planner_core.h, DESIGN.md 5e.
+ *
+ * One planner step does, per scene and in this order: done[s] != 0 clears the path; a found word (rs_word[s][6] > 0) is adopted
+ * if the scene is idle, or always with HOPE_PLAN_FORCED (a word that expands to no action leaves the scene idle); a busy scene
+ * pops its next action and is idle again after its last one. */
+#define HOPE_PLAN_STATE_WORDS 6     /* 8-byte words of state per scene, stored as planes: [6][N] */
+#define HOPE_PLAN_STEP_RATIO 1.25   /* kinetic_model.step_len * n_step * VALID_SPEED[1] = 0.05 * 10 * 2.5 (train_HOPE_sac.py:164) */
+/* bits of the `forced` argument */
+#define HOPE_PLAN_FORCED 0x1        /* set_planner_path(forced=True): a found word replaces a path that is being replayed */
+#define HOPE_PLAN_NO_POP 0x2        /* sub-steps 1 and 2 only: nothing is popped, no output is written */
+/* allocate and zero the state (every scene idle).  step_ratio: metres per full action; <= 0 takes HOPE_PLAN_STEP_RATIO.  Enabling an
+ * enabled planner clears it.  Host-synchronous. */
+int hope_env_planner_enable(hope_env_t *h, double step_ratio);
+/* free the state.  Host-synchronous (planner steps in flight read it). */
+int hope_env_planner_disable(hope_env_t *h);
+/* clears the path of the scenes with mask[s] != 0 (DEVICE u8 [N]), or of every scene when mask is NULL; asynchronous on `stream` */
+int hope_env_planner_reset(hope_env_t *h, const uint8_t *mask, void *stream);
+/* k_plan, asynchronous on `stream`; never synchronises the host.  DEVICE buffers: rs_word i8 [N][8] (8-byte aligned) and rs_lengths
+ * real [N][5] as hope_step_out has them (float64 iff the handle has HOPE_F_OBS_F64); done u8 [N] or NULL; planned_out f64 [N][2]
+ * (16-byte aligned; rows of scenes that pop nothing are written as 0) or NULL; executing_out u8 [N] (1 where planned_out holds an
+ * action) or NULL; actions_inout [N][2] float32 or float64 (action_is_f64; 8- / 16-byte aligned) or NULL: the rows of executing
+ * scenes are overwritten with the planned action rounded to that type, the others are left as they are.  forced: HOPE_PLAN_* bits.
+ * step != 0: the call first does exactly what hope_env_wait_rs_step(h, step, stream) does -- the words it reads are those of THAT
+ * step's search, and HOPE_ESTATE (nothing touched) when a newer step has been enqueued since.  step == 0: no wait; the caller has
+ * ordered `stream` after whatever wrote the buffers.  HOPE_ESTATE before hope_env_planner_enable, HOPE_EINVAL for a NULL or
+ * misaligned rs_word / rs_lengths / output. */
+int hope_env_planner_step(hope_env_t *h, const int8_t *rs_word, const void *rs_lengths, const uint8_t *done, int forced, uint64_t step,
+                          double *planned_out, uint8_t *executing_out, void *actions_inout, int action_is_f64, void *stream);
+/* The same step over HOST arrays with a caller-owned state block (HOPE_PLAN_STATE_WORDS * n 8-byte words, zeroed = every scene
+ * idle; zeroing a scene's six words clears its path): pure host code from the same source, no handle, no device.  Bit-equal to k_plan. */
+int hope_planner_step_host(int n, double step_ratio, void *state, const int8_t *rs_word, const void *rs_lengths, int lengths_f64,
+                           const uint8_t *done, int forced, double *planned_out, uint8_t *executing_out, void *actions_inout,
+                           int action_is_f64);
+/* the state block as the next planner step will read it (host array of HOPE_PLAN_STATE_WORDS * N 8-byte words); host-synchronous */
+int hope_env_planner_download_state(hope_env_t *h, void *state_out);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
