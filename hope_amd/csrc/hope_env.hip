@@ -354,6 +354,98 @@ __global__ void k_debug_math(int fn, int n, const double* a, const double* b, do
     out[i] = r;
 }
 
+// hope_debug_geom: the geometry primitives of hope_dev.h / hope_step_kernel.h on packed test cases, called the way the step kernels
+// call them.  One 64-lane wave per block.  REC doubles per case in; int32 (fn 0-5, 9) or float64 (fn 6-8) out.  fn 1, 2, 4: the 64
+// lanes hold 64 cases and take the ONE work area xl one lane at a time (the loop of k_env_step's multi-sub-step pass); fn 5, 6: one
+// case per block; fn 7: the lanes clip CLIP_COLS cases at a time in the column layout (the loop of k_post).
+constexpr int DEBUG_GEOM_FNS = 10, DEBUG_GEOM_MAX_OBST = 32;
+__host__ __device__ inline int debug_geom_rec(int fn, int n_obst) {
+    return fn <= 2 ? 6 : (fn == 3 || fn == 4 || fn == 9) ? 8 : (fn == 5 ? 4 + 8 * n_obst : (fn == 8 ? 4 : 16));
+}
+template <int FN>
+__global__ __launch_bounds__(64) void k_debug_geom(int n, int n_obst, const double* in, void* out) {
+    __shared__ double xl[ROBUST_LDS_WORDS];
+    const int lane = threadIdx.x;
+    int32_t* oi = (int32_t*)out;
+    double* od = (double*)out;
+    if (FN == 5) {                                              // detect_collision by the whole wave: block = case
+        __shared__ double tile[8 * DEBUG_GEOM_MAX_OBST];
+        __shared__ int list[DEBUG_GEOM_MAX_OBST];
+        const int c = blockIdx.x;
+        if (c >= n || n_obst > DEBUG_GEOM_MAX_OBST) return;
+        const double* v = in + (size_t)c * debug_geom_rec(5, n_obst);
+        for (int i = lane; i < 8 * n_obst; i += WAVE) tile[i] = v[4 + i];
+        for (int i = lane; i < n_obst; i += WAVE) list[i] = i;
+        __syncthreads();
+        unsigned und = 0;
+        const bool hit = detect_collision(v[0], v[1], v[2], v[3], tile, list, n_obst, xl, lane, &und);
+        if (lane == 0) { oi[2 * c] = hit; oi[2 * c + 1] = (int32_t)und; }
+        return;
+    }
+    if (FN == 6) {                                              // the one-lane clip: block = case, operands in LDS as in overlap_area
+        __shared__ double sh[64];
+        __shared__ double dbox[8];
+        const int c = blockIdx.x;
+        if (c >= n) return;
+        const double* v = in + (size_t)c * 16;
+        if (lane < 8) dbox[lane] = v[8 + lane];
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) { sh[i] = v[2 * i]; sh[16 + i] = v[2 * i + 1]; }
+            od[c] = quad_intersection_area_lane0(dbox, sh);
+        }
+        return;
+    }
+    const int i = blockIdx.x * WAVE + lane;
+    const bool live = i < n;
+    const double* v = in + (size_t)(live ? i : 0) * debug_geom_rec(FN, 0);
+    if (FN == 7) {                                              // the column clip, CLIP_COLS lanes at a time (k_post's loop)
+        __shared__ double clip_lds[32 * CLIP_COLS];
+        double area = 0.0;
+        unsigned long long cm = __ballot(live);
+        while (cm) {
+            const int rank = __popcll(cm & ((1ull << lane) - 1));
+            const bool mine = live && ((cm >> lane) & 1) && rank < CLIP_COLS;
+            if (mine) {
+                double* sh = clip_lds + rank;
+#pragma unroll
+                for (int k = 0; k < 4; k++) { sh[k * CLIP_COLS] = v[2 * k]; sh[(8 + k) * CLIP_COLS] = v[2 * k + 1]; }
+                area = quad_intersection_area_private(v + 8, sh);
+            }
+            unsigned long long served = 0;
+            {
+                unsigned long long t_ = cm;
+                for (int k = 0; k < CLIP_COLS && t_; k++) { served |= t_ & (~t_ + 1); t_ &= t_ - 1; }
+            }
+            cm &= ~served;
+            __syncthreads();
+        }
+        if (live) od[i] = area;
+        return;
+    }
+    if (FN == 1 || FN == 2 || FN == 4) {                        // one lane at a time in the shared work area
+        int r = 0;
+        unsigned long long um = __ballot(live);
+        while (um) {
+            const int l = __ffsll((long long)um) - 1;
+            um &= um - 1;
+            if (lane == l) {
+                if (FN == 1) r = orient_exact_lds(v[0], v[1], v[2], v[3], v[4], v[5], xl + 12);
+                if (FN == 2) r = orient_robust_lds(v[0], v[1], v[2], v[3], v[4], v[5], xl + 12);
+                if (FN == 4) r = hull_edge_intersect_robust(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], xl);
+            }
+        }
+        if (live) oi[i] = r;
+        return;
+    }
+    if (!live) return;
+    if (FN == 0) oi[i] = orient_filter(v[0], v[1], v[2], v[3], v[4], v[5]);
+    if (FN == 3) oi[i] = segments_intersect_fast(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+    if (FN == 8) od[i] = origin_seg_dist(v[0], v[1], v[2], v[3]);
+    if (FN == 9) oi[i] = arrival_possible(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+}
+
 // Calibration of the memory-side traffic counters (FETCH_SIZE / WRITE_SIZE) on THIS library's access widths: a grid-stride sweep
 // over a buffer far larger than the 256 MiB Infinity Cache, with a known byte count (tools/pmc_calib.py).  MODE: reads 0 = 16 B per
 // lane (the obstacle tile copies; the guide's calibrated case), 1 = 8 B per lane (kin / post / table rows), 2 = 4 B per lane, 3 = one
@@ -2671,6 +2763,30 @@ int hope_debug_math(int fn, int n, const double* a, const double* b, double* out
     if (n < 0 || !a || !out) return fail(HOPE_EINVAL, "hope_debug_math: bad argument");
     if (n == 0) return HOPE_OK;
     hipLaunchKernelGGL(k_debug_math, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, fn, n, a, b, out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_debug_geom(int fn, int n, int n_obst, const double* in, void* out, void* stream) {
+    if (n < 0 || !in || !out) return fail(HOPE_EINVAL, "hope_debug_geom: bad argument");
+    if (fn < 0 || fn >= DEBUG_GEOM_FNS) return fail(HOPE_EINVAL, "hope_debug_geom: unknown fn " + std::to_string(fn));
+    if (fn == 5 && (n_obst < 0 || n_obst > DEBUG_GEOM_MAX_OBST))
+        return fail(HOPE_EINVAL, "hope_debug_geom: n_obst " + std::to_string(n_obst) + " outside 0.." + std::to_string(DEBUG_GEOM_MAX_OBST));
+    if (n == 0) return HOPE_OK;
+    const dim3 g(fn == 5 || fn == 6 ? n : (n + WAVE - 1) / WAVE), b(WAVE);
+    hipStream_t s = (hipStream_t)stream;
+    switch (fn) {
+        case 0: hipLaunchKernelGGL((k_debug_geom<0>), g, b, 0, s, n, n_obst, in, out); break;
+        case 1: hipLaunchKernelGGL((k_debug_geom<1>), g, b, 0, s, n, n_obst, in, out); break;
+        case 2: hipLaunchKernelGGL((k_debug_geom<2>), g, b, 0, s, n, n_obst, in, out); break;
+        case 3: hipLaunchKernelGGL((k_debug_geom<3>), g, b, 0, s, n, n_obst, in, out); break;
+        case 4: hipLaunchKernelGGL((k_debug_geom<4>), g, b, 0, s, n, n_obst, in, out); break;
+        case 5: hipLaunchKernelGGL((k_debug_geom<5>), g, b, 0, s, n, n_obst, in, out); break;
+        case 6: hipLaunchKernelGGL((k_debug_geom<6>), g, b, 0, s, n, n_obst, in, out); break;
+        case 7: hipLaunchKernelGGL((k_debug_geom<7>), g, b, 0, s, n, n_obst, in, out); break;
+        case 8: hipLaunchKernelGGL((k_debug_geom<8>), g, b, 0, s, n, n_obst, in, out); break;
+        default: hipLaunchKernelGGL((k_debug_geom<9>), g, b, 0, s, n, n_obst, in, out); break;
+    }
     HIPCHK(hipGetLastError());
     return HOPE_OK;
 }

@@ -354,6 +354,25 @@ int hope_env_upload_state(hope_env_t *h, const double *pose, const int32_t *t, c
  * from IEEE-exact operations only, so the results must equal the host evaluation bit for bit. */
 int hope_debug_math(int fn, int n, const double *a, const double *b, double *out, void *stream);
 
+/* Test hook for the geometry primitives behind the collision, arrival and ring-cull decisions (hope_amd/csrc/hope_dev.h,
+ * hope_step_kernel.h): runs the shipped inline function itself on n packed cases on the DEVICE, one 64-lane wave per block, in the
+ * calling pattern of the step kernels.  `in`: DEVICE pointer, the cases' float64 records back to back; `out`: DEVICE pointer, int32
+ * (fn 0-5, 9) or float64 (fn 6-8), one value per case (fn 5: two).
+ *   fn 0 orient_filter             a b c (6)                        -> -1 / 0 / 1, 2 = undecided
+ *   fn 1 orient_exact_lds          a b c (6), the expansion on EVERY case -> sign
+ *   fn 2 orient_robust_lds         a b c (6)                        -> sign
+ *   fn 3 segments_intersect_fast   p1 p2 q1 q2 (8)                  -> 0 / 1, 2 = undecided
+ *   fn 4 hull_edge_intersect_robust  pose x, y, cos, sin, edge x1 y1 x2 y2 (8) -> 0 / 1
+ *   fn 5 detect_collision          pose x, y, cos, sin, n_obst quads (4 + 8 n_obst); the whole wave, one block per case, quads staged
+ *                                  to an LDS tile with the identity list -> hit, number of lanes the filter left undecided
+ *   fn 6 quad_intersection_area_lane0    quad A, quad B (16)        -> area
+ *   fn 7 quad_intersection_area_private  quad A, quad B (16), 16 lanes clipping 16 cases at a time in k_post's column layout -> area
+ *   fn 8 origin_seg_dist           a b (4)                          -> distance
+ *   fn 9 arrival_possible          x, y, cos, sin, dest centre x, y, cos, sin of the dest heading (8) -> 0 / 1
+ * fn 1, 2 and 4 give the single LDS work area to the 64 cases of a block one lane after the other, as the step kernels do.
+ * n_obst is read by fn 5 only (0..32).  HOPE_EINVAL for n < 0, a null pointer, an unknown fn, n_obst out of range.  Additive to ABI 8. */
+int hope_debug_geom(int fn, int n, int n_obst, const double *in, void *out, void *stream);
+
 /* Test hook (pure host code, no device needed): the count-interval table hope_env_upload_tables derives from dist_star / hull_base for
  * the action-mask stage (hope_amd/csrc/hope_step_kernel.h MASK_LUT_*): lut_out [(120 * 128 + 1)][32] uint16, scale_out [120] bins per
  * metre.  tests/test_mask_lut.py checks its bracketing property against the float64 table (action_mask.py:166-177). */

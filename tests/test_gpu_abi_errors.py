@@ -89,7 +89,7 @@ def test_create_rejects_bad_arguments_and_removed_flags():
 @pytest.mark.parametrize('case', ['step_before_tables', 'step_before_scenes', 'n_obst_too_large', 'scene_id_out_of_range', 'null_arrays',
                                   'img_without_flag', 'redraw_without_reset', 'redraw_without_pool', 'pool_without_class', 'null_out',
                                   'null_actions', 'profile_without_flag', 'stale_wait_rs_step', 'null_masks', 'commit_beyond_staging',
-                                  'bad_draw_class', 'restore_without_pool'])
+                                  'bad_draw_class', 'restore_without_pool', 'debug_geom_bad_arguments'])
 def test_misuse_returns_its_code_and_leaves_the_handle_usable(case):
     lib = _lib()
     arrays = _scene_arrays()
@@ -204,6 +204,18 @@ def test_misuse_returns_its_code_and_leaves_the_handle_usable(case):
         ep = np.zeros(N, np.uint32)
         assert lib.hope_env_restore_maps(h, drawn.ctypes.data, ep.ctypes.data, 0, 0) == ESTATE
         assert lib.hope_env_restore_maps(h, None, ep.ctypes.data, 0, 0) == EINVAL
+    elif case == 'debug_geom_bad_arguments':
+        a = torch.zeros(4 + 8 * 33, dtype=torch.float64, device='cuda:0')
+        o = torch.zeros(2, dtype=torch.int32, device='cuda:0')
+        pa, po = C.c_void_p(a.data_ptr()), C.c_void_p(o.data_ptr())
+        assert lib.hope_debug_geom(0, -1, 0, pa, po, None) == EINVAL
+        assert lib.hope_debug_geom(0, 1, 0, None, po, None) == EINVAL
+        assert lib.hope_debug_geom(0, 1, 0, pa, None, None) == EINVAL
+        assert lib.hope_debug_geom(10, 1, 0, pa, po, None) == EINVAL and 'unknown fn' in _err()
+        assert lib.hope_debug_geom(-1, 1, 0, pa, po, None) == EINVAL
+        assert lib.hope_debug_geom(5, 1, 33, pa, po, None) == EINVAL and 'n_obst' in _err()
+        assert lib.hope_debug_geom(5, 1, -1, pa, po, None) == EINVAL
+        assert lib.hope_debug_geom(5, 0, 32, pa, po, None) == OK                                 # (no case: nothing is launched)
 
     # ---- the handle still works: its next steps equal a fresh twin's -------------------------------------------------------------
     if case == 'pool_without_class':
