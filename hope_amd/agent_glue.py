@@ -175,6 +175,89 @@ class DeviceRsPlanner:
                                env.done if done is None else done, self._L.PLAN_FORCED if forced else 0)
 
 
+class DeviceActionChooser:
+    """The block of `_AgentCommon.act` from choose_action to gaussian_log_prob as ONE k_choose launch (include/hope_env.h "masked
+    choice of the discrete action"; rule: csrc/hope_chooser_core.h): mask-weighted draw, cast, clamp, the planner's override and the
+    log-probability of the action taken.  Draws are counter-based, keyed by (seed, call number, scene): this object keeps the
+    counter, so a run is reproduced by its seed and resumed by restoring `counter`.  They are NOT torch.multinomial's stream.
+    On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same choice runs on the host through
+    hope_chooser_host: the rule is one source for both."""
+
+    def __init__(self, env, seed=0):
+        self.env, self.n, self.seed, self.counter = env, env.n, int(seed) & (2 ** 64 - 1), 0
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'choose_actions')
+        self.action_env = None                        # the last choice in the env's action dtype: what env.step takes
+        if self.on_device:
+            env.enable_chooser()
+        else:
+            import numpy as np
+            from . import _lib as L
+            assert self.device.type == 'cpu', 'an env without choose_actions must hold CPU tensors'
+            self._L, self._lib = L, L.load_library()
+            self._acts = np.ascontiguousarray(T.discrete_actions() / [T.VALID_STEER[1], 1.0], dtype=np.float64)
+            self._adt = getattr(env, 'action_dtype', torch.float32)
+            self._a32 = torch.zeros((self.n, 2), dtype=torch.float32)
+            self._a = self._a32 if self._adt == torch.float32 else torch.zeros((self.n, 2), dtype=torch.float64)
+            self._idx = torch.zeros(self.n, dtype=torch.int32)
+            self._lp = torch.zeros((self.n, 2), dtype=torch.float32)
+
+    def _host(self, mean, log_std, mask, planned, executing, u):
+        assert mean.dtype in (torch.float32, torch.float64) and mean.shape == (self.n, 2)
+        mean = mean.contiguous()
+        log_std = log_std.to(mean.dtype).contiguous()
+        assert log_std.shape in ((self.n, 2), (1, 2))
+        if mask.dtype not in (torch.float32, torch.float64):
+            mask = mask.to(torch.float32)
+        mask = mask.contiguous()
+        assert mask.shape == (self.n, 42)
+        pp = ep = up = None
+        if planned is not None:
+            planned = planned.to(torch.float64).contiguous()
+            executing = executing.to(torch.uint8).contiguous()
+            pp, ep = planned.data_ptr(), executing.data_ptr()
+        if u is not None:
+            u = u.to(torch.float64).contiguous()
+            up = u.data_ptr()
+        self._L.check(self._lib.hope_chooser_host(self.n, self._acts.ctypes.data, mean.data_ptr(), log_std.data_ptr(),
+                                                  2 if log_std.shape[0] == self.n and self.n > 1 else 0, int(mean.dtype == torch.float64),
+                                                  mask.data_ptr(), int(mask.dtype == torch.float64), pp, ep, up, self.seed, self.counter, 0,
+                                                  self._a.data_ptr(), int(self._adt == torch.float64), self._a32.data_ptr(), self._idx.data_ptr(),
+                                                  self._lp.data_ptr(), None), 'hope_chooser_host')
+        return self._a, self._a32, self._idx, self._lp
+
+    def choose(self, mean, log_std, mask, planned=None, executing=None, u=None):
+        """mean [N, 2]; log_std [N, 2] or the agents' [1, 2] parameter (an expanded view of it is taken back to one row); mask
+        [N, 42]; planned / executing: the planner's outputs or None.  -> (action_f32 [N, 2], log_prob f32 [N, 2], action of the env's
+        action dtype): persistent tensors, overwritten by the next call.  Advances the counter."""
+        if log_std.dim() == 2 and log_std.shape[0] == self.n and self.n > 1 and log_std.stride(0) == 0:
+            log_std = log_std[:1]
+        if self.on_device:
+            env = self.env
+            mean = mean.contiguous()
+            log_std = log_std.to(mean.dtype).contiguous()
+            if mask.dtype != env.obs_dtype:
+                mask = mask.to(env.obs_dtype)
+            if planned is not None and planned.dtype != torch.float64:
+                planned = planned.to(torch.float64)
+            a, a32, self.idx, lp = env.choose_actions(mean, log_std, mask.contiguous(), None if planned is None else planned.contiguous(),
+                                                      None if executing is None else executing.contiguous(), u, self.seed, self.counter)
+        else:
+            a, a32, self.idx, lp = self._host(mean, log_std, mask, planned, executing, u)
+        self.counter += 1
+        self.action_env = a
+        return a32, lp, a
+
+
+def make_chooser(chooser, env, seed=0):
+    """the loops' `chooser` argument: None (today's torch path), 'device', or a DeviceActionChooser"""
+    if chooser is None or isinstance(chooser, DeviceActionChooser):
+        return chooser
+    if chooser == 'device':
+        return DeviceActionChooser(env, seed)
+    raise ValueError(f"chooser must be None, 'device' or a DeviceActionChooser, not {chooser!r}")
+
+
 _ACTIONS = None
 
 

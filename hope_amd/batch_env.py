@@ -428,6 +428,66 @@ class ParkingBatch:
         L.check(self.lib.hope_env_planner_download_state(self.h, out.ctypes.data), 'hope_env_planner_download_state')
         return out
 
+    # -- masked choice of the discrete action on the device (hope_env.h; rule: csrc/hope_chooser_core.h) -----------------
+    def enable_chooser(self):
+        """ActionMask.choose_action + the agent's cast / clamp / planner override / log-probability as one kernel (k_choose).
+        Uploads the 42 x 2 action table in the policy's scaling (numpy's own bits).  Off by default."""
+        torch.cuda.synchronize(self.device)
+        acts = np.ascontiguousarray(T.discrete_actions() / [T.VALID_STEER[1], 1.0], dtype=np.float64)
+        L.check(self.lib.hope_env_chooser_enable(self.h, acts.ctypes.data), 'hope_env_chooser_enable')
+        if getattr(self, 'chosen_action', None) is None:
+            dev = self.device
+            self.chosen_action_f32 = torch.zeros((self.n, 2), dtype=torch.float32, device=dev)
+            # a float32 env steps with the very tensor the transition ring stores
+            self.chosen_action = self.chosen_action_f32 if self.action_dtype == torch.float32 else torch.zeros((self.n, 2), dtype=torch.float64, device=dev)
+            self.chosen_idx = torch.zeros(self.n, dtype=torch.int32, device=dev)
+            self.chosen_log_prob = torch.zeros((self.n, 2), dtype=torch.float32, device=dev)
+            self.chosen_probs = None                      # [N, 42] float64, allocated by the first call that asks for it
+        return self
+
+    def disable_chooser(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_chooser_disable(self.h), 'hope_env_chooser_disable')
+        return self
+
+    def choose_actions(self, mean, log_std, mask=None, planned=None, executing=None, u=None, seed=0, counter=0, probs=False):
+        """one k_choose launch on the current stream, no host synchronisation, no wait for a deferred search (planner_step does that).
+        mean [N, 2] and log_std [N, 2] or [1, 2] (broadcast): both float32 or both float64; mask [N, 42] of the env's observation
+        dtype (None: the env's own action_mask); planned f64 [N, 2] + executing bool / u8 [N] (planner_step's outputs): those rows
+        take the planned action; u f64 [N] in [0, 1) or None: counter-based draws keyed by (seed, counter, scene).
+        -> (action [N, 2] of the env's action dtype, contiguous: goes straight into step(); action_f32 [N, 2]; idx int32 [N], index |
+        CHOOSE_NOMASK / CHOOSE_FIXED on a degenerate row; log_prob f32 [N, 2][; probs f64 [N, 42]]): persistent tensors of this
+        object, overwritten by the next call."""
+        n, dev = self.n, self.device
+        mask = self.action_mask if mask is None else mask
+        assert mean.dtype in (torch.float32, torch.float64) and log_std.dtype == mean.dtype
+        assert mean.shape == (n, 2) and mean.device == dev and mean.is_contiguous()
+        assert log_std.shape in ((n, 2), (1, 2)) and log_std.device == dev and log_std.is_contiguous()
+        assert mask.dtype == self.obs_dtype and mask.shape == (n, 42) and mask.device == dev and mask.is_contiguous()
+        assert (planned is None) == (executing is None), 'planned and executing go together'
+        pp = ep = up = None
+        if planned is not None:
+            assert planned.dtype == torch.float64 and planned.shape == (n, 2) and planned.device == dev and planned.is_contiguous()
+            assert executing.dtype in (torch.bool, torch.uint8) and executing.shape == (n,) and executing.device == dev and executing.is_contiguous()
+            pp, ep = C.c_void_p(planned.data_ptr()), C.c_void_p(executing.data_ptr())
+        if u is not None:
+            assert u.dtype == torch.float64 and u.shape == (n,) and u.device == dev and u.is_contiguous()
+            up = C.c_void_p(u.data_ptr())
+        if getattr(self, 'chosen_action', None) is None:  # (the library then reports that the chooser is off)
+            ap = fp = ip = lp = qp = None
+        else:
+            if probs and self.chosen_probs is None:
+                self.chosen_probs = torch.zeros((n, 42), dtype=torch.float64, device=dev)
+            ap, fp = C.c_void_p(self.chosen_action.data_ptr()), C.c_void_p(self.chosen_action_f32.data_ptr())
+            ip, lp = C.c_void_p(self.chosen_idx.data_ptr()), C.c_void_p(self.chosen_log_prob.data_ptr())
+            qp = C.c_void_p(self.chosen_probs.data_ptr()) if probs else None
+        L.check(self.lib.hope_env_choose(self.h, C.c_void_p(mean.data_ptr()), C.c_void_p(log_std.data_ptr()), 2 if log_std.shape[0] == n and n > 1 else 0,
+                                         int(mean.dtype == torch.float64), C.c_void_p(mask.data_ptr()), pp, ep, up,
+                                         C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), ap, fp, ip, lp, qp,
+                                         self._stream()), 'hope_env_choose')
+        out = (self.chosen_action, self.chosen_action_f32, self.chosen_idx, self.chosen_log_prob)
+        return out + (self.chosen_probs,) if probs else out
+
     def queue_check(self):
         """hope_env_create's measurement of which library streams share a hardware queue (hope_env_queue_check):
         {'queue_of_role': [8 ints, [0] = the NULL stream], 'distinct_queues': n, 'roles_shared': pairs of roles busy in the same step

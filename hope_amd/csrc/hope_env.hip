@@ -21,6 +21,7 @@
 #include "hope_curriculum_kernel.h"
 #include "hope_maplevel_kernel.h"
 #include "hope_planner_kernel.h"
+#include "hope_chooser_kernel.h"
 
 using namespace hope;
 
@@ -193,6 +194,8 @@ struct hope_env {
     int draw_set = -1;                                      // pool set the last step / hope_env_redraw drew from
     // replay of found Reeds-Shepp paths (hope_planner_kernel.h): [PL_WORDS][n] state words, nullptr while the planner is off
     struct Planner { bool on = false; double step_ratio = HOPE_PLAN_STEP_RATIO; uint64_t* state = nullptr; } plan;
+    // masked choice of the discrete action (hope_chooser_kernel.h): the [42][2] action table, nullptr while the chooser is off
+    struct Chooser { bool on = false; double* actions = nullptr; } choose;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -678,6 +681,7 @@ int hope_abi_version(void) { return HOPE_ABI_VERSION; }
 static int destroy_impl(hope_env_t* h);
 static void cur_free(hope_env_t* h);
 static void plan_free(hope_env_t* h);
+static void choose_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -942,6 +946,7 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     for (hipEvent_t e : h->free_events) hipEventDestroy(e);
     cur_free(h);
     plan_free(h);
+    choose_free(h);
     for (auto& ps : h->pset) for (void* q : {(void*)ps.label, (void*)ps.sorted_own[0], (void*)ps.sorted_own[1]}) if (q) hipFree(q);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
@@ -1105,6 +1110,81 @@ int hope_env_planner_download_state(hope_env_t* h, void* state_out) {
     if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(state_out, h->plan.state, (size_t)PL_WORDS * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+// ---- masked choice of the discrete action (include/hope_env.h; kernel: hope_chooser_kernel.h, rule: hope_chooser_core.h) ----
+static void choose_free(hope_env_t* h) {
+    if (h->choose.actions) hipFree(h->choose.actions);
+    h->choose = hope_env::Chooser{};
+}
+
+int hope_env_chooser_enable(hope_env_t* h, const double* actions) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_chooser_enable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_chooser_enable: not a live handle (destroyed?)");
+    if (!actions) return fail(HOPE_EINVAL, "hope_env_chooser_enable: null action table");
+    if (!ch_table_ok(actions))
+        return fail(HOPE_EINVAL, "hope_env_chooser_enable: the action table must be finite, rows 0..20 at one speed and rows 21..41 the same steers at another");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());                         // choices in flight read the table
+    const size_t bytes = (size_t)CH_NA * 2 * sizeof(double);
+    if (!h->choose.actions) {
+        hipError_t e_ = hipMalloc((void**)&h->choose.actions, bytes);
+        if (e_ != hipSuccess) { h->choose.actions = nullptr; return fail(HOPE_ENOMEM, std::string("hope_env_chooser_enable: ") + hipGetErrorString(e_)); }
+    }
+    HIPCHK(hipMemcpy(h->choose.actions, actions, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    h->choose.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_chooser_disable(hope_env_t* h) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_chooser_disable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_chooser_disable: not a live handle (destroyed?)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    choose_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_choose(hope_env_t* h, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, const double* planned,
+                    const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, void* action, float* action_f32, int32_t* idx,
+                    float* log_prob, double* probs, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_choose: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_choose: not a live handle (destroyed?)");
+    if (!h->choose.on) return fail(HOPE_ESTATE, "hope_env_choose: the chooser is off (hope_env_chooser_enable first)");
+    if (!mean || !log_std || !mask || !action) return fail(HOPE_EINVAL, "hope_env_choose: null mean / log_std / mask / action");
+    if ((planned != nullptr) != (executing != nullptr)) return fail(HOPE_EINVAL, "hope_env_choose: planned and executing go together");
+    if (log_std_row_stride != 0 && log_std_row_stride != 2) return fail(HOPE_EINVAL, "hope_env_choose: log_std_row_stride is 0 (one row for all) or 2");
+    const bool mf64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
+    if (((uintptr_t)mean & (in_f64 ? 15 : 7)) || ((uintptr_t)log_std & (in_f64 ? 7 : 3)) || ((uintptr_t)mask & (mf64 ? 7 : 3)) || ((uintptr_t)planned & 15) ||
+        ((uintptr_t)u & 7) || ((uintptr_t)action & (af64 ? 15 : 7)) || ((uintptr_t)action_f32 & 7) || ((uintptr_t)idx & 3) || ((uintptr_t)log_prob & 7) ||
+        ((uintptr_t)probs & 7))
+        return fail(HOPE_EINVAL, "hope_env_choose: misaligned buffer (mean and action rows 8 / 16, planned 16, action_f32 and log_prob 8 bytes, the others their element)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (mf64)
+        hipLaunchKernelGGL(k_choose<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
+                           in_f64 ? 1 : 0, (const double*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
+                           (int*)idx, (float2*)log_prob, probs);
+    else
+        hipLaunchKernelGGL(k_choose<float>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
+                           in_f64 ? 1 : 0, (const float*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
+                           (int*)idx, (float2*)log_prob, probs);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_chooser_host(int n, const double* actions, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, int mask_f64,
+                      const double* planned, const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, uint64_t scene0, void* action,
+                      int action_f64, float* action_f32, int32_t* idx, float* log_prob, double* probs) {
+    const int rc = ch_host(n, actions, mean, log_std, log_std_row_stride, in_f64, mask, mask_f64, planned, executing, u, seed, counter, scene0, action, action_f64,
+                           action_f32, idx, log_prob, probs);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_chooser_host: bad argument (n <= 0, a null actions / mean / log_std / mask / action, planned without executing or the reverse, a stride other than 0 / 2, or an action table that is not 21 steers x 2 speeds)");
     return HOPE_OK;
 }
 

@@ -23,10 +23,14 @@ TOLERANT_TIME = 200
 
 
 class BatchedEvaluator:
-    def __init__(self, env, agent, post_proc_action=True, use_planner=True, seed=0):
+    def __init__(self, env, agent, post_proc_action=True, use_planner=True, seed=0, chooser=None):
         """agent: a hope_amd.agents agent (`act(obs, use_mask, generator, planned, executing)`); post_proc_action: PPO's
-        mask-weighted choose_action (eval_utils.py:42-43) instead of the plain sample (:44-45)."""
+        mask-weighted choose_action (eval_utils.py:42-43) instead of the plain sample (:44-45).
+        chooser: None, or 'device' -- with post_proc_action the choice, the planner's override and the log-probability are one
+        k_choose launch per step (agent_glue.DeviceActionChooser; counter-based draws keyed by `seed`).  The stuck detector's
+        random action is applied after it, as before."""
         self.env, self.agent, self.use_mask = env, agent, bool(post_proc_action)
+        self.chooser = G.make_chooser(chooser, env, seed)
         if use_planner == 'device':          # the library's planner: one k_plan launch per step (agent_glue.DeviceRsPlanner)
             self.planner = G.DeviceRsPlanner(env)
         else:
@@ -75,7 +79,7 @@ class BatchedEvaluator:
                 planned, executing = self.planner.step(*pending)
             else:
                 planned, executing = self.planner.get_actions() if self.planner is not None else (None, None)
-            action, _, _ = agent.act(self._obs(), self.use_mask, self.gen, planned, executing)
+            action, _, _ = agent.act(self._obs(), self.use_mask, self.gen, planned, executing, chooser=self.chooser)
             # stuck detector (:46-47): the very first comparison is obs['target'] with itself -> always a random first action
             same = torch.ones(n, dtype=torch.bool, device=dev) if first else (env.target == last_target).all(dim=1)
             first = False

@@ -135,7 +135,7 @@ class TransitionRing:
 
 class HopeRollout:
     def __init__(self, env, agent, horizon, use_mask=True, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None,
-                 defer_rs=True, curriculum=None):
+                 defer_rs=True, curriculum=None, chooser=None):
         """defer_rs: step the env with two completion points (HOPE_DEFER_RS): the next policy forward is enqueued as soon as the
         observation is written, the planner reads rs_word / rs_lengths (after ParkingBatch.wait_rs) just before its override --
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
@@ -151,7 +151,12 @@ class HopeRollout:
         curriculum: None, or dict(update_every=K, **rule parameters) -- the reference's SceneChoose / DlpCaseChoose
         (train_HOPE_sac.py:23-97) on the device: the env tallies every finished episode's outcome per scene type / Dragon-Lake case
         after each step and rebuilds its weighted draw lists every K steps (hope_amd.curriculum.CurriculumDriver); needs
-        fresh_scenes (ValueError without).  Measured cost at 65 536 scenes: ~8 % per step.  None: no call at all."""
+        fresh_scenes (ValueError without).  Measured cost at 65 536 scenes: ~8 % per step.  None: no call at all.
+        chooser: None -- the mask-weighted sampling, the planner's override and the log-probability are torch code (agent_glue.
+        choose_action, torch.multinomial); 'device' -- one k_choose launch per step (agent_glue.DeviceActionChooser; counter-based
+        draws keyed by `seed`, not torch.multinomial's stream), whose env-typed action tensor goes straight into the step.  Used
+        where the mask is (use_mask); the plain Gaussian sample and the uniform exploration are not its business."""
+        self.chooser = G.make_chooser(chooser, env, seed)
         self.curriculum = None
         if curriculum is not None:
             if not fresh_scenes:
@@ -222,7 +227,7 @@ class HopeRollout:
             planned, executing = self._plan()
             action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, planned, executing)
         else:
-            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, plan_fn=self._plan)
+            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, plan_fn=self._plan, chooser=self.chooser)
         if random_action:                             # train_HOPE_sac.py:196-198: uniform exploration while the memory fills
             rnd = torch.rand(action.shape, device=action.device, generator=self.gen) * 2 - 1
             action = rnd if executing is None else torch.where(executing.unsqueeze(1), action, rnd)
@@ -231,10 +236,14 @@ class HopeRollout:
             log_prob = gaussian_log_prob(mean, agent.log_std.expand_as(mean), action)
         self.ring.write_before(nobs, action, log_prob)              # copies: env.step overwrites the buffers in place
         kw = {'defer_rs': True} if self.defer_rs else {}
-        if self.fresh:                                # new map per episode, drawn inside the step kernel (HOPE_AUTO_REDRAW)
-            env.step(action.to(env.action_dtype).contiguous(), auto_reset=True, fresh=True, **kw)
+        if self.chooser is not None and self.use_mask and not random_action:
+            step_action = self.chooser.action_env     # the chooser's own tensor in the env's action dtype, contiguous
         else:
-            env.step(action.to(env.action_dtype).contiguous(), auto_reset=True, **kw)
+            step_action = action.to(env.action_dtype).contiguous()
+        if self.fresh:                                # new map per episode, drawn inside the step kernel (HOPE_AUTO_REDRAW)
+            env.step(step_action, auto_reset=True, fresh=True, **kw)
+        else:
+            env.step(step_action, auto_reset=True, **kw)
         if self.curriculum is not None:               # update_success_record (:215-225), and every K steps the new draw weights
             self.curriculum.after_step()
         self.ring.write_after(env.reward, env.done)
@@ -265,13 +274,13 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None):
+                 curriculum=None, chooser=None):
         """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update"""
         self._curriculum_per_update = curriculum is not None and 'update_every' not in curriculum
         if self._curriculum_per_update:
             curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser)
         self.updates = 0
 
     def step(self):
@@ -294,9 +303,10 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True, curriculum=None):
+                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None):
+        """chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used"""
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

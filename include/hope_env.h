@@ -610,6 +610,46 @@ int hope_planner_step_host(int n, double step_ratio, void *state, const int8_t *
 /* the state block as the next planner step will read it (host array of HOPE_PLAN_STATE_WORDS * N 8-byte words); host-synchronous */
 int hope_env_planner_download_state(hope_env_t *h, void *state_out);
 
+/* ---- masked choice of the discrete action (additive to ABI 8) -------------------------------------------------------------------
+ * The reference's ActionMask.choose_action (src/model/action_mask.py:199-227) as one kernel, k_choose, behind the policy forward:
+ * the Gaussian head's density at the 42 discrete actions, weighed with the action mask, one draw per scene, the cast / clamp / path
+ * replay override of the agent (parking_agent.py:80-99) and the log-probability of the action taken -- two numbers per scene out of
+ * one launch.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule, the
+ * treatment of degenerate rows and the bit-equal host twin: hope_amd/csrc/hope_chooser_core.h, DESIGN.md 5f. */
+/* flag bits of the index output; idx & 63 is always a legal action index */
+#define HOPE_CHOOSE_NOMASK 64       /* the row's mask was unusable (sum of weights not positive / not finite): drawn with every mask = 1 */
+#define HOPE_CHOOSE_FIXED 128       /* still unusable, or a non-finite mean / log_std: index 10 (straight ahead) was taken */
+/* upload the action table: HOST float64 [42][2] in the policy's [-1, 1] scaling, rows 0 .. 20 the 21 steers at one speed, rows
+ * 21 .. 41 the same steers at the other (HOPE_EINVAL otherwise).  Enabling again replaces the table.  Host-synchronous. */
+int hope_env_chooser_enable(hope_env_t *h, const double *actions);
+/* free the table.  Host-synchronous (choices in flight read it). */
+int hope_env_chooser_disable(hope_env_t *h);
+/* k_choose, asynchronous on `stream`; waits for nothing and never synchronises the host -- it does not join a deferred search
+ * (hope_env_planner_step / hope_env_wait_rs do; call them first when planned / executing come from that step).  DEVICE buffers, N =
+ * the handle's scenes:
+ *   mean [N][2], log_std     float32, or float64 with in_f64 != 0; mean aligned to a row (8 / 16 bytes).  log_std_row_stride: 2 for
+ *                            [N][2], 0 to broadcast one row
+ *   mask [N][42]             the handle's observation type (hope_step_out.action_mask); required
+ *   planned f64 [N][2] (16-byte aligned), executing u8 [N]: both or neither (hope_env_planner_step's outputs); rows with
+ *                            executing != 0 take (float)planned
+ *   u f64 [N] in [0, 1)      or NULL: the draw of scene s is then the counter-based uniform of (seed, counter, s)
+ *   action [N][2]            the handle's action type (float64 iff HOPE_F_ACTION_F64: (double) of the float32 value); required;
+ *                            8- / 16-byte aligned
+ *   action_f32 f32 [N][2], idx i32 [N] (index | HOPE_CHOOSE_* bits), log_prob f32 [N][2], probs f64 [N][42] (= e_k / S): each may
+ *                            be NULL; action_f32 may be `action` itself on a float32 handle
+ * HOPE_ESTATE before hope_env_chooser_enable; HOPE_EINVAL for a NULL mean / log_std / mask / action, planned without executing or
+ * the reverse, a stride other than 0 / 2, a misaligned buffer. */
+int hope_env_choose(hope_env_t *h, const void *mean, const void *log_std, int log_std_row_stride, int in_f64, const void *mask,
+                    const double *planned, const uint8_t *executing, const double *u, uint64_t seed, uint64_t counter, void *action,
+                    float *action_f32, int32_t *idx, float *log_prob, double *probs, void *stream);
+/* The same choice over HOST arrays of n scenes: pure host code from the same source, no handle, no device.  Bit-equal to k_choose.
+ * mask_f64 / action_f64: the types the handle's flags give on the device.  scene0: the index of row 0 in the counter-based draw, so
+ * that a batch may be split.  No alignment requirements. */
+int hope_chooser_host(int n, const double *actions, const void *mean, const void *log_std, int log_std_row_stride, int in_f64,
+                      const void *mask, int mask_f64, const double *planned, const uint8_t *executing, const double *u, uint64_t seed,
+                      uint64_t counter, uint64_t scene0, void *action, int action_f64, float *action_f32, int32_t *idx, float *log_prob,
+                      double *probs);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
