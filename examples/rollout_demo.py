@@ -34,6 +34,9 @@ def main():
     ap.add_argument('--device-chooser', action='store_true',
                     help='also run a short PPO loop and the evaluation with the masked action choice on the device '
                          "(chooser='device': one k_choose launch per step instead of mask_action_probs, torch.multinomial and gaussian_log_prob)")
+    ap.add_argument('--device-norm', action='store_true',
+                    help='also run a short PPO loop and the evaluation with the observation normalisation on the device '
+                         "(obs_norm='device': k_obsnorm_partial / _merge / _apply per step instead of BatchedStateNorm's torch code)")
     ap.add_argument('--eval-levels', action='store_true',
                     help='one more batched evaluation over Dragon-Lake lots DRAWN ON THE DEVICE (jitter, cull, flips per slot), labelled by '
                          'the HIP kernel k_map_level: the per-level block of result.txt for maps that exist on the device only')
@@ -84,6 +87,21 @@ def main():
             flagged = int((tr.chooser.idx >= 64).sum())
             print(f'  device chooser: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f'{flagged} degenerate rows in the last step')
+    if args.device_norm:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
+                        seed=rank, use_planner='device' if args.device_planner else True,
+                        chooser='device' if args.device_chooser else None, obs_norm='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(16):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            sn = tr.obs_norm
+            print(f'  device norm: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f"{sn.n_state} observations folded in, mean lidar std {float(sn.std['lidar'].mean()):.3f} m")
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer
@@ -113,7 +131,8 @@ def main():
     ag = A.BatchedPPO(device=dev, use_img=False)
     env.set_scenes(np.arange(args.scenes), [uniq[i % len(uniq)] for i in range(args.scenes)])
     rec = E.BatchedEvaluator(env, ag, seed=rank, use_planner='device' if args.device_planner else True,
-                             chooser='device' if args.device_chooser else None).run()
+                             chooser='device' if args.device_chooser else None,
+                             obs_norm='device' if args.device_norm else None).run()
     if rank == 0:
         levels = [uniq[i % len(uniq)].level for i in range(args.scenes)] * world
         for k, v in E.summarize(rec, levels).items():

@@ -5,6 +5,7 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   mask_action_probs /
   choose_action        <-> ActionMask.choose_action  src/model/action_mask.py:199-227
   BatchedStateNorm     <-> StateNorm                 src/model/state_norm.py:7-46
+  DeviceStateNorm      <-> the same through the library's kernels (hope_env_obsnorm) or their host twin
   batched_gae          <-> PPO.update's GAE loop     src/model/agent/ppo_agent.py:258-273
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
@@ -334,6 +335,166 @@ class BatchedStateNorm:
             self.S[k] = self.S[k] + bS + delta ** 2 * (n0 * m / (n0 + m))
             self.std[k] = torch.sqrt(self.S[k] / (n0 + m))
         self.n_state = n0 + m
+
+
+class DeviceStateNorm:
+    """BatchedStateNorm's surface over the library's observation normalisation (include/hope_env.h "normalisation of the
+    observations"; rule: csrc/hope_obsnorm_core.h), so that it can stand in as `agent.state_norm`: the statistics live in the env's
+    handle (one set per env), `update` is two launches (k_obsnorm_partial, k_obsnorm_merge), `normalize` one (k_obsnorm_apply), and
+    `update_and_normalize(obs)` fuses the two -- what a rollout does with an observation between two env steps.  The arithmetic
+    order of the fold is fixed, so the statistics do not depend on the launch geometry; they differ from BatchedStateNorm's in the
+    last bits only.  `normalize` returns lidar / target as float32 -- what the agents cast to anyway -- in persistent tensors that
+    the next normalising call overwrites; other keys pass through.  Both modalities go together and hold at most env.n rows.
+    `mean` / `S` / `std` download the statistics on access (host-synchronous).  `fixed` is host-side: update is then a no-op.
+    On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same runs on the host through hope_obsnorm_host: the
+    rule is one source for both.
+    from_norm: a BatchedStateNorm (e.g. from checkpoint.load_hope_checkpoint) or DeviceStateNorm whose statistics and `fixed` are
+    taken over; to_batched() goes the other way, for saving."""
+
+    modal = ('lidar', 'target')
+
+    def __init__(self, env, from_norm=None):
+        from . import _lib as L
+        self.env, self.n, self.fixed = env, env.n, False
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'obsnorm')
+        self._L = L
+        if self.on_device:
+            env.enable_obsnorm()
+        else:
+            assert self.device.type == 'cpu', 'an env without obsnorm must hold CPU tensors'
+            self._lib = L.load_library()
+            self._state = L.ObsNormState()
+            self._out = None
+        if from_norm is not None:
+            self.load(from_norm)
+        elif self.on_device:                          # a new object starts from nothing, whatever the handle held
+            import numpy as np
+            z = np.zeros(L.OBSNORM_COLS)
+            env.obsnorm_load(0, z, z, z)
+
+    # -- statistics ----------------------------------------------------------------------------------------------------
+    def _stats(self):
+        import numpy as np
+        if self.on_device:
+            return self.env.obsnorm_state()
+        s = self._state
+        return (int(s.n_state),) + tuple(np.array(a, dtype=np.float64) for a in (s.mean, s.S, s.std))
+
+    def _split(self, a):
+        t = torch.from_numpy(a).to(self.device)
+        nl = self._L.OBSNORM_LIDAR
+        return {'lidar': t[:nl], 'target': t[nl:]}
+
+    @property
+    def n_state(self):
+        return self.env.obsnorm_count() if self.on_device else int(self._state.n_state)
+
+    @property
+    def mean(self):
+        return self._split(self._stats()[1])
+
+    @property
+    def S(self):
+        return self._split(self._stats()[2])
+
+    @property
+    def std(self):
+        return self._split(self._stats()[3])
+
+    def load(self, norm):
+        """take over n_state, mean, S, std and `fixed` of a BatchedStateNorm / DeviceStateNorm"""
+        import numpy as np
+        assert tuple(norm.modal) == self.modal, 'the device normalisation covers lidar and target'
+        mean, S, std = norm.mean, norm.S, norm.std
+        a = [np.concatenate([d[k].detach().double().cpu().numpy().reshape(-1) for k in self.modal]) for d in (mean, S, std)]
+        if self.on_device:
+            self.env.obsnorm_load(int(norm.n_state), *a)
+        else:
+            self._state.n_state = int(norm.n_state)
+            for name, v in zip(('mean', 'S', 'std'), a):
+                assert v.shape == (self._L.OBSNORM_COLS,)
+                getattr(self._state, name)[:] = v.tolist()
+        self.fixed = bool(norm.fixed)
+        return self
+
+    def to_batched(self, device=None):
+        """-> a BatchedStateNorm with these statistics (bit for bit)"""
+        n, mean, S, std = self._stats()
+        out = BatchedStateNorm(device=self.device if device is None else device)
+        nl = self._L.OBSNORM_LIDAR
+        for name, a in (('mean', mean), ('S', S), ('std', std)):
+            t = torch.from_numpy(a).to(out.mean['lidar'].device)
+            setattr(out, name, {'lidar': t[:nl].clone(), 'target': t[nl:].clone()})
+        out.n_state, out.fixed = n, self.fixed
+        return out
+
+    def fix_parameters(self):
+        self.fixed = True
+
+    # -- the calls -----------------------------------------------------------------------------------------------------
+    def _pair(self, obs):
+        if 'lidar' not in obs or 'target' not in obs:
+            raise ValueError('DeviceStateNorm takes lidar and target together')
+        lidar, target = obs['lidar'], obs['target']
+        if lidar.dim() == 1 and target.dim() == 1:
+            lidar, target = lidar.unsqueeze(0), target.unsqueeze(0)
+        if target.dtype != lidar.dtype:
+            target = target.to(lidar.dtype)
+        if lidar.dtype not in (torch.float32, torch.float64):
+            lidar, target = lidar.float(), target.float()
+        return lidar.contiguous(), target.contiguous()
+
+    def _run(self, obs, update, normalize):
+        lidar, target = self._pair(obs)
+        if self.on_device:
+            return self.env.obsnorm(lidar, target, update, normalize)
+        L = self._L
+        rows = lidar.shape[0]
+        assert lidar.shape == (rows, L.OBSNORM_LIDAR) and target.shape == (rows, L.OBSNORM_TARGET)
+        ol = ot = None
+        if normalize:
+            if self._out is None or self._out[0].shape[0] < rows:
+                self._out = (torch.zeros((max(rows, self.n), L.OBSNORM_LIDAR)), torch.zeros((max(rows, self.n), L.OBSNORM_TARGET)))
+            ol, ot = self._out[0].data_ptr(), self._out[1].data_ptr()
+        flags = (L.OBSNORM_UPDATE if update else 0) | (L.OBSNORM_NORMALIZE if normalize else 0)
+        L.check(self._lib.hope_obsnorm_host(self._state, lidar.data_ptr(), target.data_ptr(), rows, int(lidar.dtype == torch.float64), flags,
+                                            ol, ot), 'hope_obsnorm_host')
+        return (self._out[0][:rows], self._out[1][:rows]) if normalize else (None, None)
+
+    def update(self, obs):
+        """fold obs['lidar'] [B, 120] / obs['target'] [B, 5] into the running statistics (no-op when fixed)"""
+        if not self.fixed:
+            self._run(obs, True, False)
+
+    def _dict(self, obs, nl, nt):
+        if obs['lidar'].dim() == 1:
+            nl, nt = nl[0], nt[0]
+        out = dict(obs)
+        out['lidar'], out['target'] = nl, nt
+        return out
+
+    def normalize(self, obs):
+        return self._dict(obs, *self._run(obs, False, True))
+
+    def update_and_normalize(self, obs):
+        """update(obs) then normalize(obs) with the new statistics, in one call of the library"""
+        return self._dict(obs, *self._run(obs, not self.fixed, True))
+
+
+def make_obs_norm(obs_norm, env, agent):
+    """the loops' `obs_norm` argument: None (today's torch path: the agent's BatchedStateNorm), or 'device' -- the agent's
+    `state_norm` is swapped for a DeviceStateNorm over `env` that takes over its statistics.  -> the DeviceStateNorm or None."""
+    if obs_norm is None:
+        return None
+    if obs_norm != 'device':
+        raise ValueError(f"obs_norm must be None or 'device', not {obs_norm!r}")
+    sn = getattr(agent, 'state_norm', None)
+    if sn is None:
+        raise ValueError("obs_norm='device' needs an agent with a state_norm (state_norm=True)")
+    if not (isinstance(sn, DeviceStateNorm) and sn.env is env):
+        agent.state_norm = DeviceStateNorm(env, from_norm=sn)
+    return agent.state_norm
 
 
 # ---- PPO / SAC storage over [N, T] (SURVEY.md §8f row f-3) -----------------------------------------------------------

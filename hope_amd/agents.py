@@ -134,7 +134,7 @@ class _AgentCommon:
         return f['out'].clone()
 
     @torch.no_grad()
-    def act(self, obs, use_mask=True, generator=None, planned=None, executing=None, plan_fn=None, chooser=None):
+    def act(self, obs, use_mask=True, generator=None, planned=None, executing=None, plan_fn=None, chooser=None, nobs=None):
         """choose_action (mask-weighted discrete sampling, ppo_agent.py:163-169 + action_mask.py:199-227) or
         get_action (plain Gaussian sample, :171-185), clamped to [-1, 1]; scenes flagged in `executing` take the
         planner's action instead (ParkingAgent.choose_action, parking_agent.py:80-99).  Returns (action [N,2] float32,
@@ -143,8 +143,11 @@ class _AgentCommon:
         observation only, so it is enqueued before the caller waits for the Reeds-Shepp outputs of the env step.
         chooser: an `agent_glue.DeviceActionChooser`; with use_mask the block from the sampling to the log-probability is then one
         `chooser.choose` call after plan_fn() (its draws are counter-based: `generator` is not consumed; the action in the env's dtype
-        is left in `chooser.action_env`).  None, or use_mask=False: the torch path below."""
-        nobs = self._norm_obs(obs)
+        is left in `chooser.action_env`).  None, or use_mask=False: the torch path below.
+        nobs: the normalised observation of `obs`, when the caller already has it (agent_glue.DeviceStateNorm.update_and_normalize
+        in the rollout): `_norm_obs` is then not called."""
+        if nobs is None:
+            nobs = self._norm_obs(obs)
         mean = self.policy_mean(nobs)
         if chooser is not None and use_mask:
             if plan_fn is not None:

@@ -488,6 +488,67 @@ class ParkingBatch:
         out = (self.chosen_action, self.chosen_action_f32, self.chosen_idx, self.chosen_log_prob)
         return out + (self.chosen_probs,) if probs else out
 
+    # -- normalisation of the observations on the device (hope_env.h; rule: csrc/hope_obsnorm_core.h) -------------------
+    def enable_obsnorm(self):
+        """StateNorm's running mean / std of lidar and target and the normalised float32 observation as three kernels
+        (k_obsnorm_partial, k_obsnorm_merge, k_obsnorm_apply).  The statistics start at zero (n_state = 0); enabling again keeps
+        them.  Off by default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_obsnorm_enable(self.h), 'hope_env_obsnorm_enable')
+        if getattr(self, 'norm_lidar', None) is None:
+            self.norm_lidar = torch.zeros((self.n, L.OBSNORM_LIDAR), dtype=torch.float32, device=self.device)
+            self.norm_target = torch.zeros((self.n, L.OBSNORM_TARGET), dtype=torch.float32, device=self.device)
+        return self
+
+    def disable_obsnorm(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_obsnorm_disable(self.h), 'hope_env_obsnorm_disable')
+        return self
+
+    def obsnorm(self, lidar=None, target=None, update=True, normalize=True):
+        """fold `lidar` [rows, 120] / `target` [rows, 5] (both float32 or both float64, contiguous, 1 <= rows <= N; None: the env's
+        own observation tensors) into the running statistics and / or normalise them with the statistics as they then are: at most
+        three launches on the current stream, no host synchronisation, no wait for a deferred search.
+        -> (lidar f32 [rows, 120], target f32 [rows, 5]): (views of) persistent tensors of this object, overwritten by the next
+        normalising call; (None, None) without normalize."""
+        dev = self.device
+        lidar = self.lidar if lidar is None else lidar
+        target = self.target if target is None else target
+        assert lidar.dtype in (torch.float32, torch.float64) and target.dtype == lidar.dtype
+        assert lidar.dim() == 2 and target.dim() == 2 and lidar.shape[1] == L.OBSNORM_LIDAR and target.shape[1] == L.OBSNORM_TARGET
+        assert lidar.shape[0] == target.shape[0]
+        assert lidar.device == dev and target.device == dev and lidar.is_contiguous() and target.is_contiguous()
+        rows = lidar.shape[0]
+        flags = (L.OBSNORM_UPDATE if update else 0) | (L.OBSNORM_NORMALIZE if normalize else 0)
+        ol = ot = None
+        if normalize and getattr(self, 'norm_lidar', None) is not None:         # (without them the library reports that it is off)
+            ol, ot = C.c_void_p(self.norm_lidar.data_ptr()), C.c_void_p(self.norm_target.data_ptr())
+        L.check(self.lib.hope_env_obsnorm(self.h, C.c_void_p(lidar.data_ptr()), C.c_void_p(target.data_ptr()), rows,
+                                          int(lidar.dtype == torch.float64), flags, ol, ot, self._stream()), 'hope_env_obsnorm')
+        if not normalize:
+            return None, None
+        return (self.norm_lidar, self.norm_target) if rows == self.n else (self.norm_lidar[:rows], self.norm_target[:rows])
+
+    def obsnorm_count(self):
+        """n_state: the handle keeps it on the host, so this does not wait for the device"""
+        n = C.c_int64(0)
+        L.check(self.lib.hope_env_obsnorm_get(self.h, C.byref(n), None, None, None), 'hope_env_obsnorm_get')
+        return int(n.value)
+
+    def obsnorm_state(self):
+        """-> (n_state, mean, S, std): numpy float64 [125] each (columns 0..119 lidar, 120..124 target); host-synchronous"""
+        n = C.c_int64(0)
+        mean, S, std = (np.zeros(L.OBSNORM_COLS, np.float64) for _ in range(3))
+        L.check(self.lib.hope_env_obsnorm_get(self.h, C.byref(n), mean.ctypes.data, S.ctypes.data, std.ctypes.data), 'hope_env_obsnorm_get')
+        return int(n.value), mean, S, std
+
+    def obsnorm_load(self, n_state, mean, S, std):
+        """replace the statistics (e.g. a checkpoint's); host-synchronous"""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (mean, S, std)]
+        assert all(x.shape == (L.OBSNORM_COLS,) for x in a)
+        L.check(self.lib.hope_env_obsnorm_set(self.h, int(n_state), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data), 'hope_env_obsnorm_set')
+        return self
+
     def queue_check(self):
         """hope_env_create's measurement of which library streams share a hardware queue (hope_env_queue_check):
         {'queue_of_role': [8 ints, [0] = the NULL stream], 'distinct_queues': n, 'roles_shared': pairs of roles busy in the same step

@@ -22,6 +22,7 @@
 #include "hope_maplevel_kernel.h"
 #include "hope_planner_kernel.h"
 #include "hope_chooser_kernel.h"
+#include "hope_obsnorm_kernel.h"
 
 using namespace hope;
 
@@ -196,6 +197,9 @@ struct hope_env {
     struct Planner { bool on = false; double step_ratio = HOPE_PLAN_STEP_RATIO; uint64_t* state = nullptr; } plan;
     // masked choice of the discrete action (hope_chooser_kernel.h): the [42][2] action table, nullptr while the chooser is off
     struct Chooser { bool on = false; double* actions = nullptr; } choose;
+    // normalisation of the observations (hope_obsnorm_kernel.h): state = mean | S | std ([3][125] doubles), part = the chunk partials
+    // ([125][3][stride]); n_state lives here, on the host, and reaches the kernels as an argument
+    struct ObsNorm { bool on = false; int64_t n_state = 0; long long stride = 0; double* state = nullptr; double* part = nullptr; } onorm;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -682,6 +686,7 @@ static int destroy_impl(hope_env_t* h);
 static void cur_free(hope_env_t* h);
 static void plan_free(hope_env_t* h);
 static void choose_free(hope_env_t* h);
+static void onorm_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -947,6 +952,7 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     cur_free(h);
     plan_free(h);
     choose_free(h);
+    onorm_free(h);
     for (auto& ps : h->pset) for (void* q : {(void*)ps.label, (void*)ps.sorted_own[0], (void*)ps.sorted_own[1]}) if (q) hipFree(q);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
@@ -1185,6 +1191,131 @@ int hope_chooser_host(int n, const double* actions, const void* mean, const void
                            action_f32, idx, log_prob, probs);
     if (rc != HOPE_OK)
         return fail(rc, "hope_chooser_host: bad argument (n <= 0, a null actions / mean / log_std / mask / action, planned without executing or the reverse, a stride other than 0 / 2, or an action table that is not 21 steers x 2 speeds)");
+    return HOPE_OK;
+}
+
+// ---- normalisation of the observations (include/hope_env.h; kernels: hope_obsnorm_kernel.h, rule: hope_obsnorm_core.h) ----
+static void onorm_free(hope_env_t* h) {
+    if (h->onorm.state) hipFree(h->onorm.state);
+    if (h->onorm.part) hipFree(h->onorm.part);
+    h->onorm = hope_env::ObsNorm{};
+}
+
+int hope_env_obsnorm_enable(hope_env_t* h) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_enable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_enable: not a live handle (destroyed?)");
+    if (h->onorm.on) return HOPE_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    const long long stride = (h->n + ON_CHUNK - 1) / ON_CHUNK;
+    const size_t sbytes = (size_t)3 * ON_NC * sizeof(double), pbytes = sbytes * (size_t)stride;
+    double *st = nullptr, *pt = nullptr;
+    hipError_t e_ = hipMalloc((void**)&st, sbytes);
+    if (e_ == hipSuccess) e_ = hipMalloc((void**)&pt, pbytes);
+    if (e_ == hipSuccess) e_ = hipMemset(st, 0, sbytes);
+    if (e_ == hipSuccess) e_ = hipMemset(pt, 0, pbytes);
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    if (e_ != hipSuccess) {
+        if (st) hipFree(st);
+        if (pt) hipFree(pt);
+        return fail(HOPE_ENOMEM, std::string("hope_env_obsnorm_enable: ") + hipGetErrorString(e_));
+    }
+    h->onorm.state = st; h->onorm.part = pt; h->onorm.stride = stride; h->onorm.n_state = 0; h->onorm.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm_disable(hope_env_t* h) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_disable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_disable: not a live handle (destroyed?)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    onorm_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm_set(hope_env_t* h, int64_t n_state, const double* mean, const double* S, const double* std_) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: not a live handle (destroyed?)");
+    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm_set: the normalisation is off (hope_env_obsnorm_enable first)");
+    if (!mean || !S || !std_ || n_state < 0) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: null mean / S / std or a negative n_state");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());                         // calls in flight read and write the statistics
+    const size_t b = (size_t)ON_NC * sizeof(double);
+    HIPCHK(hipMemcpy(h->onorm.state, mean, b, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->onorm.state + ON_NC, S, b, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->onorm.state + 2 * ON_NC, std_, b, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    h->onorm.n_state = n_state;
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm_get(hope_env_t* h, int64_t* n_state, double* mean, double* S, double* std_) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_get: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_get: not a live handle (destroyed?)");
+    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm_get: the normalisation is off (hope_env_obsnorm_enable first)");
+    if (n_state) *n_state = h->onorm.n_state;
+    if (!mean && !S && !std_) return HOPE_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    const size_t b = (size_t)ON_NC * sizeof(double);
+    if (mean) HIPCHK(hipMemcpy(mean, h->onorm.state, b, hipMemcpyDeviceToHost));
+    if (S) HIPCHK(hipMemcpy(S, h->onorm.state + ON_NC, b, hipMemcpyDeviceToHost));
+    if (std_) HIPCHK(hipMemcpy(std_, h->onorm.state + 2 * ON_NC, b, hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+}  // extern "C" (a template has C++ linkage)
+template <class T>
+static void onorm_launch(hope_env_t* h, const T* lidar, const T* target, int rows, uint32_t flags, float* out_lidar, float* out_target, hipStream_t st) {
+    hope_env::ObsNorm& o = h->onorm;
+    if (flags & HOPE_OBSNORM_UPDATE) {
+        const int first = o.n_state == 0 ? 1 : 0;
+        const long long m = (long long)rows - first, nk = on_chunks(m);      // nk <= stride: rows <= N
+        if (nk > 0)
+            hipLaunchKernelGGL(k_obsnorm_partial<T>, dim3((unsigned)nk, 2), dim3(64), 0, st, lidar, target, (long long)first, m, o.stride, o.part);
+        hipLaunchKernelGGL(k_obsnorm_merge<T>, dim3(ON_NC), dim3(64), 0, st, lidar, target, first, (long long)o.n_state, nk, o.stride, o.part, o.state);
+        o.n_state += rows;
+    }
+    if (flags & HOPE_OBSNORM_NORMALIZE) {
+        const size_t total = (size_t)rows * ON_NC;
+        hipLaunchKernelGGL(k_obsnorm_apply<T>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, lidar, target, (long long)rows, (const double*)o.state,
+                           out_lidar, out_target);
+    }
+}
+
+extern "C" {
+int hope_env_obsnorm(hope_env_t* h, const void* lidar, const void* target, int rows, int in_f64, uint32_t flags, float* out_lidar, float* out_target,
+                     void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm: not a live handle (destroyed?)");
+    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm: the normalisation is off (hope_env_obsnorm_enable first)");
+    if (!lidar || !target) return fail(HOPE_EINVAL, "hope_env_obsnorm: null lidar / target");
+    if (rows < 1 || rows > h->n) return fail(HOPE_EINVAL, "hope_env_obsnorm: rows must be 1 .. the handle's scenes");
+    if (!(flags & (HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)) || (flags & ~(uint32_t)(HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)))
+        return fail(HOPE_EINVAL, "hope_env_obsnorm: flags are HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE, at least one");
+    const bool norm = flags & HOPE_OBSNORM_NORMALIZE;
+    if (norm && (!out_lidar || !out_target)) return fail(HOPE_EINVAL, "hope_env_obsnorm: HOPE_OBSNORM_NORMALIZE needs out_lidar and out_target");
+    const uintptr_t am = in_f64 ? 7 : 3;
+    if (((uintptr_t)lidar & am) || ((uintptr_t)target & am) || (norm && (((uintptr_t)out_lidar & 3) || ((uintptr_t)out_target & 3))))
+        return fail(HOPE_EINVAL, "hope_env_obsnorm: misaligned buffer (each aligned to its element)");
+    if ((size_t)rows * ON_NC > (size_t)0x7FFFFFFF * 64) return fail(HOPE_EINVAL, "hope_env_obsnorm: too many rows for one launch");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (in_f64) onorm_launch(h, (const double*)lidar, (const double*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
+    else onorm_launch(h, (const float*)lidar, (const float*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_obsnorm_host(hope_obsnorm_state* state, const void* lidar, const void* target, int64_t rows, int in_f64, uint32_t flags, float* out_lidar,
+                      float* out_target) {
+    const int rc = on_host(state, lidar, target, rows, in_f64, flags, out_lidar, out_target);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_obsnorm_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_obsnorm_host: bad argument (a null state / lidar / target, rows < 1, a negative n_state, no or an unknown flag, or NORMALIZE without both outputs)");
     return HOPE_OK;
 }
 

@@ -23,14 +23,17 @@ TOLERANT_TIME = 200
 
 
 class BatchedEvaluator:
-    def __init__(self, env, agent, post_proc_action=True, use_planner=True, seed=0, chooser=None):
+    def __init__(self, env, agent, post_proc_action=True, use_planner=True, seed=0, chooser=None, obs_norm=None):
         """agent: a hope_amd.agents agent (`act(obs, use_mask, generator, planned, executing)`); post_proc_action: PPO's
         mask-weighted choose_action (eval_utils.py:42-43) instead of the plain sample (:44-45).
         chooser: None, or 'device' -- with post_proc_action the choice, the planner's override and the log-probability are one
         k_choose launch per step (agent_glue.DeviceActionChooser; counter-based draws keyed by `seed`).  The stuck detector's
-        random action is applied after it, as before."""
+        random action is applied after it, as before.
+        obs_norm: None, or 'device' -- the agent's state_norm is swapped for an agent_glue.DeviceStateNorm with the same statistics:
+        the normalisation in `act` is then one k_obsnorm_apply launch.  Evaluation folds nothing in, as before."""
         self.env, self.agent, self.use_mask = env, agent, bool(post_proc_action)
         self.chooser = G.make_chooser(chooser, env, seed)
+        self.obs_norm = G.make_obs_norm(obs_norm, env, agent)
         if use_planner == 'device':          # the library's planner: one k_plan launch per step (agent_glue.DeviceRsPlanner)
             self.planner = G.DeviceRsPlanner(env)
         else:

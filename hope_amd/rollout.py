@@ -135,7 +135,7 @@ class TransitionRing:
 
 class HopeRollout:
     def __init__(self, env, agent, horizon, use_mask=True, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None,
-                 defer_rs=True, curriculum=None, chooser=None):
+                 defer_rs=True, curriculum=None, chooser=None, obs_norm=None):
         """defer_rs: step the env with two completion points (HOPE_DEFER_RS): the next policy forward is enqueued as soon as the
         observation is written, the planner reads rs_word / rs_lengths (after ParkingBatch.wait_rs) just before its override --
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
@@ -155,8 +155,14 @@ class HopeRollout:
         chooser: None -- the mask-weighted sampling, the planner's override and the log-probability are torch code (agent_glue.
         choose_action, torch.multinomial); 'device' -- one k_choose launch per step (agent_glue.DeviceActionChooser; counter-based
         draws keyed by `seed`, not torch.multinomial's stream), whose env-typed action tensor goes straight into the step.  Used
-        where the mask is (use_mask); the plain Gaussian sample and the uniform exploration are not its business."""
+        where the mask is (use_mask); the plain Gaussian sample and the uniform exploration are not its business.
+        obs_norm: None -- the agent's BatchedStateNorm (torch code: `agent.observe` after the step, `_norm_obs` in the next `act`);
+        'device' -- the agent's state_norm is swapped for an agent_glue.DeviceStateNorm that takes over its statistics, and the two
+        become ONE update_and_normalize call after the step (three launches), whose float32 result is handed to the next `act`.  The
+        fold's arithmetic order is fixed there, so the statistics differ from the torch path's in the last bits."""
         self.chooser = G.make_chooser(chooser, env, seed)
+        self.obs_norm = G.make_obs_norm(obs_norm, env, agent)
+        self._nobs = None                             # device norm: the normalised observation the next act takes
         self.curriculum = None
         if curriculum is not None:
             if not fresh_scenes:
@@ -190,7 +196,22 @@ class HopeRollout:
         if fresh_scenes and hasattr(env, 'set_redraw_seed'):
             env.set_redraw_seed(seed * 1000003 + 17)
         env.reset_obs()
-        agent.observe(self._raw_obs())
+        if self.obs_norm is not None:
+            self._nobs = self._fold(self._raw_obs())
+        else:
+            agent.observe(self._raw_obs())
+
+    def _agent_obs(self, raw, nz):
+        """what `_norm_obs` returns, with lidar / target from the device norm; mask and image pass through as there"""
+        o = {k: raw[k] for k in self.agent.keys}
+        o['lidar'], o['target'] = nz['lidar'], nz['target']
+        o['action_mask'] = o['action_mask'].float()
+        return o
+
+    def _fold(self, raw):
+        """device norm: observe + _norm_obs of the same observation.  The result lives in the norm's persistent tensors until its
+        next normalising call -- the ring copies it in write_before, and last_obs() rewrites the same values."""
+        return self._agent_obs(raw, self.obs_norm.update_and_normalize({'lidar': raw['lidar'], 'target': raw['target']}))
 
     def _raw_obs(self):
         e = self.env
@@ -225,9 +246,10 @@ class HopeRollout:
         executing = None
         if random_action:
             planned, executing = self._plan()
-            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, planned, executing)
+            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, planned, executing, nobs=self._nobs)
         else:
-            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, plan_fn=self._plan, chooser=self.chooser)
+            action, log_prob, nobs = agent.act(self._raw_obs(), self.use_mask, self.gen, plan_fn=self._plan, chooser=self.chooser,
+                                               nobs=self._nobs)
         if random_action:                             # train_HOPE_sac.py:196-198: uniform exploration while the memory fills
             rnd = torch.rand(action.shape, device=action.device, generator=self.gen) * 2 - 1
             action = rnd if executing is None else torch.where(executing.unsqueeze(1), action, rnd)
@@ -247,7 +269,10 @@ class HopeRollout:
         if self.curriculum is not None:               # update_success_record (:215-225), and every K steps the new draw weights
             self.curriculum.after_step()
         self.ring.write_after(env.reward, env.done)
-        agent.observe(self._raw_obs())                              # push_memory: state_norm(next_obs, update=True)
+        if self.obs_norm is not None:
+            self._nobs = self._fold(self._raw_obs())
+        else:
+            agent.observe(self._raw_obs())                          # push_memory: state_norm(next_obs, update=True)
         done = env.done.bool()
         self.episodes += done.sum()
         self.successes += (env.status == 2).sum()
@@ -258,6 +283,9 @@ class HopeRollout:
 
     def last_obs(self):
         """normalised observation the agent will act on next (value bootstrap / newest next_obs)"""
+        if self.obs_norm is not None:                 # normalise only: the observation was folded in after its step
+            raw = self._raw_obs()
+            return self._agent_obs(raw, self.obs_norm.normalize({'lidar': raw['lidar'], 'target': raw['target']}))
         return self.agent._norm_obs(self._raw_obs())
 
     def stats(self):
@@ -274,13 +302,13 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None):
+                 curriculum=None, chooser=None, obs_norm=None):
         """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update"""
         self._curriculum_per_update = curriculum is not None and 'update_every' not in curriculum
         if self._curriculum_per_update:
             curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm)
         self.updates = 0
 
     def step(self):
@@ -303,10 +331,10 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None):
+                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None):
         """chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used"""
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

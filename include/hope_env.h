@@ -650,6 +650,48 @@ int hope_chooser_host(int n, const double *actions, const void *mean, const void
                       uint64_t counter, uint64_t scene0, void *action, int action_f64, float *action_f32, int32_t *idx, float *log_prob,
                       double *probs);
 
+/* ---- normalisation of the observations (additive to ABI 8) ----------------------------------------------------------------------
+ * The reference's StateNorm (src/model/state_norm.py:25-47) for every scene at once: running mean / S / std of the 120 lidar and 5
+ * target columns in float64, folded in with a parallel merge whose arithmetic order is fixed (64-row chunks, an aligned binary tree),
+ * and out = (float)((x - mean) / (std + 1e-8)).  Three kernels: k_obsnorm_partial, k_obsnorm_merge (update), k_obsnorm_apply
+ * (normalize).  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule and the
+ * bit-equal host twin: hope_amd/csrc/hope_obsnorm_core.h, DESIGN.md 5g. */
+#define HOPE_OBSNORM_LIDAR 120
+#define HOPE_OBSNORM_TARGET 5
+#define HOPE_OBSNORM_COLS 125       /* columns 0 .. 119 lidar, 120 .. 124 target */
+#define HOPE_OBSNORM_UPDATE 0x1u    /* fold the rows into the running statistics */
+#define HOPE_OBSNORM_NORMALIZE 0x2u /* write the normalised rows (after the fold when both are set) */
+/* the statistics as the host twin holds them */
+typedef struct hope_obsnorm_state {
+    int64_t n_state;                /* observations folded in so far */
+    double mean[HOPE_OBSNORM_COLS], S[HOPE_OBSNORM_COLS], std[HOPE_OBSNORM_COLS];
+} hope_obsnorm_state;
+/* allocate the statistics (zero, n_state = 0) and the chunk partials (3 x 125 x ceil(N / 64) doubles).  Enabling an enabled handle
+ * keeps its statistics.  Host-synchronous. */
+int hope_env_obsnorm_enable(hope_env_t *h);
+/* free both.  Host-synchronous (calls in flight use them). */
+int hope_env_obsnorm_disable(hope_env_t *h);
+/* replace / read the statistics: HOST arrays of 125 doubles each.  Both wait for the device (calls in flight read and write the
+ * statistics).  `set` is how statistics from a checkpoint reach the device; n_state >= 0.  `get` with mean, S and std all NULL
+ * returns n_state alone, which the handle keeps on the host, without waiting. */
+int hope_env_obsnorm_set(hope_env_t *h, int64_t n_state, const double *mean, const double *S, const double *std);
+int hope_env_obsnorm_get(hope_env_t *h, int64_t *n_state, double *mean, double *S, double *std);
+/* asynchronous on `stream`; waits for nothing, never synchronises the host and does not join a deferred search (the observation
+ * buffers are complete at the step's first completion point).  DEVICE buffers:
+ *   lidar [rows][120], target [rows][5]    float32, or float64 with in_f64 != 0; aligned to their element; 1 <= rows <= N
+ *   out_lidar [rows][120], out_target [rows][5]   float32; required with HOPE_OBSNORM_NORMALIZE, ignored without
+ * flags: HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE, at least one.  With both the call folds first and normalises with the new
+ * statistics.  The handle counts n_state at the call, so calls belong on one stream (or are ordered by the caller).
+ * HOPE_ESTATE before hope_env_obsnorm_enable; HOPE_EINVAL for a NULL or misaligned pointer, rows out of range, no or an unknown
+ * flag, NORMALIZE without both outputs. */
+int hope_env_obsnorm(hope_env_t *h, const void *lidar, const void *target, int rows, int in_f64, uint32_t flags, float *out_lidar,
+                     float *out_target, void *stream);
+/* The same over HOST arrays: pure host code from the same source, no handle, no device; bit-equal to the kernels.  The caller owns
+ * `state` (zero it to start).  No alignment requirements, no upper bound on rows.  HOPE_EINVAL for a NULL state / lidar / target,
+ * rows < 1, a negative n_state, no or an unknown flag, NORMALIZE without both outputs. */
+int hope_obsnorm_host(hope_obsnorm_state *state, const void *lidar, const void *target, int64_t rows, int in_f64, uint32_t flags,
+                      float *out_lidar, float *out_target);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
