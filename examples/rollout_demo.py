@@ -37,6 +37,9 @@ def main():
     ap.add_argument('--device-norm', action='store_true',
                     help='also run a short PPO loop and the evaluation with the observation normalisation on the device '
                          "(obs_norm='device': k_obsnorm_partial / _merge / _apply per step instead of BatchedStateNorm's torch code)")
+    ap.add_argument('--device-eval', action='store_true',
+                    help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
+                         'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
     ap.add_argument('--eval-levels', action='store_true',
                     help='one more batched evaluation over Dragon-Lake lots DRAWN ON THE DEVICE (jitter, cull, flips per slot), labelled by '
                          'the HIP kernel k_map_level: the per-level block of result.txt for maps that exist on the device only')
@@ -132,7 +135,7 @@ def main():
     env.set_scenes(np.arange(args.scenes), [uniq[i % len(uniq)] for i in range(args.scenes)])
     rec = E.BatchedEvaluator(env, ag, seed=rank, use_planner='device' if args.device_planner else True,
                              chooser='device' if args.device_chooser else None,
-                             obs_norm='device' if args.device_norm else None).run()
+                             obs_norm='device' if args.device_norm else None, tracker='device' if args.device_eval else None).run()
     if rank == 0:
         levels = [uniq[i % len(uniq)].level for i in range(args.scenes)] * world
         for k, v in E.summarize(rec, levels).items():

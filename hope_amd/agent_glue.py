@@ -6,7 +6,8 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   choose_action        <-> ActionMask.choose_action  src/model/action_mask.py:199-227
   BatchedStateNorm     <-> StateNorm                 src/model/state_norm.py:7-46
   DeviceStateNorm      <-> the same through the library's kernels (hope_env_obsnorm) or their host twin
-  batched_gae          <-> PPO.update's GAE loop     src/model/agent/ppo_agent.py:258-273
+  DeviceEvalTracker    <-> eval()'s per-episode tally   src/evaluation/eval_utils.py:35-57 (hope_env_eval_* or their host twins)
+  batched_gae          <-> PPO.update's GAE loop    src/model/agent/ppo_agent.py:258-273
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
 import math
@@ -257,6 +258,118 @@ def make_chooser(chooser, env, seed=0):
     if chooser == 'device':
         return DeviceActionChooser(env, seed)
     raise ValueError(f"chooser must be None, 'device' or a DeviceActionChooser, not {chooser!r}")
+
+
+class DeviceEvalTracker:
+    """The bookkeeping of the reference's eval() (src/evaluation/eval_utils.py:35-57) over the library's tracker (include/hope_env.h
+    "bookkeeping of an evaluation run"; rule: csrc/hope_evaltrack_core.h): the stuck detector and its random action, step count,
+    summed reward, path length, final status, the alive mask and the hiding of frozen slots' Reeds-Shepp words, as one launch before
+    and one after the env step, with no host synchronisation.  The stuck detector's draws are counter-based, keyed by (seed, episode
+    step, scene, dimension): this object keeps the step counter; `evaluate.stuck_uniforms` restates them.
+    On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same operations run on the host through
+    hope_eval_begin_host / hope_eval_override_host / hope_eval_track_host: the rule is one source for both.
+
+    alive: uint8 [N], the episodes still running as of the last `override` (what env.step takes as `active`); word: int8 [N, 8] and
+    done: uint8 [N], the planner's inputs as of the last `track`.  Persistent tensors."""
+
+    def __init__(self, env, seed=0):
+        self.env, self.n, self.seed, self.counter = env, env.n, int(seed) & (2 ** 64 - 1), 0
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'eval_track')
+        if self.on_device:
+            env.enable_eval_tracker()
+            self.alive, self.word, self.done = env.eval_alive, env.eval_word, env.eval_done
+        else:
+            import numpy as np
+            from . import _lib as L
+            assert self.device.type == 'cpu', 'an env without eval_track must hold CPU tensors'
+            self._L, self._lib = L, L.load_library()
+            self._state = np.zeros((L.EVAL_STATE_WORDS, self.n), np.uint64)
+            self._box = np.array([T.VALID_STEER[0], T.VALID_STEER[1], T.VALID_SPEED[0], T.VALID_SPEED[1]], dtype=np.float64)
+            self.alive = torch.zeros(self.n, dtype=torch.uint8)
+            self.word = torch.zeros((self.n, 8), dtype=torch.int8)
+            self.done = torch.zeros(self.n, dtype=torch.uint8)
+
+    def _obs(self, t):
+        """the tensor as contiguous float32 / float64"""
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float32)
+        return t.contiguous()
+
+    def begin(self):
+        """a new episode in every scene, from the env's first observation; the step counter restarts"""
+        self.counter = 0
+        self.alive.fill_(1)
+        self.done.zero_()
+        if self.on_device:
+            self.env.eval_begin()
+            return
+        env = self.env
+        target, pose = self._obs(env.target), env.pose.to(torch.float64).contiguous()
+        self._L.check(self._lib.hope_eval_begin_host(self.n, self.n, self._state.ctypes.data, target.data_ptr(),
+                                                     int(target.dtype == torch.float64), pose.data_ptr()), 'hope_eval_begin_host')
+
+    def override(self, action, u=None):
+        """the stuck detector's random action, in place on `action` ([N, 2] float32 / float64, contiguous); -> `alive`.  Advances the
+        step counter."""
+        if self.on_device:
+            self.env.eval_override(action, u, self.seed, self.counter)
+        else:
+            assert action.shape == (self.n, 2) and action.dtype in (torch.float32, torch.float64) and action.is_contiguous()
+            up = None
+            if u is not None:
+                u = u.to(torch.float64).contiguous()
+                up = u.data_ptr()
+            self._L.check(self._lib.hope_eval_override_host(self.n, self.n, self._state.ctypes.data, self._box.ctypes.data, action.data_ptr(),
+                                                            int(action.dtype == torch.float64), up, self.seed, self.counter, 0,
+                                                            self.alive.data_ptr()), 'hope_eval_override_host')
+        self.counter += 1
+        return self.alive
+
+    def track(self):
+        """the tally of the env step just taken; -> (word, done)"""
+        if self.on_device:
+            self.env.eval_track()
+            return self.word, self.done
+        env = self.env
+        target, pose = self._obs(env.target), env.pose.to(torch.float64).contiguous()
+        reward = env.reward.to(target.dtype).contiguous()
+        status, done, word = env.status.to(torch.int32).contiguous(), env.done.to(torch.uint8).contiguous(), env.rs_word.contiguous()
+        assert word.dtype == torch.int8 and word.shape == (self.n, 8)
+        self._L.check(self._lib.hope_eval_track_host(self.n, self.n, self._state.ctypes.data, target.data_ptr(), int(target.dtype == torch.float64),
+                                                     pose.data_ptr(), reward.data_ptr(), status.data_ptr(), done.data_ptr(), word.data_ptr(),
+                                                     self.word.data_ptr(), self.done.data_ptr()), 'hope_eval_track_host')
+        return self.word, self.done
+
+    def any_alive(self):
+        """is an episode still running, as of the last call of any kind?  alive (of the last override) and not done (of the track
+        behind it) is alive after that track.  Host-synchronous: the evaluator asks every poll_every steps."""
+        return bool((self.alive & (self.done ^ 1)).any())
+
+    def state(self):
+        """numpy uint64 [10, N]: the state planes (host-synchronous on the device)"""
+        return self.env.eval_state() if self.on_device else self._state
+
+    def records(self):
+        """-> float32 [N, 4]: status, steps, summed reward, path length"""
+        if self.on_device:
+            return self.env.eval_records()
+        import numpy as np
+        st = self._state
+        w = st[9]
+        with np.errstate(invalid='ignore', over='ignore'):
+            rec = np.stack([((w >> np.uint64(32)) & np.uint64(0xFF)).astype(np.float32), (w & np.uint64(0xFFFFFFFF)).astype(np.float32),
+                            st[7].view(np.float64).astype(np.float32), st[8].view(np.float64).astype(np.float32)], axis=1)
+        return torch.from_numpy(rec)
+
+
+def make_tracker(tracker, env, seed=0):
+    """the evaluator's `tracker` argument: None (the torch bookkeeping), 'device', or a DeviceEvalTracker"""
+    if tracker is None or isinstance(tracker, DeviceEvalTracker):
+        return tracker
+    if tracker == 'device':
+        return DeviceEvalTracker(env, seed)
+    raise ValueError(f"tracker must be None, 'device' or a DeviceEvalTracker, not {tracker!r}")
 
 
 _ACTIONS = None

@@ -549,6 +549,90 @@ class ParkingBatch:
         L.check(self.lib.hope_env_obsnorm_set(self.h, int(n_state), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data), 'hope_env_obsnorm_set')
         return self
 
+    # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
+    def enable_eval_tracker(self):
+        """eval()'s per-episode tally (eval_utils.py:35-57) as device state of the handle (80 B per scene) and three kernels:
+        k_eval_begin, k_eval_override, k_eval_track.  The stuck detector draws from the physical action box (tables.VALID_STEER /
+        VALID_SPEED).  Enabling again keeps the state.  Off by default."""
+        torch.cuda.synchronize(self.device)
+        box = np.array([T.VALID_STEER[0], T.VALID_STEER[1], T.VALID_SPEED[0], T.VALID_SPEED[1]], dtype=np.float64)
+        L.check(self.lib.hope_env_eval_enable(self.h, box.ctypes.data), 'hope_env_eval_enable')
+        if getattr(self, 'eval_alive', None) is None:
+            dev = self.device
+            self.eval_alive = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+            self.eval_word = torch.zeros((self.n, 8), dtype=torch.int8, device=dev)
+            self.eval_done = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+            self._eval_rec = torch.zeros((self.n, 4), dtype=torch.float32, device=dev)
+        return self
+
+    def disable_eval_tracker(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_eval_disable(self.h), 'hope_env_eval_disable')
+        return self
+
+    def _eval_obs(self, t, shape, dtype):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.device == self.device and t.is_contiguous()
+        return C.c_void_p(t.data_ptr())
+
+    def eval_begin(self, target=None, pose=None):
+        """a new episode in every scene, from the first observation (None: the env's own target / pose); one k_eval_begin launch on
+        the current stream, no host synchronisation"""
+        n = self.n
+        tp = self._eval_obs(self.target if target is None else target, (n, 5), self.obs_dtype)
+        pp = self._eval_obs(self.pose if pose is None else pose, (n, 3), torch.float64)
+        L.check(self.lib.hope_env_eval_begin(self.h, tp, pp, self._stream()), 'hope_env_eval_begin')
+        return self
+
+    def eval_override(self, actions, u=None, seed=0, counter=0):
+        """the stuck detector's random action, in place: the rows of `actions` ([N, 2] float32 or float64, contiguous) of the scenes
+        whose target did not change in the last step are replaced by the clipped draw from the physical action box.  u f64 [N, 2] in
+        [0, 1) or None: counter-based draws keyed by (seed, counter, scene, dimension).  One k_eval_override launch, no host
+        synchronisation.  -> eval_alive (uint8 [N], persistent): the scenes whose episode is still running -- step()'s `active`."""
+        n, dev = self.n, self.device
+        assert actions.shape == (n, 2) and actions.dtype in (torch.float32, torch.float64) and actions.is_contiguous() and actions.device == dev
+        up = None
+        if u is not None:
+            assert u.dtype == torch.float64 and u.shape == (n, 2) and u.device == dev and u.is_contiguous()
+            up = C.c_void_p(u.data_ptr())
+        al = getattr(self, 'eval_alive', None)               # (without it the library reports that the tracker is off)
+        L.check(self.lib.hope_env_eval_override(self.h, C.c_void_p(actions.data_ptr()), int(actions.dtype == torch.float64), up,
+                                                C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)),
+                                                C.c_void_p(al.data_ptr()) if al is not None else None, self._stream()), 'hope_env_eval_override')
+        return al
+
+    def eval_track(self, target=None, pose=None, reward=None, status=None, done=None, rs_word=None):
+        """the tally of the step just taken (None: the env's own outputs); one k_eval_track launch on the current stream, no host
+        synchronisation, no wait for a deferred search.  -> (eval_word int8 [N, 8]: rs_word with the found flag cleared for frozen
+        scenes, eval_done uint8 [N]: episodes that ended in this step): persistent tensors, overwritten by the next call."""
+        n = self.n
+        ptrs = [self._eval_obs(self.target if target is None else target, (n, 5), self.obs_dtype),
+                self._eval_obs(self.pose if pose is None else pose, (n, 3), torch.float64),
+                self._eval_obs(self.reward if reward is None else reward, (n,), self.obs_dtype),
+                self._eval_obs(self.status if status is None else status, (n,), torch.int32),
+                self._eval_obs(self.done if done is None else done, (n,), torch.uint8),
+                self._eval_obs(self.rs_word if rs_word is None else rs_word, (n, 8), torch.int8)]
+        if getattr(self, 'eval_word', None) is None:         # (the library then reports that the tracker is off)
+            wp = dp = None
+        else:
+            wp, dp = C.c_void_p(self.eval_word.data_ptr()), C.c_void_p(self.eval_done.data_ptr())
+        L.check(self.lib.hope_env_eval_track(self.h, *ptrs, wp, dp, self._stream()), 'hope_env_eval_track')
+        return getattr(self, 'eval_word', None), getattr(self, 'eval_done', None)
+
+    def eval_records(self):
+        """-> float32 [N, 4]: status, steps, summed reward, path length of every scene's episode so far (a persistent tensor,
+        overwritten by the next call); one launch, no host synchronisation"""
+        rec = getattr(self, '_eval_rec', None)
+        L.check(self.lib.hope_env_eval_records(self.h, C.c_void_p(rec.data_ptr()) if rec is not None else None, self._stream()),
+                'hope_env_eval_records')
+        return rec
+
+    def eval_state(self):
+        """the tracker's state block (numpy uint64 [10, N]: previous target, previous position, summed reward, path length as
+        float64 bits, the packed steps / status / alive / stuck word) -- host-synchronous; tests"""
+        out = np.zeros((L.EVAL_STATE_WORDS, self.n), np.uint64)
+        L.check(self.lib.hope_env_eval_download_state(self.h, out.ctypes.data), 'hope_env_eval_download_state')
+        return out
+
     def queue_check(self):
         """hope_env_create's measurement of which library streams share a hardware queue (hope_env_queue_check):
         {'queue_of_role': [8 ints, [0] = the NULL stream], 'distinct_queues': n, 'roles_shared': pairs of roles busy in the same step

@@ -23,6 +23,7 @@
 #include "hope_planner_kernel.h"
 #include "hope_chooser_kernel.h"
 #include "hope_obsnorm_kernel.h"
+#include "hope_evaltrack_kernel.h"
 
 using namespace hope;
 
@@ -200,6 +201,9 @@ struct hope_env {
     // normalisation of the observations (hope_obsnorm_kernel.h): state = mean | S | std ([3][125] doubles), part = the chunk partials
     // ([125][3][stride]); n_state lives here, on the host, and reaches the kernels as an argument
     struct ObsNorm { bool on = false; int64_t n_state = 0; long long stride = 0; double* state = nullptr; double* part = nullptr; } onorm;
+    // bookkeeping of an evaluation run (hope_evaltrack_kernel.h): [ET_WORDS][n] state words, nullptr while it is off; the action box
+    // of the stuck detector's draw reaches k_eval_override as an argument
+    struct EvalTrack { bool on = false; EtBox box = {}; uint64_t* state = nullptr; } evalt;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -687,6 +691,7 @@ static void cur_free(hope_env_t* h);
 static void plan_free(hope_env_t* h);
 static void choose_free(hope_env_t* h);
 static void onorm_free(hope_env_t* h);
+static void evalt_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -953,6 +958,7 @@ static int destroy_impl(hope_env_t* h) {                   // (also the clean-up
     plan_free(h);
     choose_free(h);
     onorm_free(h);
+    evalt_free(h);
     for (auto& ps : h->pset) for (void* q : {(void*)ps.label, (void*)ps.sorted_own[0], (void*)ps.sorted_own[1]}) if (q) hipFree(q);
     void* ptrs[] = {h->obb, h->fverts, h->fbox, h->eflag, h->verts, h->n_obst, h->scene_c, h->state, h->cs, h->tstep, h->tab, h->pmax, h->mask_lut, h->mask_bsc,
                     h->hull_base, h->beam_ab, h->rs_count, h->rs_surv_count, h->rs_surv, h->rs_list, h->rs_in, h->rs_flag, h->kin, h->post, h->cls_list[0], h->cls_list[1], h->rs_rec, h->cur_pool, h->episode, h->pset[0].verts, h->pset[0].c, h->pset[0].nobst, h->pset[0].list[0], h->pset[0].list[1], h->pset[1].verts, h->pset[1].c, h->pset[1].nobst, h->pset[1].list[0], h->pset[1].list[1], h->pstage_dev, h->pool_overflow, h->slot_cls, h->active_snap, h->cold_dev, h->dlp_mem[0], h->dlp_mem[1], h->dlp_mem[2], h->dlp_mem[3], h->dlp_mem[4], h->dlp_mem[5], h->stage, h->traj, h->traj_len, h->traj_valid, h->layer_valid, h->bev_layer, h->bev_dyn, h->bev_list, h->bev_legacy, h->bev_scratch};
@@ -1316,6 +1322,149 @@ int hope_obsnorm_host(hope_obsnorm_state* state, const void* lidar, const void* 
     if (rc == HOPE_ENOMEM) return fail(rc, "hope_obsnorm_host: out of memory for the chunk partials");
     if (rc != HOPE_OK)
         return fail(rc, "hope_obsnorm_host: bad argument (a null state / lidar / target, rows < 1, a negative n_state, no or an unknown flag, or NORMALIZE without both outputs)");
+    return HOPE_OK;
+}
+
+// ---- bookkeeping of an evaluation run (include/hope_env.h; kernels: hope_evaltrack_kernel.h, rule: hope_evaltrack_core.h) ----
+static void evalt_free(hope_env_t* h) {
+    if (h->evalt.state) hipFree(h->evalt.state);
+    h->evalt = hope_env::EvalTrack{};
+}
+
+int hope_env_eval_enable(hope_env_t* h, const double* box) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_enable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_enable: not a live handle (destroyed?)");
+    if (!et_box_ok(box)) return fail(HOPE_EINVAL, "hope_env_eval_enable: the action box is null or not finite (steer lo, steer hi, speed lo, speed hi)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());                         // calls in flight read the box as it was
+    if (!h->evalt.state) {
+        const size_t bytes = (size_t)ET_WORDS * h->n * sizeof(uint64_t);
+        uint64_t* st = nullptr;
+        hipError_t e_ = hipMalloc((void**)&st, bytes);
+        if (e_ == hipSuccess) e_ = hipMemset(st, 0, bytes);
+        if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+        if (e_ != hipSuccess) {
+            if (st) hipFree(st);
+            return fail(HOPE_ENOMEM, std::string("hope_env_eval_enable: ") + hipGetErrorString(e_));
+        }
+        h->evalt.state = st;
+    }
+    h->evalt.box = et_box(box);
+    h->evalt.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_eval_disable(hope_env_t* h) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_disable: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_disable: not a live handle (destroyed?)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    evalt_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_eval_begin(hope_env_t* h, const void* target, const double* pose, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_begin: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_begin: not a live handle (destroyed?)");
+    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_begin: the evaluation tracker is off (hope_env_eval_enable first)");
+    if (!target || !pose) return fail(HOPE_EINVAL, "hope_env_eval_begin: null target / pose");
+    const bool of64 = h->flags & HOPE_F_OBS_F64;
+    if (((uintptr_t)target & (of64 ? 7 : 3)) || ((uintptr_t)pose & 7)) return fail(HOPE_EINVAL, "hope_env_eval_begin: misaligned buffer (each aligned to its element)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (of64) hipLaunchKernelGGL(k_eval_begin<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, h->evalt.state);
+    else hipLaunchKernelGGL(k_eval_begin<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, h->evalt.state);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_override(hope_env_t* h, void* actions_inout, int action_is_f64, const double* u, uint64_t seed, uint64_t counter, uint8_t* active_out,
+                           void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_override: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_override: not a live handle (destroyed?)");
+    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_override: the evaluation tracker is off (hope_env_eval_enable first)");
+    if (!actions_inout || !active_out) return fail(HOPE_EINVAL, "hope_env_eval_override: null actions / active_out");
+    if (((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)) || ((uintptr_t)u & 7))
+        return fail(HOPE_EINVAL, "hope_env_eval_override: misaligned buffer (actions 8 / 16 bytes, u 8 bytes)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(k_eval_override, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, h->evalt.box,
+                       actions_inout, action_is_f64 ? 1 : 0, u, seed, counter, active_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_track(hope_env_t* h, const void* target, const double* pose, const void* reward, const int32_t* status, const uint8_t* done,
+                        const int8_t* rs_word, int8_t* word_out, uint8_t* done_out, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_track: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_track: not a live handle (destroyed?)");
+    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_track: the evaluation tracker is off (hope_env_eval_enable first)");
+    if (!target || !pose || !reward || !status || !done || !rs_word || !word_out || !done_out)
+        return fail(HOPE_EINVAL, "hope_env_eval_track: null target / pose / reward / status / done / rs_word / word_out / done_out");
+    const bool of64 = h->flags & HOPE_F_OBS_F64;
+    const uintptr_t om = of64 ? 7 : 3;
+    if (((uintptr_t)target & om) || ((uintptr_t)reward & om) || ((uintptr_t)pose & 7) || ((uintptr_t)status & 3) || ((uintptr_t)rs_word & 7) ||
+        ((uintptr_t)word_out & 7))
+        return fail(HOPE_EINVAL, "hope_env_eval_track: misaligned buffer (rs_word and word_out 8 bytes, the others their element)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (of64)
+        hipLaunchKernelGGL(k_eval_track<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, (const double*)reward, status, done,
+                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
+    else
+        hipLaunchKernelGGL(k_eval_track<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, (const float*)reward, status, done,
+                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_records(hope_env_t* h, float* rec_out, void* stream) {
+    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_records: null handle");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_records: not a live handle (destroyed?)");
+    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_records: the evaluation tracker is off (hope_env_eval_enable first)");
+    if (!rec_out) return fail(HOPE_EINVAL, "hope_env_eval_records: null rec_out");
+    if ((uintptr_t)rec_out & 15) return fail(HOPE_EINVAL, "hope_env_eval_records: misaligned buffer (rec_out 16 bytes)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(k_eval_records, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, (float4*)rec_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_download_state(hope_env_t* h, void* state_out) {
+    if (!h || !state_out) return fail(HOPE_EINVAL, "hope_env_eval_download_state: null argument");
+    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_download_state: not a live handle (destroyed?)");
+    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_download_state: the evaluation tracker is off (hope_env_eval_enable first)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(state_out, h->evalt.state, (size_t)ET_WORDS * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+int hope_eval_begin_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose) {
+    const int rc = et_begin_host(n, state_stride, state, target, obs_f64, pose);
+    if (rc != HOPE_OK) return fail(rc, "hope_eval_begin_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose)");
+    return HOPE_OK;
+}
+
+int hope_eval_override_host(int64_t n, int64_t state_stride, const void* state, const double* box, void* actions_inout, int action_is_f64, const double* u,
+                            uint64_t seed, uint64_t counter, uint64_t scene0, uint8_t* active_out) {
+    const int rc = et_override_host(n, state_stride, state, box, actions_inout, action_is_f64, u, seed, counter, scene0, active_out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_eval_override_host: bad argument (n <= 0, state_stride < n, a null state / actions / active_out, or a box that is null or not finite)");
+    return HOPE_OK;
+}
+
+int hope_eval_track_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose, const void* reward,
+                         const int32_t* status, const uint8_t* done, const int8_t* rs_word, int8_t* word_out, uint8_t* done_out) {
+    const int rc = et_track_host(n, state_stride, state, target, obs_f64, pose, reward, status, done, rs_word, word_out, done_out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_eval_track_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose / reward / status / done / rs_word / word_out / done_out)");
     return HOPE_OK;
 }
 

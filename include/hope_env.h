@@ -692,6 +692,59 @@ int hope_env_obsnorm(hope_env_t *h, const void *lidar, const void *target, int r
 int hope_obsnorm_host(hope_obsnorm_state *state, const void *lidar, const void *target, int64_t rows, int in_f64, uint32_t flags,
                       float *out_lidar, float *out_target);
 
+/* ---- bookkeeping of an evaluation run (additive to ABI 8) -----------------------------------------------------------------------
+ * What the reference's eval() keeps per episode (src/evaluation/eval_utils.py:35-57) for every scene at once: the stuck detector
+ * and its random physical action (:46-47), the step count, the summed reward, the path length (:52-53), the final status, the mask of
+ * the episodes still running, and the hiding of a frozen slot's stale Reeds-Shepp word from the planner.  Three kernels, one lane per
+ * scene: k_eval_begin (after the first observation), k_eval_override (between the policy and the env step), k_eval_track (after the
+ * env step).  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule, the state
+ * layout, the counter-based draw and the bit-equal host twins: hope_amd/csrc/hope_evaltrack_core.h, DESIGN.md 5h.
+ *
+ * State: 80 bytes per scene, stored as planes [10][N] of 8-byte words -- planes 0-4 the previous target (float64), 5-6 the previous
+ * rear-axle position, 7 the summed reward, 8 the path length, 9 packed: bits 0-31 steps, 32-39 status, bit 40 alive, bit 41 stuck.
+ * A stored NaN is always 0x7FF8000000000000.  `target` and `reward` below have the handle's observation type (float64 iff
+ * HOPE_F_OBS_F64), `pose` is f64 [N][3], `status` i32 [N], `done` u8 [N], `rs_word` i8 [N][8] (8-byte aligned), as hope_step_out has
+ * them; every pointer is explicit and a DEVICE pointer.  All calls but enable / disable / download_state are asynchronous on
+ * `stream`, wait for nothing (they do not join a deferred search) and never synchronise the host.  HOPE_ESTATE before
+ * hope_env_eval_enable; HOPE_EINVAL for a NULL required pointer or a misaligned buffer; the handle stays usable after an error. */
+#define HOPE_EVAL_STATE_WORDS 10    /* 8-byte words of state per scene, stored as planes: [10][N] */
+/* allocate and zero the state.  box: HOST float64 [4] = steer lo, steer hi, speed lo, speed hi of the physical action box the stuck
+ * detector draws from (finite, HOPE_EINVAL otherwise).  Enabling an enabled handle replaces the box and keeps the state.
+ * Host-synchronous. */
+int hope_env_eval_enable(hope_env_t *h, const double *box);
+/* free the state.  Host-synchronous (calls in flight use it). */
+int hope_env_eval_disable(hope_env_t *h);
+/* k_eval_begin: a new episode in every scene -- the previous target and position are (target, pose), sums and steps 0, status 1,
+ * alive, stuck (the reference's first comparison is obs['target'] with itself: the first action of every episode is the random one) */
+int hope_env_eval_begin(hope_env_t *h, const void *target, const double *pose, void *stream);
+/* k_eval_override: active_out u8 [N] = alive; the action row of every scene whose `stuck` bit is set (alive or not) is replaced by
+ * clamp(lo_d + (hi_d - lo_d) * u_d, -1, 1) rounded once to the action type; other rows are not touched.  actions_inout [N][2]
+ * float32 or float64 (action_is_f64; 8- / 16-byte aligned).  u f64 [N][2] in [0, 1) or NULL: the draw of scene s, dimension d is then
+ * the counter-based uniform of (seed, counter, s, d); counter = the index of the episode step. */
+int hope_env_eval_override(hope_env_t *h, void *actions_inout, int action_is_f64, const double *u, uint64_t seed, uint64_t counter,
+                           uint8_t *active_out, void *stream);
+/* k_eval_track, after the env step: a live scene counts the step, adds reward and displacement; `done` on a live scene freezes it
+ * with the env's status; every scene compares target with the previous one (stuck) and takes over target and position.  word_out i8
+ * [N][8] (8-byte aligned; may be rs_word itself) = rs_word with byte 6 (found) zeroed unless the scene is still alive after this
+ * step; done_out u8 [N] = the scene's episode ended in this step. */
+int hope_env_eval_track(hope_env_t *h, const void *target, const double *pose, const void *reward, const int32_t *status,
+                        const uint8_t *done, const int8_t *rs_word, int8_t *word_out, uint8_t *done_out, void *stream);
+/* rec_out f32 [N][4] (16-byte aligned) = status, steps, (float)summed reward, (float)path length */
+int hope_env_eval_records(hope_env_t *h, float *rec_out, void *stream);
+/* the state block as the next call will read it (host array of HOPE_EVAL_STATE_WORDS * N 8-byte words); host-synchronous */
+int hope_env_eval_download_state(hope_env_t *h, void *state_out);
+/* The same three operations over HOST arrays with a caller-owned state block: pure host code from the same source, no handle, no
+ * device; bit-equal to the kernels.  state: HOPE_EVAL_STATE_WORDS planes, `state_stride` words apart, whose words 0 .. n-1 are this
+ * call's scenes (state_stride >= n; a part of a larger block passes the block's stride and the address of its first scene's word in
+ * plane 0).  obs_f64: the type of target and reward.  scene0: the index of row 0 in the counter-based draw, so that a batch may be
+ * split.  No alignment requirements.  HOPE_EINVAL for n <= 0, state_stride < n, a NULL required pointer or a box that is not finite. */
+int hope_eval_begin_host(int64_t n, int64_t state_stride, void *state, const void *target, int obs_f64, const double *pose);
+int hope_eval_override_host(int64_t n, int64_t state_stride, const void *state, const double *box, void *actions_inout,
+                            int action_is_f64, const double *u, uint64_t seed, uint64_t counter, uint64_t scene0, uint8_t *active_out);
+int hope_eval_track_host(int64_t n, int64_t state_stride, void *state, const void *target, int obs_f64, const double *pose,
+                         const void *reward, const int32_t *status, const uint8_t *done, const int8_t *rs_word, int8_t *word_out,
+                         uint8_t *done_out);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
