@@ -38,7 +38,8 @@ __host__ __device__ inline int rs_list_n_obst(int entry) { return (int)((unsigne
 //   [64 + 8 c ..] the word of candidate slot c (RsWord)                                                       -- k_rs_words
 //   [448 + 50 k ..] segment table of the k-th popped word (k < words to test), written by k_rs_segs: 5 segments x 8 doubles
 //       (origin x, y, heading, cos, sin of the heading, type, length, [seg 0 only] int2 (type code, segment count));
-//       table 0 also carries cos / sin(-pose heading) in the spare words [15], [23];
+//       table 0 also carries cos / sin(-pose heading) in the spare words [15], [23]; every table: [31] = 1.0 iff the word's end point has a
+//       local x of exactly 0.0 (the reference's trailing pop then removes the final sample: pop_trailing_zero_x, hope_rs.hip);
 //       then 5 x 2 doubles = 5 x 4 floats for the float32 filter of k_rs_validate: per segment the origin in the frame
 //       "world minus (map box xmin, ymin)" [m] (the frame of the scene's float32 obstacle view) and cos / sin of the WORLD heading at the origin
 // Per queued search, written by k_rs_compact next to the queue entry (same index): everything k_rs_words / k_rs_segs need from the

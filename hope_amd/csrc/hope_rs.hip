@@ -19,11 +19,9 @@
 //                  boxes overlap (the reference requires the intersection point inside both), so pairs failing that
 //                  exact pre-test skip the two float64 divisions.  The reference's obstacle cull (:482-494) and its
 //                  T x 4 x E matrix are result-neutral and are not materialised.
-// Deviation (documented in DESIGN.md §4): generate_local_course's "pop trailing samples whose local x is
-// exactly 0.0" (:501-505) is not replayed beyond the unused array tail.  Exactly aligned poses do reach it (a word that
-// ends on the start's lateral axis: 288 of the 4 002 searches of tests/rs_degenerate.py lose their last sample in the
-// reference); on none of them does it change the found flag, the number of tested words, the word or its lengths
-// (tests/test_rs_degenerate.py runs the oracle both ways; tests/test_gpu_rs_degenerate.py compares the kernels with it).
+// generate_local_course's "pop trailing samples whose local x is exactly 0.0" (:501-505) is replayed (pop_trailing_zero_x): a word
+// that ends on the start's lateral axis loses its last sample(s) in the reference, and an obstacle that only that sample meets
+// does not condemn the word (tests/rs_one_sample.py family (b), tests/test_gpu_rs_one_sample.py).
 #include <stdlib.h>
 
 #include "hope_dev.h"
@@ -210,6 +208,37 @@ __device__ __forceinline__ void interpolate(double l, int m, double ox, double o
         px = ox + gdx;
         py = oy + gdy;
         pyaw = (m == TL) ? oyaw + l : oyaw - l;
+    }
+}
+
+// generate_local_course's "remove unused data" (:500-505): `while px[-1] == 0.0: pop` removes every trailing entry whose LOCAL x
+// (interpolate's px, before calc_all_paths' rotation) is exactly 0.0 -- the unused tail of the lists AND samples in use: a word that
+// ends on the start's lateral axis loses its last sample(s), and is_traj_valid never sees them.  Called when a word's generator
+// has appended the final sample and k_rs_segs found that sample's local x to be 0.0 (nothing is popped otherwise): the queue (qpd / qseg [0, nq), written and fenced by the caller) then ends with the
+// word's last samples.  Lane j recomputes the px of the j-th sample from the end with the reference's float64 expressions; the
+// leading run of exact zeros is dropped, 64 samples per trip of the loop, until a sample stays or the queue is empty.  Samples
+// that left the queue in an earlier window were tested and found clear (the word is still alive), so a pop that reached back to
+// them would not change this verdict; a queue popped empty (every sample gone, the start pose included) leaves a word without
+// samples, which is_traj_valid accepts.  What is NOT replayed: a word condemned in an EARLIER window by a sample that the pop
+// would have removed together with everything behind it -- a run of exact zeros longer than the word's last window.  On the
+// lattice of tests/rs_degenerate.py the pop takes at most two samples (the final one and a lattice sample that ties with the
+// segment end), always inside the last window (tests/rs_one_sample.py asserts it).  The screen pass never sees a popped sample
+// either: it only uses lattice points more than SCREEN_EPS inside their segment, and both kinds sit on a segment end.
+// Returns the new queue length.
+__device__ __forceinline__ int pop_trailing_zero_x(int nq, const double* segp, int segw, const double* qpd, const unsigned char* qseg, int lane) {
+    for (;;) {
+        const int k = nq - 1 - lane;
+        bool zero = false;
+        if (k >= 0) {
+            const double* sp_ = segp + segw * (int)qseg[k];
+            double px, py, pyaw;
+            interpolate(qpd[k], (int)sp_[5], sp_[0], sp_[1], sp_[2], sp_[3], -sp_[4], sp_[3], sp_[4], px, py, pyaw);
+            zero = px == 0.0;
+        }
+        const unsigned long long stays = ~__ballot(zero);
+        const int cnt = stays ? __ffsll((long long)stays) - 1 : 64;
+        nq -= cnt;
+        if (cnt < 64) return nq;
     }
 }
 
@@ -639,6 +668,9 @@ __global__ __launch_bounds__(64) void k_rs_segs(RsParams p) {
                 hy = (m == TL) ? hy + l : ((m == TR) ? hy - l : hy);
             }
         }
+        // the word's end point is its final sample, and (ox, oy) was advanced by interpolate's own expressions: a local x of exactly
+        // 0.0 there is what starts the reference's trailing pop (pop_trailing_zero_x); the walk only looks when this says so
+        tb[3 * RS_SEGW + 7] = ox == 0.0 ? 1.0 : 0.0;
         if (k == 0) {                                    // calc_all_paths' rotation by -q0 yaw (:47-49), once per search:
             tb[RS_SEGW + 7] = cq0;                       // hm_cos(-q0w): spare words of table 0 (hm_sincos is exactly even / odd)
             tb[2 * RS_SEGW + 7] = -sq0;                  // hm_sin(-q0w)
@@ -701,6 +733,9 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate(RsParams p, int obs_f64
     // direction: pd = d, 2d, ... from the origin (0, 0, 0).  So a first-segment sample found in collision condemns every
     // later word that starts with the same type and direction and is long enough to contain it (|l0| >= |pd|, the
     // generator's own inclusion test) -- those words are skipped without being sampled.  bad1[type * 2 + forward].
+    // The later word's own trailing pop cannot take that sample away: a first-segment sample's local x is pd / maxc or
+    // sin(pd) / maxc, zero only at pd = 0.  The start pose itself (pd = 0) does have local x 0 and goes when a word is popped
+    // empty, so a cache entry of 0 skips nothing: such a word is walked and its own pop decides.
     double* bad1 = scr + RSB_BAD;                         // LDS, wave-uniform
     if (lane < 6) bad1[lane] = INFINITY;
     wsync();
@@ -713,7 +748,7 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate(RsParams p, int obs_f64
         const double len0 = readlane_d(tcur, 6), w6 = readlane_d(tcur, 7);
         const int code = __double2loint(w6), nseg = __double2hiint(w6);
         const int cls1 = type_of(code, 0) * 2 + (len0 > 0.0 ? 1 : 0);
-        if (!(obs_f64 & 0x800) && fabs(len0) >= bad1[cls1]) continue;    // contains a sample already known to collide
+        if (!(obs_f64 & 0x800) && bad1[cls1] > 0.0 && fabs(len0) >= bad1[cls1]) continue;    // contains a sample already known to collide
 
         // generate_local_course (:452-507).  Samples are queued as (pd, segment) and collision-tested 64 at a
         // time, so short segments share a pass.  Sample 0 (the start pose, local (0,0,0)) = segment 0 at pd = 0.
@@ -787,13 +822,14 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate(RsParams p, int obs_f64
             }
             wsync();
             RS_T(2);
+            if (finished && segp[3 * RSB_SEGW + 7] != 0.0) nq = pop_trailing_zero_x(nq, segp, RSB_SEGW, qpd, qseg, lane);      // the reference's trailing pop (:500-505; k_rs_segs: the final sample's local x is 0.0)
             // only whole waves of samples are tested while the path goes on; the remainder (< 64) stays queued and is
             // topped up by the next segments, so every pass but the path's last runs with all 64 lanes busy
             const int n_all = nq;
             const int n = finished ? n_all : (n_all & ~(WAVE - 1));
             // coarse pass: every `stride`-th sample with stride = ceil(n / 64), i.e. as dense as one full-wave pass
-            // allows (a fixed stride of 8 left 3/4 of the lanes idle on a 130-sample window)
-            const int stride = (n + WAVE - 1) / WAVE;
+            // allows (a fixed stride of 8 left 3/4 of the lanes idle on a 130-sample window); n = 0 (a word popped empty): nobody active
+            const int stride = max((n + WAVE - 1) / WAVE, 1);
             const int n_coarse = (n + stride - 1) / stride;
             const int n_rest = n - n_coarse;
             for (int rnd = 0; rnd == 0 || (rnd - 1) * WAVE < n_rest; rnd++) {
@@ -1419,7 +1455,7 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate_f(RsParams p, int obs_f
         const double len0 = readlane_d(tcur, 6), w6 = readlane_d(tcur, 7);
         const int code = __double2loint(w6), nseg = __double2hiint(w6);
         const int cls1 = type_of(code, 0) * 2 + (len0 > 0.0 ? 1 : 0);
-        if (fabs(len0) >= bad1[cls1]) continue;           // contains a sample already known to collide
+        if (bad1[cls1] > 0.0 && fabs(len0) >= bad1[cls1]) continue;           // contains a sample already known to collide
         const bool screened = (condemned >> (idx - 1)) & 1;
         if (screened && !verify_screen) continue;         // the screen found a certainly colliding sample of this word
         bool invalid = false;
@@ -1497,6 +1533,7 @@ __global__ __launch_bounds__(64, OCC) void k_rs_validate_f(RsParams p, int obs_f
             }
             lsync();
             RS_T(2);
+            if (finished && segp[3 * RSB_SEGW + 7] != 0.0) nq = pop_trailing_zero_x(nq, segp, RSB_SEGW, qpd, qseg, lane);      // the reference's trailing pop (:500-505; k_rs_segs: the final sample's local x is 0.0)
             const int n_all = nq;
             const int n = finished ? n_all : (n_all & ~(WAVE - 1));
             const int stride = (n + WAVE - 1) >> 6;                  // 1 .. 3 (n <= 192): no integer divisions below

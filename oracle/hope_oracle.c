@@ -970,7 +970,7 @@ static void *arena_alloc(size_t bytes, int zero) {
     }
 }
 
-static int g_rs_tail_only;                  /* orc_rs_pop_mode: 1 = keep every sample in use (the kernels' form) */
+static int g_rs_tail_only;                  /* orc_rs_pop_mode: 1 = keep every sample in use (not the reference's form) */
 static __thread long g_rs_used_popped;      /* samples in use that the reference's pop removed, on this thread */
 void orc_rs_pop_mode(int tail_only) { g_rs_tail_only = tail_only; }
 long orc_rs_used_popped(int reset) { long v = g_rs_used_popped; if (reset) g_rs_used_popped = 0; return v; }
@@ -1018,7 +1018,8 @@ static int rs_local_course(double L, const double *lengths, const int *mode, int
     }
     /* "remove unused data" (:500-505) pops every trailing entry whose local x is exactly 0.0: the unused tail of the arrays AND,
      * on exactly aligned poses, the samples in use that end on the start's lateral axis (tests/test_rs_degenerate.py).  The
-     * kernels drop the unused tail only; g_rs_tail_only restates that form so that the two can be compared on the host. */
+     * kernels replay it too; g_rs_tail_only restates the form that drops the unused tail only, so that the two can be compared on
+     * the host (tests/rs_one_sample.py: where they differ). */
     const int used = ind + 1;
     int n = point_num;
     while (n > 0 && px[n - 1] == 0.0) n--;

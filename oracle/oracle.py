@@ -209,7 +209,7 @@ def find_rs_path(pose, dest, verts, nvert, bbox):
 
 def rs_pop_mode(tail_only):
     """generate_local_course's trailing pop (reeds_shepp.py:500-505) in the selected single-thread library: False (default) =
-    the reference's (samples in use whose local x is exactly 0.0 go too), True = the unused array tail only, as the kernels do."""
+    the reference's and the kernels' (samples in use whose local x is exactly 0.0 go too), True = the unused array tail only."""
     lib().orc_rs_pop_mode(C.c_int(int(bool(tail_only))))
 
 

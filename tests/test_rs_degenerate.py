@@ -162,8 +162,9 @@ def test_hope_math_oracle_differs_only_where_the_result_is_libm_noise(lattice, f
 
 def test_trailing_pop_is_reached_and_changes_no_result(lattice, fixture, runs):
     """generate_local_course pops trailing samples whose local x is exactly 0.0 (reeds_shepp.py:500-505).  On this lattice that
-    removes samples IN USE (the oracle replays it: the glibc test above pins the sample counts); the kernels drop the unused
-    tail only.  The two forms must give the same search result on every case, else the kernels have to replay the pop."""
+    removes samples IN USE (the oracle replays it: the glibc test above pins the sample counts; so do the kernels).  On the lattice's
+    own obstacles the two forms give the same search result on every case; tests/rs_one_sample.py has the obstacles that tell them
+    apart."""
     full, popped = runs['hope_math']
     tail, would_pop = runs['hope_math_tail_only']
     assert np.array_equal(popped, would_pop)
