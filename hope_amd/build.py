@@ -1,12 +1,12 @@
 """Builds hope_amd/libhope_env.so for gfx950 with hipcc (in-tree, so the .so travels to the GPU box)."""
+import glob
 import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, 'csrc')
 _ROOT = os.path.dirname(_HERE)
-SOURCES = ['hope_env.hip', 'hope_rs.hip', 'hope_bev.hip', 'hope_scenegen.cpp']
-HEADERS = ['hope_math.h', 'hope_dev.h', 'hope_internal.h', 'hope_step_kernel.h', 'hope_obs_pair.h', 'hope_motion_pair.h', 'hope_scenegen_core.h', 'hope_scenegen_kernel.h', 'hope_curriculum_core.h', 'hope_curriculum_kernel.h', 'hope_maplevel_core.h', 'hope_maplevel_kernel.h', 'hope_planner_core.h', 'hope_planner_kernel.h', 'hope_chooser_core.h', 'hope_chooser_kernel.h', 'hope_obsnorm_core.h', 'hope_obsnorm_kernel.h', 'hope_evaltrack_core.h', 'hope_evaltrack_kernel.h', os.path.join(_ROOT, 'include', 'hope_env.h')]
+SOURCES = ['hope_env.hip', 'hope_agent.hip', 'hope_rs.hip', 'hope_bev.hip', 'hope_scenegen.cpp']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
          '-Wno-unused-value', '-pthread']
 
@@ -20,7 +20,8 @@ def _stale(out):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    deps = [os.path.join(_CSRC, s) for s in SOURCES] + [h if os.path.isabs(h) else os.path.join(_CSRC, h) for h in HEADERS]
+    # every header of the library, so that a new one cannot be missed
+    deps = [os.path.join(_CSRC, s) for s in SOURCES] + glob.glob(os.path.join(_CSRC, '*.h')) + [os.path.join(_ROOT, 'include', 'hope_env.h')]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

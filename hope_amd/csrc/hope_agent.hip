@@ -1,0 +1,408 @@
+// hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
+// action, normalisation of the observations, bookkeeping of an evaluation run -- and their host twins.  They share nothing with the
+// step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "hope_handle.h"
+#include "hope_planner_kernel.h"
+#include "hope_chooser_kernel.h"
+#include "hope_obsnorm_kernel.h"
+#include "hope_evaltrack_kernel.h"
+
+using namespace hope;
+
+#define PLANNER_ON(h, name) HOPE_NEED((h)->plan.on, name, "the planner is off (hope_env_planner_enable first)")
+#define CHOOSER_ON(h, name) HOPE_NEED((h)->choose.on, name, "the chooser is off (hope_env_chooser_enable first)")
+#define OBSNORM_ON(h, name) HOPE_NEED((h)->onorm.on, name, "the normalisation is off (hope_env_obsnorm_enable first)")
+#define EVAL_ON(h, name) HOPE_NEED((h)->evalt.on, name, "the evaluation tracker is off (hope_env_eval_enable first)")
+
+// What every hope_env_*_enable does with a feature's device buffer: allocate it if absent, fill it (from `src`, or with zeros) and
+// wait.  On any failure the buffer is freed and *buf is null; the caller then puts the feature's struct back to "off" (*_free).
+template <class T>
+static int device_buffer(const char* who, T** buf, size_t bytes, const void* src = nullptr) {
+    hipError_t e_ = hipSuccess;
+    if (!*buf && (e_ = hipMalloc((void**)buf, bytes)) != hipSuccess) {
+        *buf = nullptr;
+        return fail(HOPE_ENOMEM, std::string(who) + ": " + hipGetErrorString(e_));
+    }
+    e_ = src ? hipMemcpy(*buf, src, bytes, hipMemcpyHostToDevice) : hipMemset(*buf, 0, bytes);
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    if (e_ == hipSuccess) return HOPE_OK;
+    hipFree(*buf);
+    *buf = nullptr;
+    return fail(HOPE_EHIP, std::string(who) + ": " + hipGetErrorString(e_));
+}
+
+// hope_env_*_disable: nothing in flight reads the feature's memory any more, then it goes
+static int feature_disable(hope_env_t* h, void (*free_fn)(hope_env_t*)) {
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    free_fn(h);
+    return HOPE_OK;
+}
+
+// the state block of a feature ([words][n] 64-bit words) to the host
+static int download_words(hope_env_t* h, const uint64_t* state, int words, void* state_out) {
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(state_out, state, (size_t)words * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+void hope::plan_free(hope_env_t* h) {
+    if (h->plan.state) hipFree(h->plan.state);
+    h->plan = hope_env::Planner{};
+}
+void hope::choose_free(hope_env_t* h) {
+    if (h->choose.actions) hipFree(h->choose.actions);
+    h->choose = hope_env::Chooser{};
+}
+void hope::onorm_free(hope_env_t* h) {
+    if (h->onorm.state) hipFree(h->onorm.state);
+    if (h->onorm.part) hipFree(h->onorm.part);
+    h->onorm = hope_env::ObsNorm{};
+}
+void hope::evalt_free(hope_env_t* h) {
+    if (h->evalt.state) hipFree(h->evalt.state);
+    h->evalt = hope_env::EvalTrack{};
+}
+
+template <class T>
+static void onorm_launch(hope_env_t* h, const T* lidar, const T* target, int rows, uint32_t flags, float* out_lidar, float* out_target, hipStream_t st) {
+    hope_env::ObsNorm& o = h->onorm;
+    if (flags & HOPE_OBSNORM_UPDATE) {
+        const int first = o.n_state == 0 ? 1 : 0;
+        const long long m = (long long)rows - first, nk = on_chunks(m);      // nk <= stride: rows <= N
+        if (nk > 0)
+            hipLaunchKernelGGL(k_obsnorm_partial<T>, dim3((unsigned)nk, 2), dim3(64), 0, st, lidar, target, (long long)first, m, o.stride, o.part);
+        hipLaunchKernelGGL(k_obsnorm_merge<T>, dim3(ON_NC), dim3(64), 0, st, lidar, target, first, (long long)o.n_state, nk, o.stride, o.part, o.state);
+        o.n_state += rows;
+    }
+    if (flags & HOPE_OBSNORM_NORMALIZE) {
+        const size_t total = (size_t)rows * ON_NC;
+        hipLaunchKernelGGL(k_obsnorm_apply<T>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, lidar, target, (long long)rows, (const double*)o.state,
+                           out_lidar, out_target);
+    }
+}
+
+extern "C" {
+
+// ---- replay of found Reeds-Shepp paths (include/hope_env.h; kernel: hope_planner_kernel.h, rule: hope_planner_core.h) ----
+int hope_env_planner_enable(hope_env_t* h, double step_ratio) {
+    HOPE_ENTER(h, "hope_env_planner_enable");
+    if (step_ratio != step_ratio || !pl_finite(step_ratio)) return fail(HOPE_EINVAL, "hope_env_planner_enable: step_ratio is not finite");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // planner steps in flight read the state
+    const int rc = device_buffer("hope_env_planner_enable", &h->plan.state, (size_t)PL_WORDS * h->n * sizeof(uint64_t));
+    if (rc != HOPE_OK) { plan_free(h); return rc; }
+    h->plan.step_ratio = step_ratio > 0.0 ? step_ratio : HOPE_PLAN_STEP_RATIO;
+    h->plan.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_planner_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_planner_disable");
+    return feature_disable(h, plan_free);
+}
+
+int hope_env_planner_reset(hope_env_t* h, const uint8_t* mask, void* stream) {
+    HOPE_ENTER(h, "hope_env_planner_reset");
+    PLANNER_ON(h, "hope_env_planner_reset");
+    HOPE_ON_DEVICE(h);
+    if (!mask) {
+        HIPCHK(hipMemsetAsync(h->plan.state, 0, (size_t)PL_WORDS * h->n * sizeof(uint64_t), (hipStream_t)stream));
+        return HOPE_OK;
+    }
+    hipLaunchKernelGGL(k_plan_reset, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, mask, h->plan.state);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_planner_step(hope_env_t* h, const int8_t* rs_word, const void* rs_lengths, const uint8_t* done, int forced, uint64_t step,
+                          double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64, void* stream) {
+    HOPE_ENTER(h, "hope_env_planner_step");
+    PLANNER_ON(h, "hope_env_planner_step");
+    if (!rs_word || !rs_lengths) return fail(HOPE_EINVAL, "hope_env_planner_step: null rs_word / rs_lengths");
+    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_env_planner_step: unknown bit in `forced`");
+    const bool lf64 = h->flags & HOPE_F_OBS_F64;
+    if (((uintptr_t)rs_word & 7) || ((uintptr_t)rs_lengths & (lf64 ? 7 : 3)) || ((uintptr_t)planned_out & 15) ||
+        ((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)))
+        return fail(HOPE_EINVAL, "hope_env_planner_step: misaligned buffer (rs_word 8, planned_out 16, actions 8 / 16 bytes)");
+    if (step != 0) {                                        // hope_env_wait_rs_step, before anything is touched
+        if (step > h->step_seq) return fail(HOPE_EINVAL, "hope_env_planner_step: no such step (hope_env_last_step)");
+        if (step != h->step_seq)
+            return fail(HOPE_ESTATE, "hope_env_planner_step: step " + std::to_string(step) + " is not the last one (" + std::to_string(h->step_seq) +
+                                     "): a later hope_env_step / hope_env_reset_obs has replaced its Reeds-Shepp outputs -- plan before enqueuing the next step");
+    }
+    HOPE_ON_DEVICE(h);
+    if (step != 0) { int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
+    hipLaunchKernelGGL(k_plan, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)rs_word, rs_lengths, lf64 ? 1 : 0, done,
+                       forced, h->plan.step_ratio, h->plan.state, (double2*)planned_out, executing_out, actions_inout, action_is_f64 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_planner_step_host(int n, double step_ratio, void* state, const int8_t* rs_word, const void* rs_lengths, int lengths_f64,
+                           const uint8_t* done, int forced, double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64) {
+    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_planner_step_host: unknown bit in `forced`");
+    const int rc = pl_step_host(n, step_ratio > 0.0 ? step_ratio : (step_ratio == 0.0 ? HOPE_PLAN_STEP_RATIO : step_ratio), state, rs_word, rs_lengths, lengths_f64,
+                                done, forced, planned_out, executing_out, actions_inout, action_is_f64);
+    if (rc != HOPE_OK) return fail(rc, "hope_planner_step_host: bad argument (n <= 0, a null state / rs_word / rs_lengths, or a step_ratio that is not positive and finite)");
+    return HOPE_OK;
+}
+
+int hope_env_planner_download_state(hope_env_t* h, void* state_out) {
+    HOPE_ENTER_AS(h, "hope_env_planner_download_state", "null argument");
+    if (!state_out) return fail(HOPE_EINVAL, "hope_env_planner_download_state: null argument");
+    PLANNER_ON(h, "hope_env_planner_download_state");
+    return download_words(h, h->plan.state, PL_WORDS, state_out);
+}
+
+// ---- masked choice of the discrete action (include/hope_env.h; kernel: hope_chooser_kernel.h, rule: hope_chooser_core.h) ----
+int hope_env_chooser_enable(hope_env_t* h, const double* actions) {
+    HOPE_ENTER(h, "hope_env_chooser_enable");
+    if (!actions) return fail(HOPE_EINVAL, "hope_env_chooser_enable: null action table");
+    if (!ch_table_ok(actions))
+        return fail(HOPE_EINVAL, "hope_env_chooser_enable: the action table must be finite, rows 0..20 at one speed and rows 21..41 the same steers at another");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // choices in flight read the table
+    const int rc = device_buffer("hope_env_chooser_enable", &h->choose.actions, (size_t)CH_NA * 2 * sizeof(double), actions);
+    if (rc != HOPE_OK) { choose_free(h); return rc; }
+    h->choose.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_chooser_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_chooser_disable");
+    return feature_disable(h, choose_free);
+}
+
+int hope_env_choose(hope_env_t* h, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, const double* planned,
+                    const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, void* action, float* action_f32, int32_t* idx,
+                    float* log_prob, double* probs, void* stream) {
+    HOPE_ENTER(h, "hope_env_choose");
+    CHOOSER_ON(h, "hope_env_choose");
+    if (!mean || !log_std || !mask || !action) return fail(HOPE_EINVAL, "hope_env_choose: null mean / log_std / mask / action");
+    if ((planned != nullptr) != (executing != nullptr)) return fail(HOPE_EINVAL, "hope_env_choose: planned and executing go together");
+    if (log_std_row_stride != 0 && log_std_row_stride != 2) return fail(HOPE_EINVAL, "hope_env_choose: log_std_row_stride is 0 (one row for all) or 2");
+    const bool mf64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
+    if (((uintptr_t)mean & (in_f64 ? 15 : 7)) || ((uintptr_t)log_std & (in_f64 ? 7 : 3)) || ((uintptr_t)mask & (mf64 ? 7 : 3)) || ((uintptr_t)planned & 15) ||
+        ((uintptr_t)u & 7) || ((uintptr_t)action & (af64 ? 15 : 7)) || ((uintptr_t)action_f32 & 7) || ((uintptr_t)idx & 3) || ((uintptr_t)log_prob & 7) ||
+        ((uintptr_t)probs & 7))
+        return fail(HOPE_EINVAL, "hope_env_choose: misaligned buffer (mean and action rows 8 / 16, planned 16, action_f32 and log_prob 8 bytes, the others their element)");
+    HOPE_ON_DEVICE(h);
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (mf64)
+        hipLaunchKernelGGL(k_choose<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
+                           in_f64 ? 1 : 0, (const double*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
+                           (int*)idx, (float2*)log_prob, probs);
+    else
+        hipLaunchKernelGGL(k_choose<float>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
+                           in_f64 ? 1 : 0, (const float*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
+                           (int*)idx, (float2*)log_prob, probs);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_chooser_host(int n, const double* actions, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, int mask_f64,
+                      const double* planned, const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, uint64_t scene0, void* action,
+                      int action_f64, float* action_f32, int32_t* idx, float* log_prob, double* probs) {
+    const int rc = ch_host(n, actions, mean, log_std, log_std_row_stride, in_f64, mask, mask_f64, planned, executing, u, seed, counter, scene0, action, action_f64,
+                           action_f32, idx, log_prob, probs);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_chooser_host: bad argument (n <= 0, a null actions / mean / log_std / mask / action, planned without executing or the reverse, a stride other than 0 / 2, or an action table that is not 21 steers x 2 speeds)");
+    return HOPE_OK;
+}
+
+// ---- normalisation of the observations (include/hope_env.h; kernels: hope_obsnorm_kernel.h, rule: hope_obsnorm_core.h) ----
+int hope_env_obsnorm_enable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_obsnorm_enable");
+    if (h->onorm.on) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    const long long stride = (h->n + ON_CHUNK - 1) / ON_CHUNK;
+    const size_t sbytes = (size_t)3 * ON_NC * sizeof(double);
+    int rc = device_buffer("hope_env_obsnorm_enable", &h->onorm.state, sbytes);
+    if (rc == HOPE_OK) rc = device_buffer("hope_env_obsnorm_enable", &h->onorm.part, sbytes * (size_t)stride);
+    if (rc != HOPE_OK) { onorm_free(h); return rc; }
+    h->onorm.stride = stride; h->onorm.n_state = 0; h->onorm.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_obsnorm_disable");
+    return feature_disable(h, onorm_free);
+}
+
+int hope_env_obsnorm_set(hope_env_t* h, int64_t n_state, const double* mean, const double* S, const double* std_) {
+    HOPE_ENTER(h, "hope_env_obsnorm_set");
+    OBSNORM_ON(h, "hope_env_obsnorm_set");
+    if (!mean || !S || !std_ || n_state < 0) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: null mean / S / std or a negative n_state");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // calls in flight read and write the statistics
+    const size_t b = (size_t)ON_NC * sizeof(double);
+    HIPCHK(hipMemcpy(h->onorm.state, mean, b, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->onorm.state + ON_NC, S, b, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->onorm.state + 2 * ON_NC, std_, b, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    h->onorm.n_state = n_state;
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm_get(hope_env_t* h, int64_t* n_state, double* mean, double* S, double* std_) {
+    HOPE_ENTER(h, "hope_env_obsnorm_get");
+    OBSNORM_ON(h, "hope_env_obsnorm_get");
+    if (n_state) *n_state = h->onorm.n_state;
+    if (!mean && !S && !std_) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    const size_t b = (size_t)ON_NC * sizeof(double);
+    if (mean) HIPCHK(hipMemcpy(mean, h->onorm.state, b, hipMemcpyDeviceToHost));
+    if (S) HIPCHK(hipMemcpy(S, h->onorm.state + ON_NC, b, hipMemcpyDeviceToHost));
+    if (std_) HIPCHK(hipMemcpy(std_, h->onorm.state + 2 * ON_NC, b, hipMemcpyDeviceToHost));
+    return HOPE_OK;
+}
+
+int hope_env_obsnorm(hope_env_t* h, const void* lidar, const void* target, int rows, int in_f64, uint32_t flags, float* out_lidar, float* out_target,
+                     void* stream) {
+    HOPE_ENTER(h, "hope_env_obsnorm");
+    OBSNORM_ON(h, "hope_env_obsnorm");
+    if (!lidar || !target) return fail(HOPE_EINVAL, "hope_env_obsnorm: null lidar / target");
+    if (rows < 1 || rows > h->n) return fail(HOPE_EINVAL, "hope_env_obsnorm: rows must be 1 .. the handle's scenes");
+    if (!(flags & (HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)) || (flags & ~(uint32_t)(HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)))
+        return fail(HOPE_EINVAL, "hope_env_obsnorm: flags are HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE, at least one");
+    const bool norm = flags & HOPE_OBSNORM_NORMALIZE;
+    if (norm && (!out_lidar || !out_target)) return fail(HOPE_EINVAL, "hope_env_obsnorm: HOPE_OBSNORM_NORMALIZE needs out_lidar and out_target");
+    const uintptr_t am = in_f64 ? 7 : 3;
+    if (((uintptr_t)lidar & am) || ((uintptr_t)target & am) || (norm && (((uintptr_t)out_lidar & 3) || ((uintptr_t)out_target & 3))))
+        return fail(HOPE_EINVAL, "hope_env_obsnorm: misaligned buffer (each aligned to its element)");
+    if ((size_t)rows * ON_NC > (size_t)0x7FFFFFFF * 64) return fail(HOPE_EINVAL, "hope_env_obsnorm: too many rows for one launch");
+    HOPE_ON_DEVICE(h);
+    if (in_f64) onorm_launch(h, (const double*)lidar, (const double*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
+    else onorm_launch(h, (const float*)lidar, (const float*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_obsnorm_host(hope_obsnorm_state* state, const void* lidar, const void* target, int64_t rows, int in_f64, uint32_t flags, float* out_lidar,
+                      float* out_target) {
+    const int rc = on_host(state, lidar, target, rows, in_f64, flags, out_lidar, out_target);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_obsnorm_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_obsnorm_host: bad argument (a null state / lidar / target, rows < 1, a negative n_state, no or an unknown flag, or NORMALIZE without both outputs)");
+    return HOPE_OK;
+}
+
+// ---- bookkeeping of an evaluation run (include/hope_env.h; kernels: hope_evaltrack_kernel.h, rule: hope_evaltrack_core.h) ----
+int hope_env_eval_enable(hope_env_t* h, const double* box) {
+    HOPE_ENTER(h, "hope_env_eval_enable");
+    if (!et_box_ok(box)) return fail(HOPE_EINVAL, "hope_env_eval_enable: the action box is null or not finite (steer lo, steer hi, speed lo, speed hi)");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // calls in flight read the box as it was
+    if (!h->evalt.state) {                                  // (enabled again while on: the new box, the state as it is)
+        const int rc = device_buffer("hope_env_eval_enable", &h->evalt.state, (size_t)ET_WORDS * h->n * sizeof(uint64_t));
+        if (rc != HOPE_OK) { evalt_free(h); return rc; }
+    }
+    h->evalt.box = et_box(box);
+    h->evalt.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_eval_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_eval_disable");
+    return feature_disable(h, evalt_free);
+}
+
+int hope_env_eval_begin(hope_env_t* h, const void* target, const double* pose, void* stream) {
+    HOPE_ENTER(h, "hope_env_eval_begin");
+    EVAL_ON(h, "hope_env_eval_begin");
+    if (!target || !pose) return fail(HOPE_EINVAL, "hope_env_eval_begin: null target / pose");
+    const bool of64 = h->flags & HOPE_F_OBS_F64;
+    if (((uintptr_t)target & (of64 ? 7 : 3)) || ((uintptr_t)pose & 7)) return fail(HOPE_EINVAL, "hope_env_eval_begin: misaligned buffer (each aligned to its element)");
+    HOPE_ON_DEVICE(h);
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (of64) hipLaunchKernelGGL(k_eval_begin<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, h->evalt.state);
+    else hipLaunchKernelGGL(k_eval_begin<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, h->evalt.state);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_override(hope_env_t* h, void* actions_inout, int action_is_f64, const double* u, uint64_t seed, uint64_t counter, uint8_t* active_out,
+                           void* stream) {
+    HOPE_ENTER(h, "hope_env_eval_override");
+    EVAL_ON(h, "hope_env_eval_override");
+    if (!actions_inout || !active_out) return fail(HOPE_EINVAL, "hope_env_eval_override: null actions / active_out");
+    if (((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)) || ((uintptr_t)u & 7))
+        return fail(HOPE_EINVAL, "hope_env_eval_override: misaligned buffer (actions 8 / 16 bytes, u 8 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_eval_override, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, h->evalt.box,
+                       actions_inout, action_is_f64 ? 1 : 0, u, seed, counter, active_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_track(hope_env_t* h, const void* target, const double* pose, const void* reward, const int32_t* status, const uint8_t* done,
+                        const int8_t* rs_word, int8_t* word_out, uint8_t* done_out, void* stream) {
+    HOPE_ENTER(h, "hope_env_eval_track");
+    EVAL_ON(h, "hope_env_eval_track");
+    if (!target || !pose || !reward || !status || !done || !rs_word || !word_out || !done_out)
+        return fail(HOPE_EINVAL, "hope_env_eval_track: null target / pose / reward / status / done / rs_word / word_out / done_out");
+    const bool of64 = h->flags & HOPE_F_OBS_F64;
+    const uintptr_t om = of64 ? 7 : 3;
+    if (((uintptr_t)target & om) || ((uintptr_t)reward & om) || ((uintptr_t)pose & 7) || ((uintptr_t)status & 3) || ((uintptr_t)rs_word & 7) ||
+        ((uintptr_t)word_out & 7))
+        return fail(HOPE_EINVAL, "hope_env_eval_track: misaligned buffer (rs_word and word_out 8 bytes, the others their element)");
+    HOPE_ON_DEVICE(h);
+    const dim3 grid((h->n + 63) / 64), block(64);
+    if (of64)
+        hipLaunchKernelGGL(k_eval_track<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, (const double*)reward, status, done,
+                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
+    else
+        hipLaunchKernelGGL(k_eval_track<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, (const float*)reward, status, done,
+                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_records(hope_env_t* h, float* rec_out, void* stream) {
+    HOPE_ENTER(h, "hope_env_eval_records");
+    EVAL_ON(h, "hope_env_eval_records");
+    if (!rec_out) return fail(HOPE_EINVAL, "hope_env_eval_records: null rec_out");
+    if ((uintptr_t)rec_out & 15) return fail(HOPE_EINVAL, "hope_env_eval_records: misaligned buffer (rec_out 16 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_eval_records, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, (float4*)rec_out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_eval_download_state(hope_env_t* h, void* state_out) {
+    HOPE_ENTER_AS(h, "hope_env_eval_download_state", "null argument");
+    if (!state_out) return fail(HOPE_EINVAL, "hope_env_eval_download_state: null argument");
+    EVAL_ON(h, "hope_env_eval_download_state");
+    return download_words(h, h->evalt.state, ET_WORDS, state_out);
+}
+
+int hope_eval_begin_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose) {
+    const int rc = et_begin_host(n, state_stride, state, target, obs_f64, pose);
+    if (rc != HOPE_OK) return fail(rc, "hope_eval_begin_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose)");
+    return HOPE_OK;
+}
+
+int hope_eval_override_host(int64_t n, int64_t state_stride, const void* state, const double* box, void* actions_inout, int action_is_f64, const double* u,
+                            uint64_t seed, uint64_t counter, uint64_t scene0, uint8_t* active_out) {
+    const int rc = et_override_host(n, state_stride, state, box, actions_inout, action_is_f64, u, seed, counter, scene0, active_out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_eval_override_host: bad argument (n <= 0, state_stride < n, a null state / actions / active_out, or a box that is null or not finite)");
+    return HOPE_OK;
+}
+
+int hope_eval_track_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose, const void* reward,
+                         const int32_t* status, const uint8_t* done, const int8_t* rs_word, int8_t* word_out, uint8_t* done_out) {
+    const int rc = et_track_host(n, state_stride, state, target, obs_f64, pose, reward, status, done, rs_word, word_out, done_out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_eval_track_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose / reward / status / done / rs_word / word_out / done_out)");
+    return HOPE_OK;
+}
+
+}  // extern "C"

@@ -16,17 +16,7 @@
 
 namespace hope {
 
-// device state of the curriculum (one allocation, laid out by cur_layout, hope_env.hip)
-struct CwDev {
-    unsigned long long* episodes;    // [nb + 1] cumulative; [nb]: unlabelled maps
-    unsigned long long* successes;   // [nb + 1]
-    unsigned long long* folded_e;    // [nb] value of episodes at the last update
-    unsigned long long* folded_s;    // [nb]
-    double* win_n;                   // [nb]
-    double* win_s;                   // [nb]
-    double* prob;                    // [nb] q_0 .. q_3, p_c
-    double* pw;                      // [4]
-};
+// (CwDev, the device state of the curriculum: hope_internal.h)
 
 // lab: labels of the pool set the step drew from ([n_lab], values 0 / 1 / 2 / 255).  done == nullptr: only note the buckets, of
 // the scenes with mask[i] != 0 (behind hope_env_redraw) or of all (mask == nullptr).  episode: the handle's redraw counters;

@@ -1,4 +1,5 @@
-// hope_env.hip -- host side of the C ABI (include/hope_env.h) + the fused step kernel instantiation.
+// hope_env.hip -- host side of the C ABI (include/hope_env.h) + the fused step kernel instantiation: create / destroy, step launcher,
+// scene pool, curriculum, debug.  (The handle and the entry prologue: hope_handle.h; planner, chooser, normalisation, evaluation: hope_agent.hip.)
 // gfx950 only; no CPU fallback: every entry point fails with HOPE_ENODEV/HOPE_EHIP when no device works.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -12,225 +13,30 @@
 #include <vector>
 
 #include "hope_dev.h"
-#include "hope_env.h"
-#include "hope_internal.h"
+#include "hope_handle.h"
 #include "hope_step_kernel.h"
 #include "hope_obs_pair.h"
 #include "hope_motion_pair.h"
 #include "hope_scenegen_kernel.h"
 #include "hope_curriculum_kernel.h"
 #include "hope_maplevel_kernel.h"
-#include "hope_planner_kernel.h"
-#include "hope_chooser_kernel.h"
-#include "hope_obsnorm_kernel.h"
-#include "hope_evaltrack_kernel.h"
 
 using namespace hope;
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
+int hope::fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(HOPE_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
-    } while (0)
 
-// Stream roles of a step's launch structure.  The numbers are those hope_env_queue_check reports (include/hope_env.h).
-enum Role {
-    ROLE_CALLER = 0,      // the caller's stream
-    ROLE_CHAIN = 1,       // the second chain (small-tile class): all of it, or its search launches in a pipelined step
-    ROLE_IMAGE = 2,       // the image (joined steps) / the static-layer rebuild next to it (pipelined steps)
-    ROLE_OBS_LARGE = 3,   // observation half of the first chain (large-tile class)
-    ROLE_OBS_SMALL = 4,   // observation half of the second chain (small-tile class)
-    ROLE_SEARCH0 = 5,     // search launches of the first chain in a pipelined step
-    ROLE_SPARE = 6,       // created, never used: the runtime spreads streams over hardware queues in creation order
-    ROLE_OBS_SUB = 7,     // observation half of the second sub-chain of a single-class batch
-    N_ROLES = 8
-};
-
-struct hope_env {
-    int n = 0, max_obst = 0, device = 0;
-    uint32_t flags = 0;
-    uint32_t profile_mask = ~0u;   // HOPE_F_PROFILE: kernels (bit = HOPE_K_*) whose launches are bracketed by events
-    bool have_tables = false, have_scenes = false;
-    char arch[64] = {0};
-    // device memory
-    double* verts = nullptr;
-    int32_t* n_obst = nullptr;
-    double* scene_c = nullptr;
-    double* state = nullptr;
-    double* cs = nullptr;         // [n][2] cos / sin of state's heading (motion launch -> observation launch)
-    int32_t* tstep = nullptr;
-    double* tab = nullptr;
-    double* pmax = nullptr;
-    uint16_t* mask_lut = nullptr;   // count-interval table of the action mask's coarse beams (MASK_LUT_*, hope_step_kernel.h)
-    double* mask_bsc = nullptr;     // [NBEAM] bins per metre of every coarse beam's table
-    double* hull_base = nullptr;
-    double* beam_ab = nullptr;
-    int32_t* rs_count = nullptr;
-    int32_t* rs_list = nullptr;
-    double* rs_in = nullptr;      // [2 n][RS_IN_WORDS] search inputs by queue position (k_rs_compact -> k_rs_words / k_rs_segs)
-    uint8_t* rs_flag = nullptr;
-    double* kin = nullptr;
-    double* post = nullptr;        // [n][POST_WORDS] k_env_step -> k_post hand-over
-    double* traj = nullptr;        // HOPE_F_IMAGE: [n][20][3] ring of vehicle.trajectory
-    int32_t* traj_len = nullptr;   // HOPE_F_IMAGE: [n] len(vehicle.trajectory)
-    int32_t* traj_valid = nullptr; // HOPE_F_IMAGE: [n] entries below this index have span tables in bev_scratch
-    int32_t* layer_valid = nullptr; // HOPE_F_IMAGE: [n] the static image layer (obstacles, start outline, dest) matches the scene's map
-    uint8_t* bev_layer = nullptr;   // HOPE_F_IMAGE: [n][64 KiB] the static layer, 2 bits per pixel, tiled
-    uint8_t* bev_dyn = nullptr;     // HOPE_F_IMAGE: [n][256 KiB] the trajectory layer, one byte per pixel, tiled
-    int32_t* bev_list = nullptr;    // HOPE_F_IMAGE: [1 + n] count + scenes whose layer must be rebuilt this step
-    int32_t* bev_legacy = nullptr;  // HOPE_F_IMAGE: [1 + n] count + scenes for the per-tile raster launch of k_bev_image
-    int* bev_scratch = nullptr;    // HOPE_F_IMAGE: [n][BEV_SCENE_INTS]
-    // per tile class (0: n_obst <= SMALL_TILE, 1: larger) dense scene lists; classes are static between set_scenes calls
-    int32_t* cls_list[2] = {nullptr, nullptr};
-    int cls_count[2] = {0, 0};
-    std::vector<int32_t> n_obst_host;
-    std::vector<uint8_t> slot_cls_host;          // draw / launch class of every scene slot (0: <= 32 obstacles, 1: larger lots)
-    uint8_t* slot_cls = nullptr;                 // the same on the device
-    double* rs_rec = nullptr;
-    int32_t* rs_surv_count = nullptr;            // [MAX_CHAIN] two-kernel validation: searches k_rs_screen left a word of, per chain
-    int2* rs_surv = nullptr;                     // [2 n] (queue index, queue entry), laid out like rs_list
-    uint8_t* active_snap = nullptr; // [n] the caller's `active` mask as the motion launch saw it (read by k_rs_compact, HOPE_DEFER_RS)
-    // StepCold (rarely used kernel parameters) in device memory: a ring of immutable versions, uploaded stream-ordered on change
-    static constexpr int COLD_RING = 8;
-    StepCold* cold_dev = nullptr;   // [COLD_RING]
-    StepCold* cold_host = nullptr;  // [COLD_RING] pinned
-    hipEvent_t cold_ev[COLD_RING] = {};
-    int cold_idx = -1;
-    StepCold cold_last;
-    uint64_t pool_generation = 0;   // bumped by every change of what a draw can return (pool commit / upload, Dragon-Lake cases)
-    uint64_t redraw_seed = 0;       // HOPE_AUTO_REDRAW
-    float4* obb = nullptr;          // [n][max_obst] obstacle boxes (xmin, xmax, ymin, ymax), float32 rounded outwards
-    float4* fverts = nullptr;       // [n][max_obst][2] float32 view of the obstacles relative to (map box xmin, ymin): obstacle_f32
-    float4* fbox = nullptr;         // [n][max_obst]
-    uint8_t* eflag = nullptr;       // [n][eflag_stride(max_obst)]
-    // staging for set_scenes
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
-    // HOPE_F_PROFILE: event pairs recorded on the launch stream, drained by hope_env_kernel_ms
-    struct EvPair { hipEvent_t a, b; int kind; uint64_t seq; };   // seq: the hope_env_step / reset_obs call the launch belongs to
-    uint64_t step_seq = 0;
-    double union_ms[HOPE_N_KERNELS] = {};       // per kernel: time during which >= 1 launch of a call was running
-    int64_t union_calls[HOPE_N_KERNELS] = {};
-    std::vector<EvPair> pending;
-    std::vector<hipEvent_t> free_events;
-    double ms[HOPE_N_KERNELS] = {};
-    int64_t launches[HOPE_N_KERNELS] = {};
-    // scene pool (hope_env_set_pool): complete scenes resident in HBM; hope_env_redraw copies one into a finished slot
-    int pool_n = 0;
-    double* pool_verts = nullptr;   // [pool_n][max_obst][8]
-    double* pool_c = nullptr;       // [pool_n][SC_WORDS]
-    int32_t* pool_nobst = nullptr;  // [pool_n]
-    // double-buffered storage behind the pointers above: a new pool is uploaded (asynchronously, from pinned staging) into the
-    // set the step kernels are NOT reading and swapped in by stream order (hope_env_pool_staging / hope_env_commit_pool)
-    struct PoolSet { double* verts = nullptr; double* c = nullptr; int32_t* nobst = nullptr; int32_t* list[2] = {nullptr, nullptr}; int cap = 0, list_cap = 0;
-                     // curriculum labels of the set's entries (device table: written while the curriculum is on)
-                     uint8_t* label = nullptr;
-                     int n_pool = 0, npool_cls[2] = {0, 0};    // entries, and the pool entries (without the cases) at the head of list[c]
-                     int lab_kind = 0;                         // 0: all unlabelled, 1: generated (gen_counts lots per level, in order), 2: lab_host
-                     int gen_counts[3] = {0, 0, 0};
-                     std::vector<uint8_t> lab_host;            // hope_env_set_pool_buckets
-                     int32_t* sorted_own[2] = {nullptr, nullptr}; int sorted_own_cap = 0; };   // lab_kind 2: list[c]'s pool entries ordered by label
-    PoolSet pset[2];
-    int pactive = -1;
-    struct PoolStage { double* start = nullptr; double* dest = nullptr; double* bbox = nullptr; double* verts = nullptr; int32_t* nobst = nullptr;
-                       int32_t* list = nullptr; int cap = 0; bool busy = false;
-                       bool staged = false; };   // staged: handed out by hope_env_pool_staging, not committed yet
-    PoolStage pstage;                            // pinned host memory
-    double* pstage_dev = nullptr;                // device staging of start | dest | bbox
-    // hope_env_generate_pool: n_obst of a generated set travels back through the set's own pinned array, asynchronously on pool_stream;
-    // pool_nobst_host takes it over lazily, when somebody needs it (settle_gen_nobst: refresh_pool_lists_sync), so that no call
-    // waits for the generator.  gen_host_set: the ACTIVE set if its host copy is still outstanding, else -1.
-    int32_t* gen_nobst[2] = {nullptr, nullptr};
-    int gen_nobst_cap[2] = {0, 0}, gen_nobst_n[2] = {0, 0};
-    hipEvent_t ev_gen_copied[2] = {nullptr, nullptr};
-    int gen_host_set = -1;
-    int pstage_dev_cap = 0;
-    hipStream_t pool_stream = nullptr;
-    hipEvent_t ev_pool_ready = nullptr, ev_pool_copied = nullptr, ev_last_step = nullptr;
-    bool pool_wait_pending = false;
-    // hope_env_commit_pool_relaxed: the uploaded set takes over once ev_pool_ready has passed (apply_pending_pool)
-    struct PendingPool { bool on = false, generated = false; int set = 0, n_pool = 0, cls_n[2] = {0, 0}; uint64_t content = 0; std::vector<int32_t> nobst_host; } pend;
-    int32_t* pool_cls[2] = {nullptr, nullptr};   // pool entries of each tile class
-    int pool_cls_n[2] = {0, 0};
-    std::vector<int32_t> pool_nobst_host;        // n_obst of the pool's complete scenes (class lists are rebuilt from it)
-    // Dragon-Lake-Parking cases drawn on the device (hope_env_set_dlp_cases)
-    DlpCases dlp = {};
-    void* dlp_mem[6] = {};
-    int32_t* pool_overflow = nullptr;            // [1] device counter: draws truncated to max_obst obstacles
-    int32_t* cur_pool = nullptr;    // [n] pool entry a scene currently holds (-1: uploaded by set_scenes; -1 - c... see hope_env.h)
-    uint32_t* episode = nullptr;    // [n] redraw counter (part of the draw's hash)
-    // HOPE_F_OVERLAP: the two tile classes' launches go to library streams, one per role (fork / join with events)
-    static constexpr int MAX_CHAIN = 2;                     // launch chains of a step: one per tile class, or two sub-chains of one class
-    hipStream_t side[N_ROLES] = {};                         // stream of each role ([ROLE_CALLER] unused: the caller's stream)
-    hipEvent_t ev_fork = nullptr, ev_step[MAX_CHAIN] = {}, ev_segs[MAX_CHAIN] = {}, ev_post[MAX_CHAIN] = {};
-    hipEvent_t ev_chain1_done = nullptr, ev_image_done = nullptr, ev_obs_done[MAX_CHAIN] = {}, ev_search0_done = nullptr;
-    hipEvent_t ev_collect = nullptr;                        // round 6: ONE join point for the caller's stream (the library stream of the other chain's observation collects the rest)
-    bool last_via_steps = false;                            // the last step recorded ev_step[0 / 1] behind both motion launches (the pool's only readers)
-    hipEvent_t ev_bev[2] = {};                              // image: fork / join of the static-layer rebuild next to k_bev_prep
-    int rs_parity = 0;                                      // which of the two queue counters of a chain this step uses (pipelined steps)
-    int queue_of_role[N_ROLES] = {-1, -1, -1, -1, -1, -1, -1, -1};   // measured hardware-queue class of role r's stream ([0]: the NULL stream)
-    int n_queues = 0;
-    double queue_check_ms = 0.0;
-    // curriculum for new-map draws (hope_curriculum_kernel.h): device tally + weighted draw lists, double-buffered like the pool sets
-    struct Curriculum {
-        bool on = false;
-        hope_curriculum_params P = {};
-        int n_cases = 0, nb = 0;
-        void* mem = nullptr;                                // the arrays of `dev`
-        CwDev dev = {};
-        uint8_t* scene_bucket = nullptr;                    // [n] bucket of the map a scene holds
-        uint32_t* noted_ep = nullptr;                       // [n] the scene's redraw counter when that bucket was noted
-        int32_t* wl[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [buffer][class][CW_LIST_LEN]
-        int32_t* prefix[2] = {nullptr, nullptr};            // [buffer][2][CW_MAX_GROUPS + 1]
-        int wactive = -1;                                   // buffer the next step reads
-        CwClass cls[2] = {};                                // what the active buffer's lists are made of
-        uint64_t updates = 0;
-        hipEvent_t ev_order = nullptr;
-    } cur;
-    int draw_set = -1;                                      // pool set the last step / hope_env_redraw drew from
-    // replay of found Reeds-Shepp paths (hope_planner_kernel.h): [PL_WORDS][n] state words, nullptr while the planner is off
-    struct Planner { bool on = false; double step_ratio = HOPE_PLAN_STEP_RATIO; uint64_t* state = nullptr; } plan;
-    // masked choice of the discrete action (hope_chooser_kernel.h): the [42][2] action table, nullptr while the chooser is off
-    struct Chooser { bool on = false; double* actions = nullptr; } choose;
-    // normalisation of the observations (hope_obsnorm_kernel.h): state = mean | S | std ([3][125] doubles), part = the chunk partials
-    // ([125][3][stride]); n_state lives here, on the host, and reaches the kernels as an argument
-    struct ObsNorm { bool on = false; int64_t n_state = 0; long long stride = 0; double* state = nullptr; double* part = nullptr; } onorm;
-    // bookkeeping of an evaluation run (hope_evaltrack_kernel.h): [ET_WORDS][n] state words, nullptr while it is off; the action box
-    // of the stuck detector's draw reaches k_eval_override as an argument
-    struct EvalTrack { bool on = false; EtBox box = {}; uint64_t* state = nullptr; } evalt;
-    // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
-    bool rs_pending = false;
-};
-
-
-// Live handles: hope_env_destroy on a pointer that is not (or no longer) a handle, and the hot entry points on a destroyed one, fail
-// with HOPE_EINVAL instead of touching freed memory (a ~50 ns set lookup per call next to ~15 launches).
 #include <mutex>
 #include <unordered_set>
 static std::mutex g_live_m;
 static std::unordered_set<const void*> g_live;
-static bool is_live(const void* h) {
+bool hope::is_live(const void* h) {
     std::lock_guard<std::mutex> lk(g_live_m);
     return h && g_live.count(h) != 0;
 }
-
-// every entry point runs on the handle's device and puts the caller's current device back (a process that drives
-// several GPUs keeps PyTorch's notion of the current device)
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; else prev = -1;
-    }
-    ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
-};
 
 static hipEvent_t get_event(hope_env* h) {
     if (!h->free_events.empty()) { hipEvent_t e = h->free_events.back(); h->free_events.pop_back(); return e; }
@@ -664,18 +470,16 @@ static void launch_env_step(bool of64, bool af64, dim3 grid, dim3 block, size_t 
     else hipLaunchKernelGGL((k_env_step<float, float, false, PART, FKIN>), grid, block, lds, sc, p);
 }
 
-extern "C" {
-
 // HOPE_DEFER_RS bookkeeping: `s` waits for the chains the last step left unjoined / the host does
-static int join_rs(hope_env_t* h, hipStream_t s) {
+int hope::join_rs(hope_env_t* h, hipStream_t s) {
     if (!h->rs_pending) return HOPE_OK;
     HIPCHK(hipStreamWaitEvent(s, h->ev_chain1_done, 0));
     HIPCHK(hipStreamWaitEvent(s, h->ev_search0_done, 0));
     h->rs_pending = false;
     return HOPE_OK;
 }
-static int settle_rs(hope_env_t* h) {
-    if (!h || !h->rs_pending) return HOPE_OK;
+int hope::settle_rs(hope_env_t* h) {
+    if (!h->rs_pending) return HOPE_OK;
     DeviceGuard guard(h->device);
     HIPCHK(hipEventSynchronize(h->ev_chain1_done));
     HIPCHK(hipEventSynchronize(h->ev_search0_done));
@@ -683,15 +487,13 @@ static int settle_rs(hope_env_t* h) {
     return HOPE_OK;
 }
 
+extern "C" {
+
 const char* hope_last_error(void) { return g_err.c_str(); }
 int hope_abi_version(void) { return HOPE_ABI_VERSION; }
 
 static int destroy_impl(hope_env_t* h);
 static void cur_free(hope_env_t* h);
-static void plan_free(hope_env_t* h);
-static void choose_free(hope_env_t* h);
-static void onorm_free(hope_env_t* h);
-static void evalt_free(hope_env_t* h);
 int hope_env_create(hope_env_t** out, int n_scenes, int max_obstacles, int device_id, uint32_t flags) {
     if (!out || n_scenes <= 0 || max_obstacles <= 0) return fail(HOPE_EINVAL, "hope_env_create: bad argument");
     if (flags & 0x20)
@@ -935,7 +737,7 @@ int hope_env_destroy(hope_env_t* h) {
     if (!h) return HOPE_OK;
     {
         std::lock_guard<std::mutex> lk(g_live_m);
-        if (g_live.erase(h) == 0) return fail(HOPE_EINVAL, "hope_env_destroy: not a live handle (destroyed twice?)");
+        if (g_live.erase(h) == 0) return fail(HOPE_EINVAL, HOPE_NOT_LIVE("hope_env_destroy", "destroyed twice?"));
     }
     return destroy_impl(h);
 }
@@ -1022,455 +824,18 @@ int hope_debug_rs_log(int32_t* out, int cap, int32_t* n, int reset) {
 }
 
 int hope_env_queue_check(hope_env_t* h, int32_t* queue_of_role, int32_t* n_queues, double* ms) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_queue_check: null handle");
+    HOPE_ENTER(h, "hope_env_queue_check");
     if (queue_of_role) for (int r = 0; r < N_ROLES; r++) queue_of_role[r] = h->queue_of_role[r];
     if (n_queues) *n_queues = h->n_queues;
     if (ms) *ms = h->queue_check_ms;
     return HOPE_OK;
 }
 
-// ---- replay of found Reeds-Shepp paths (include/hope_env.h; kernel: hope_planner_kernel.h, rule: hope_planner_core.h) ----
-static void plan_free(hope_env_t* h) {
-    if (h->plan.state) hipFree(h->plan.state);
-    h->plan = hope_env::Planner{};
-}
-
-int hope_env_planner_enable(hope_env_t* h, double step_ratio) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_enable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_enable: not a live handle (destroyed?)");
-    if (step_ratio != step_ratio || !pl_finite(step_ratio)) return fail(HOPE_EINVAL, "hope_env_planner_enable: step_ratio is not finite");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());                         // planner steps in flight read the state
-    const size_t bytes = (size_t)PL_WORDS * h->n * sizeof(uint64_t);
-    if (!h->plan.state) {
-        hipError_t e_ = hipMalloc((void**)&h->plan.state, bytes);
-        if (e_ != hipSuccess) { h->plan.state = nullptr; return fail(HOPE_ENOMEM, std::string("hope_env_planner_enable: ") + hipGetErrorString(e_)); }
-    }
-    HIPCHK(hipMemset(h->plan.state, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
-    h->plan.step_ratio = step_ratio > 0.0 ? step_ratio : HOPE_PLAN_STEP_RATIO;
-    h->plan.on = true;
-    return HOPE_OK;
-}
-
-int hope_env_planner_disable(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_disable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_disable: not a live handle (destroyed?)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    plan_free(h);
-    return HOPE_OK;
-}
-
-int hope_env_planner_reset(hope_env_t* h, const uint8_t* mask, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_reset: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_reset: not a live handle (destroyed?)");
-    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_reset: the planner is off (hope_env_planner_enable first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    if (!mask) {
-        HIPCHK(hipMemsetAsync(h->plan.state, 0, (size_t)PL_WORDS * h->n * sizeof(uint64_t), (hipStream_t)stream));
-        return HOPE_OK;
-    }
-    hipLaunchKernelGGL(k_plan_reset, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, mask, h->plan.state);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_env_planner_step(hope_env_t* h, const int8_t* rs_word, const void* rs_lengths, const uint8_t* done, int forced, uint64_t step,
-                          double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_planner_step: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_step: not a live handle (destroyed?)");
-    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_step: the planner is off (hope_env_planner_enable first)");
-    if (!rs_word || !rs_lengths) return fail(HOPE_EINVAL, "hope_env_planner_step: null rs_word / rs_lengths");
-    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_env_planner_step: unknown bit in `forced`");
-    const bool lf64 = h->flags & HOPE_F_OBS_F64;
-    if (((uintptr_t)rs_word & 7) || ((uintptr_t)rs_lengths & (lf64 ? 7 : 3)) || ((uintptr_t)planned_out & 15) ||
-        ((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)))
-        return fail(HOPE_EINVAL, "hope_env_planner_step: misaligned buffer (rs_word 8, planned_out 16, actions 8 / 16 bytes)");
-    if (step != 0) {                                        // hope_env_wait_rs_step, before anything is touched
-        if (step > h->step_seq) return fail(HOPE_EINVAL, "hope_env_planner_step: no such step (hope_env_last_step)");
-        if (step != h->step_seq)
-            return fail(HOPE_ESTATE, "hope_env_planner_step: step " + std::to_string(step) + " is not the last one (" + std::to_string(h->step_seq) +
-                                     "): a later hope_env_step / hope_env_reset_obs has replaced its Reeds-Shepp outputs -- plan before enqueuing the next step");
-    }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    if (step != 0) { int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
-    hipLaunchKernelGGL(k_plan, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)rs_word, rs_lengths, lf64 ? 1 : 0, done,
-                       forced, h->plan.step_ratio, h->plan.state, (double2*)planned_out, executing_out, actions_inout, action_is_f64 ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_planner_step_host(int n, double step_ratio, void* state, const int8_t* rs_word, const void* rs_lengths, int lengths_f64,
-                           const uint8_t* done, int forced, double* planned_out, uint8_t* executing_out, void* actions_inout, int action_is_f64) {
-    if (forced & ~(HOPE_PLAN_FORCED | HOPE_PLAN_NO_POP)) return fail(HOPE_EINVAL, "hope_planner_step_host: unknown bit in `forced`");
-    const int rc = pl_step_host(n, step_ratio > 0.0 ? step_ratio : (step_ratio == 0.0 ? HOPE_PLAN_STEP_RATIO : step_ratio), state, rs_word, rs_lengths, lengths_f64,
-                                done, forced, planned_out, executing_out, actions_inout, action_is_f64);
-    if (rc != HOPE_OK) return fail(rc, "hope_planner_step_host: bad argument (n <= 0, a null state / rs_word / rs_lengths, or a step_ratio that is not positive and finite)");
-    return HOPE_OK;
-}
-
-int hope_env_planner_download_state(hope_env_t* h, void* state_out) {
-    if (!h || !state_out) return fail(HOPE_EINVAL, "hope_env_planner_download_state: null argument");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_planner_download_state: not a live handle (destroyed?)");
-    if (!h->plan.on) return fail(HOPE_ESTATE, "hope_env_planner_download_state: the planner is off (hope_env_planner_enable first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(state_out, h->plan.state, (size_t)PL_WORDS * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return HOPE_OK;
-}
-
-// ---- masked choice of the discrete action (include/hope_env.h; kernel: hope_chooser_kernel.h, rule: hope_chooser_core.h) ----
-static void choose_free(hope_env_t* h) {
-    if (h->choose.actions) hipFree(h->choose.actions);
-    h->choose = hope_env::Chooser{};
-}
-
-int hope_env_chooser_enable(hope_env_t* h, const double* actions) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_chooser_enable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_chooser_enable: not a live handle (destroyed?)");
-    if (!actions) return fail(HOPE_EINVAL, "hope_env_chooser_enable: null action table");
-    if (!ch_table_ok(actions))
-        return fail(HOPE_EINVAL, "hope_env_chooser_enable: the action table must be finite, rows 0..20 at one speed and rows 21..41 the same steers at another");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());                         // choices in flight read the table
-    const size_t bytes = (size_t)CH_NA * 2 * sizeof(double);
-    if (!h->choose.actions) {
-        hipError_t e_ = hipMalloc((void**)&h->choose.actions, bytes);
-        if (e_ != hipSuccess) { h->choose.actions = nullptr; return fail(HOPE_ENOMEM, std::string("hope_env_chooser_enable: ") + hipGetErrorString(e_)); }
-    }
-    HIPCHK(hipMemcpy(h->choose.actions, actions, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    h->choose.on = true;
-    return HOPE_OK;
-}
-
-int hope_env_chooser_disable(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_chooser_disable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_chooser_disable: not a live handle (destroyed?)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    choose_free(h);
-    return HOPE_OK;
-}
-
-int hope_env_choose(hope_env_t* h, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, const double* planned,
-                    const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, void* action, float* action_f32, int32_t* idx,
-                    float* log_prob, double* probs, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_choose: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_choose: not a live handle (destroyed?)");
-    if (!h->choose.on) return fail(HOPE_ESTATE, "hope_env_choose: the chooser is off (hope_env_chooser_enable first)");
-    if (!mean || !log_std || !mask || !action) return fail(HOPE_EINVAL, "hope_env_choose: null mean / log_std / mask / action");
-    if ((planned != nullptr) != (executing != nullptr)) return fail(HOPE_EINVAL, "hope_env_choose: planned and executing go together");
-    if (log_std_row_stride != 0 && log_std_row_stride != 2) return fail(HOPE_EINVAL, "hope_env_choose: log_std_row_stride is 0 (one row for all) or 2");
-    const bool mf64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
-    if (((uintptr_t)mean & (in_f64 ? 15 : 7)) || ((uintptr_t)log_std & (in_f64 ? 7 : 3)) || ((uintptr_t)mask & (mf64 ? 7 : 3)) || ((uintptr_t)planned & 15) ||
-        ((uintptr_t)u & 7) || ((uintptr_t)action & (af64 ? 15 : 7)) || ((uintptr_t)action_f32 & 7) || ((uintptr_t)idx & 3) || ((uintptr_t)log_prob & 7) ||
-        ((uintptr_t)probs & 7))
-        return fail(HOPE_EINVAL, "hope_env_choose: misaligned buffer (mean and action rows 8 / 16, planned 16, action_f32 and log_prob 8 bytes, the others their element)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    const dim3 grid((h->n + 63) / 64), block(64);
-    if (mf64)
-        hipLaunchKernelGGL(k_choose<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
-                           in_f64 ? 1 : 0, (const double*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
-                           (int*)idx, (float2*)log_prob, probs);
-    else
-        hipLaunchKernelGGL(k_choose<float>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)h->choose.actions, mean, log_std, log_std_row_stride,
-                           in_f64 ? 1 : 0, (const float*)mask, (const double2*)planned, executing, u, seed, counter, action, af64 ? 1 : 0, (float2*)action_f32,
-                           (int*)idx, (float2*)log_prob, probs);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_chooser_host(int n, const double* actions, const void* mean, const void* log_std, int log_std_row_stride, int in_f64, const void* mask, int mask_f64,
-                      const double* planned, const uint8_t* executing, const double* u, uint64_t seed, uint64_t counter, uint64_t scene0, void* action,
-                      int action_f64, float* action_f32, int32_t* idx, float* log_prob, double* probs) {
-    const int rc = ch_host(n, actions, mean, log_std, log_std_row_stride, in_f64, mask, mask_f64, planned, executing, u, seed, counter, scene0, action, action_f64,
-                           action_f32, idx, log_prob, probs);
-    if (rc != HOPE_OK)
-        return fail(rc, "hope_chooser_host: bad argument (n <= 0, a null actions / mean / log_std / mask / action, planned without executing or the reverse, a stride other than 0 / 2, or an action table that is not 21 steers x 2 speeds)");
-    return HOPE_OK;
-}
-
-// ---- normalisation of the observations (include/hope_env.h; kernels: hope_obsnorm_kernel.h, rule: hope_obsnorm_core.h) ----
-static void onorm_free(hope_env_t* h) {
-    if (h->onorm.state) hipFree(h->onorm.state);
-    if (h->onorm.part) hipFree(h->onorm.part);
-    h->onorm = hope_env::ObsNorm{};
-}
-
-int hope_env_obsnorm_enable(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_enable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_enable: not a live handle (destroyed?)");
-    if (h->onorm.on) return HOPE_OK;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    const long long stride = (h->n + ON_CHUNK - 1) / ON_CHUNK;
-    const size_t sbytes = (size_t)3 * ON_NC * sizeof(double), pbytes = sbytes * (size_t)stride;
-    double *st = nullptr, *pt = nullptr;
-    hipError_t e_ = hipMalloc((void**)&st, sbytes);
-    if (e_ == hipSuccess) e_ = hipMalloc((void**)&pt, pbytes);
-    if (e_ == hipSuccess) e_ = hipMemset(st, 0, sbytes);
-    if (e_ == hipSuccess) e_ = hipMemset(pt, 0, pbytes);
-    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
-    if (e_ != hipSuccess) {
-        if (st) hipFree(st);
-        if (pt) hipFree(pt);
-        return fail(HOPE_ENOMEM, std::string("hope_env_obsnorm_enable: ") + hipGetErrorString(e_));
-    }
-    h->onorm.state = st; h->onorm.part = pt; h->onorm.stride = stride; h->onorm.n_state = 0; h->onorm.on = true;
-    return HOPE_OK;
-}
-
-int hope_env_obsnorm_disable(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_disable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_disable: not a live handle (destroyed?)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    onorm_free(h);
-    return HOPE_OK;
-}
-
-int hope_env_obsnorm_set(hope_env_t* h, int64_t n_state, const double* mean, const double* S, const double* std_) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: not a live handle (destroyed?)");
-    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm_set: the normalisation is off (hope_env_obsnorm_enable first)");
-    if (!mean || !S || !std_ || n_state < 0) return fail(HOPE_EINVAL, "hope_env_obsnorm_set: null mean / S / std or a negative n_state");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());                         // calls in flight read and write the statistics
-    const size_t b = (size_t)ON_NC * sizeof(double);
-    HIPCHK(hipMemcpy(h->onorm.state, mean, b, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->onorm.state + ON_NC, S, b, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->onorm.state + 2 * ON_NC, std_, b, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    h->onorm.n_state = n_state;
-    return HOPE_OK;
-}
-
-int hope_env_obsnorm_get(hope_env_t* h, int64_t* n_state, double* mean, double* S, double* std_) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm_get: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm_get: not a live handle (destroyed?)");
-    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm_get: the normalisation is off (hope_env_obsnorm_enable first)");
-    if (n_state) *n_state = h->onorm.n_state;
-    if (!mean && !S && !std_) return HOPE_OK;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    const size_t b = (size_t)ON_NC * sizeof(double);
-    if (mean) HIPCHK(hipMemcpy(mean, h->onorm.state, b, hipMemcpyDeviceToHost));
-    if (S) HIPCHK(hipMemcpy(S, h->onorm.state + ON_NC, b, hipMemcpyDeviceToHost));
-    if (std_) HIPCHK(hipMemcpy(std_, h->onorm.state + 2 * ON_NC, b, hipMemcpyDeviceToHost));
-    return HOPE_OK;
-}
-
-}  // extern "C" (a template has C++ linkage)
-template <class T>
-static void onorm_launch(hope_env_t* h, const T* lidar, const T* target, int rows, uint32_t flags, float* out_lidar, float* out_target, hipStream_t st) {
-    hope_env::ObsNorm& o = h->onorm;
-    if (flags & HOPE_OBSNORM_UPDATE) {
-        const int first = o.n_state == 0 ? 1 : 0;
-        const long long m = (long long)rows - first, nk = on_chunks(m);      // nk <= stride: rows <= N
-        if (nk > 0)
-            hipLaunchKernelGGL(k_obsnorm_partial<T>, dim3((unsigned)nk, 2), dim3(64), 0, st, lidar, target, (long long)first, m, o.stride, o.part);
-        hipLaunchKernelGGL(k_obsnorm_merge<T>, dim3(ON_NC), dim3(64), 0, st, lidar, target, first, (long long)o.n_state, nk, o.stride, o.part, o.state);
-        o.n_state += rows;
-    }
-    if (flags & HOPE_OBSNORM_NORMALIZE) {
-        const size_t total = (size_t)rows * ON_NC;
-        hipLaunchKernelGGL(k_obsnorm_apply<T>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, lidar, target, (long long)rows, (const double*)o.state,
-                           out_lidar, out_target);
-    }
-}
-
-extern "C" {
-int hope_env_obsnorm(hope_env_t* h, const void* lidar, const void* target, int rows, int in_f64, uint32_t flags, float* out_lidar, float* out_target,
-                     void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_obsnorm: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_obsnorm: not a live handle (destroyed?)");
-    if (!h->onorm.on) return fail(HOPE_ESTATE, "hope_env_obsnorm: the normalisation is off (hope_env_obsnorm_enable first)");
-    if (!lidar || !target) return fail(HOPE_EINVAL, "hope_env_obsnorm: null lidar / target");
-    if (rows < 1 || rows > h->n) return fail(HOPE_EINVAL, "hope_env_obsnorm: rows must be 1 .. the handle's scenes");
-    if (!(flags & (HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)) || (flags & ~(uint32_t)(HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE)))
-        return fail(HOPE_EINVAL, "hope_env_obsnorm: flags are HOPE_OBSNORM_UPDATE | HOPE_OBSNORM_NORMALIZE, at least one");
-    const bool norm = flags & HOPE_OBSNORM_NORMALIZE;
-    if (norm && (!out_lidar || !out_target)) return fail(HOPE_EINVAL, "hope_env_obsnorm: HOPE_OBSNORM_NORMALIZE needs out_lidar and out_target");
-    const uintptr_t am = in_f64 ? 7 : 3;
-    if (((uintptr_t)lidar & am) || ((uintptr_t)target & am) || (norm && (((uintptr_t)out_lidar & 3) || ((uintptr_t)out_target & 3))))
-        return fail(HOPE_EINVAL, "hope_env_obsnorm: misaligned buffer (each aligned to its element)");
-    if ((size_t)rows * ON_NC > (size_t)0x7FFFFFFF * 64) return fail(HOPE_EINVAL, "hope_env_obsnorm: too many rows for one launch");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    if (in_f64) onorm_launch(h, (const double*)lidar, (const double*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
-    else onorm_launch(h, (const float*)lidar, (const float*)target, rows, flags, out_lidar, out_target, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_obsnorm_host(hope_obsnorm_state* state, const void* lidar, const void* target, int64_t rows, int in_f64, uint32_t flags, float* out_lidar,
-                      float* out_target) {
-    const int rc = on_host(state, lidar, target, rows, in_f64, flags, out_lidar, out_target);
-    if (rc == HOPE_ENOMEM) return fail(rc, "hope_obsnorm_host: out of memory for the chunk partials");
-    if (rc != HOPE_OK)
-        return fail(rc, "hope_obsnorm_host: bad argument (a null state / lidar / target, rows < 1, a negative n_state, no or an unknown flag, or NORMALIZE without both outputs)");
-    return HOPE_OK;
-}
-
-// ---- bookkeeping of an evaluation run (include/hope_env.h; kernels: hope_evaltrack_kernel.h, rule: hope_evaltrack_core.h) ----
-static void evalt_free(hope_env_t* h) {
-    if (h->evalt.state) hipFree(h->evalt.state);
-    h->evalt = hope_env::EvalTrack{};
-}
-
-int hope_env_eval_enable(hope_env_t* h, const double* box) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_enable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_enable: not a live handle (destroyed?)");
-    if (!et_box_ok(box)) return fail(HOPE_EINVAL, "hope_env_eval_enable: the action box is null or not finite (steer lo, steer hi, speed lo, speed hi)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());                         // calls in flight read the box as it was
-    if (!h->evalt.state) {
-        const size_t bytes = (size_t)ET_WORDS * h->n * sizeof(uint64_t);
-        uint64_t* st = nullptr;
-        hipError_t e_ = hipMalloc((void**)&st, bytes);
-        if (e_ == hipSuccess) e_ = hipMemset(st, 0, bytes);
-        if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
-        if (e_ != hipSuccess) {
-            if (st) hipFree(st);
-            return fail(HOPE_ENOMEM, std::string("hope_env_eval_enable: ") + hipGetErrorString(e_));
-        }
-        h->evalt.state = st;
-    }
-    h->evalt.box = et_box(box);
-    h->evalt.on = true;
-    return HOPE_OK;
-}
-
-int hope_env_eval_disable(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_disable: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_disable: not a live handle (destroyed?)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    evalt_free(h);
-    return HOPE_OK;
-}
-
-int hope_env_eval_begin(hope_env_t* h, const void* target, const double* pose, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_begin: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_begin: not a live handle (destroyed?)");
-    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_begin: the evaluation tracker is off (hope_env_eval_enable first)");
-    if (!target || !pose) return fail(HOPE_EINVAL, "hope_env_eval_begin: null target / pose");
-    const bool of64 = h->flags & HOPE_F_OBS_F64;
-    if (((uintptr_t)target & (of64 ? 7 : 3)) || ((uintptr_t)pose & 7)) return fail(HOPE_EINVAL, "hope_env_eval_begin: misaligned buffer (each aligned to its element)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    const dim3 grid((h->n + 63) / 64), block(64);
-    if (of64) hipLaunchKernelGGL(k_eval_begin<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, h->evalt.state);
-    else hipLaunchKernelGGL(k_eval_begin<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, h->evalt.state);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_env_eval_override(hope_env_t* h, void* actions_inout, int action_is_f64, const double* u, uint64_t seed, uint64_t counter, uint8_t* active_out,
-                           void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_override: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_override: not a live handle (destroyed?)");
-    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_override: the evaluation tracker is off (hope_env_eval_enable first)");
-    if (!actions_inout || !active_out) return fail(HOPE_EINVAL, "hope_env_eval_override: null actions / active_out");
-    if (((uintptr_t)actions_inout & (action_is_f64 ? 15 : 7)) || ((uintptr_t)u & 7))
-        return fail(HOPE_EINVAL, "hope_env_eval_override: misaligned buffer (actions 8 / 16 bytes, u 8 bytes)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(k_eval_override, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, h->evalt.box,
-                       actions_inout, action_is_f64 ? 1 : 0, u, seed, counter, active_out);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_env_eval_track(hope_env_t* h, const void* target, const double* pose, const void* reward, const int32_t* status, const uint8_t* done,
-                        const int8_t* rs_word, int8_t* word_out, uint8_t* done_out, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_track: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_track: not a live handle (destroyed?)");
-    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_track: the evaluation tracker is off (hope_env_eval_enable first)");
-    if (!target || !pose || !reward || !status || !done || !rs_word || !word_out || !done_out)
-        return fail(HOPE_EINVAL, "hope_env_eval_track: null target / pose / reward / status / done / rs_word / word_out / done_out");
-    const bool of64 = h->flags & HOPE_F_OBS_F64;
-    const uintptr_t om = of64 ? 7 : 3;
-    if (((uintptr_t)target & om) || ((uintptr_t)reward & om) || ((uintptr_t)pose & 7) || ((uintptr_t)status & 3) || ((uintptr_t)rs_word & 7) ||
-        ((uintptr_t)word_out & 7))
-        return fail(HOPE_EINVAL, "hope_env_eval_track: misaligned buffer (rs_word and word_out 8 bytes, the others their element)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    const dim3 grid((h->n + 63) / 64), block(64);
-    if (of64)
-        hipLaunchKernelGGL(k_eval_track<double>, grid, block, 0, (hipStream_t)stream, h->n, (const double*)target, pose, (const double*)reward, status, done,
-                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
-    else
-        hipLaunchKernelGGL(k_eval_track<float>, grid, block, 0, (hipStream_t)stream, h->n, (const float*)target, pose, (const float*)reward, status, done,
-                           (const uint64_t*)rs_word, h->evalt.state, (uint64_t*)word_out, done_out);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_env_eval_records(hope_env_t* h, float* rec_out, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_eval_records: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_records: not a live handle (destroyed?)");
-    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_records: the evaluation tracker is off (hope_env_eval_enable first)");
-    if (!rec_out) return fail(HOPE_EINVAL, "hope_env_eval_records: null rec_out");
-    if ((uintptr_t)rec_out & 15) return fail(HOPE_EINVAL, "hope_env_eval_records: misaligned buffer (rec_out 16 bytes)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(k_eval_records, dim3((h->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->n, (const uint64_t*)h->evalt.state, (float4*)rec_out);
-    HIPCHK(hipGetLastError());
-    return HOPE_OK;
-}
-
-int hope_env_eval_download_state(hope_env_t* h, void* state_out) {
-    if (!h || !state_out) return fail(HOPE_EINVAL, "hope_env_eval_download_state: null argument");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_eval_download_state: not a live handle (destroyed?)");
-    if (!h->evalt.on) return fail(HOPE_ESTATE, "hope_env_eval_download_state: the evaluation tracker is off (hope_env_eval_enable first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(state_out, h->evalt.state, (size_t)ET_WORDS * h->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return HOPE_OK;
-}
-
-int hope_eval_begin_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose) {
-    const int rc = et_begin_host(n, state_stride, state, target, obs_f64, pose);
-    if (rc != HOPE_OK) return fail(rc, "hope_eval_begin_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose)");
-    return HOPE_OK;
-}
-
-int hope_eval_override_host(int64_t n, int64_t state_stride, const void* state, const double* box, void* actions_inout, int action_is_f64, const double* u,
-                            uint64_t seed, uint64_t counter, uint64_t scene0, uint8_t* active_out) {
-    const int rc = et_override_host(n, state_stride, state, box, actions_inout, action_is_f64, u, seed, counter, scene0, active_out);
-    if (rc != HOPE_OK)
-        return fail(rc, "hope_eval_override_host: bad argument (n <= 0, state_stride < n, a null state / actions / active_out, or a box that is null or not finite)");
-    return HOPE_OK;
-}
-
-int hope_eval_track_host(int64_t n, int64_t state_stride, void* state, const void* target, int obs_f64, const double* pose, const void* reward,
-                         const int32_t* status, const uint8_t* done, const int8_t* rs_word, int8_t* word_out, uint8_t* done_out) {
-    const int rc = et_track_host(n, state_stride, state, target, obs_f64, pose, reward, status, done, rs_word, word_out, done_out);
-    if (rc != HOPE_OK)
-        return fail(rc, "hope_eval_track_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose / reward / status / done / rs_word / word_out / done_out)");
-    return HOPE_OK;
-}
-
-int hope_env_num_scenes(const hope_env_t* h) { return h ? h->n : HOPE_EINVAL; }
-int hope_env_max_obstacles(const hope_env_t* h) { return h ? h->max_obst : HOPE_EINVAL; }
-const char* hope_env_device_arch(const hope_env_t* h) { return h ? h->arch : ""; }
+// the getters keep their return conventions (HOPE_EINVAL / ""); a pointer that is neither NULL nor a handle hope_env_create returned also leaves the message
+#define NOT_LIVE(h, name) ((h) ? fail(HOPE_EINVAL, HOPE_NOT_LIVE(name, "destroyed?")) : HOPE_EINVAL)
+int hope_env_num_scenes(const hope_env_t* h) { return is_live(h) ? h->n : NOT_LIVE(h, "hope_env_num_scenes"); }
+int hope_env_max_obstacles(const hope_env_t* h) { return is_live(h) ? h->max_obst : NOT_LIVE(h, "hope_env_max_obstacles"); }
+const char* hope_env_device_arch(const hope_env_t* h) { return is_live(h) ? h->arch : (NOT_LIVE(h, "hope_env_device_arch"), ""); }
 
 // Count-interval table of the action mask's coarse beams (round 6; read by k_obs_pair's mask stage).  The scan value x of coarse beam i
 // falls into bin b = floor((x - lo_i) scale_i), lo_i = hull_base_i - 1e-6 (x >= hull_base_i always); the MASK_LUT_NB bins reach to the
@@ -1539,9 +904,9 @@ int hope_debug_mask_lut(const double* dist_star, const double* hull_base, uint16
 }
 
 int hope_env_upload_tables(hope_env_t* h, const double* dist_star, const double* hull_base, const double* beam_ab) {
-    if (!h || !dist_star || !hull_base || !beam_ab) return fail(HOPE_EINVAL, "hope_env_upload_tables: null argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ENTER_AS(h, "hope_env_upload_tables", "null argument");
+    if (!dist_star || !hull_base || !beam_ab) return fail(HOPE_EINVAL, "hope_env_upload_tables: null argument");
+    HOPE_ON_DEVICE(h);
     std::vector<double> tab, pmax;
     build_mask_tab(dist_star, tab, pmax);
     HIPCHK(hipMemcpy(h->tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1600,17 +965,16 @@ static int rebuild_class_lists(hope_env_t* h) {
 
 int hope_env_set_scenes(hope_env_t* h, const int32_t* scene_ids, int n, const double* start, const double* dest,
                         const double* bbox, const double* verts, const int32_t* n_obst) {
+    HOPE_ENTER_AS(h, "hope_env_set_scenes", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || n < 0 || (n > 0 && (!scene_ids || !start || !dest || !bbox || !n_obst)))
-        return fail(HOPE_EINVAL, "hope_env_set_scenes: null argument");
+    if (n < 0 || (n > 0 && (!scene_ids || !start || !dest || !bbox || !n_obst))) return fail(HOPE_EINVAL, "hope_env_set_scenes: null argument");
     if (n == 0) return HOPE_OK;
     for (int k = 0; k < n; k++) {
         if (scene_ids[k] < 0 || scene_ids[k] >= h->n) return fail(HOPE_EINVAL, "hope_env_set_scenes: scene id out of range");
         if (n_obst[k] < 0 || n_obst[k] > h->max_obst) return fail(HOPE_EINVAL, "hope_env_set_scenes: n_obst exceeds max_obstacles");
         if (n_obst[k] > 0 && !verts) return fail(HOPE_EINVAL, "hope_env_set_scenes: verts is null");
     }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     {
         int rc = upload_scenes(h, scene_ids, n, start, dest, bbox, verts, n_obst, h->scene_c, h->state, h->tstep, h->n_obst,
                                h->verts, h->obb, h->traj, h->traj_len, h->traj_valid, h->layer_valid);
@@ -1963,8 +1327,7 @@ static int check_pool_classes(hope_env_t* h, const char* who) {
 
 static int launch_step(hope_env_t* h, const void* actions, const uint8_t* active, uint32_t stages,
                        const hope_step_out* out, void* stream, int has_action) {
-    if (!h || !out) return fail(HOPE_EINVAL, "hope_env_step: null argument");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_step: not a live handle (destroyed?)");
+    if (!out) return fail(HOPE_EINVAL, "hope_env_step: null argument");
     if (!h->have_tables) return fail(HOPE_ESTATE, "hope_env_step: hope_env_upload_tables has not been called");
     if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_step: hope_env_set_scenes has not been called");
     if (has_action && !actions) return fail(HOPE_EINVAL, "hope_env_step: actions is null");
@@ -1979,8 +1342,7 @@ static int launch_step(hope_env_t* h, const void* actions, const uint8_t* active
         if (!h->traj) return fail(HOPE_ESTATE, "hope_env_step: HOPE_STAGE_IMG needs a handle created with HOPE_F_IMAGE");
         if (!out->img) return fail(HOPE_EINVAL, "hope_env_step: HOPE_STAGE_IMG without out->img");
     }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
     const bool prof = h->flags & HOPE_F_PROFILE;
     h->step_seq++;
@@ -2106,9 +1468,9 @@ static int pool_set_reserve(hope_env_t* h, hope_env::PoolSet& ps, int n_pool, in
 }
 
 int hope_env_pool_staging(hope_env_t* h, int n_pool, double** start, double** dest, double** bbox, double** verts, int32_t** n_obst) {
-    if (!h || n_pool <= 0 || !start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_env_pool_staging: bad argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ENTER_AS(h, "hope_env_pool_staging", "bad argument");
+    if (n_pool <= 0 || !start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_env_pool_staging: bad argument");
+    HOPE_ON_DEVICE(h);
     int rc = pool_init_streams(h);
     if (rc != HOPE_OK) return rc;
     if (h->pstage.busy) { HIPCHK(hipEventSynchronize(h->ev_pool_copied)); h->pstage.busy = false; }   // the previous upload still reads it
@@ -2132,10 +1494,9 @@ int hope_env_pool_staging(hope_env_t* h, int n_pool, double** start, double** de
 }
 
 int hope_env_pool_staging_ready(hope_env_t* h) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_pool_staging_ready: null handle");
+    HOPE_ENTER(h, "hope_env_pool_staging_ready");
     if (!h->pstage.busy) return 1;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     const hipError_t e = hipEventQuery(h->ev_pool_copied);
     if (e == hipSuccess) { h->pstage.busy = false; return 1; }
     if (e == hipErrorNotReady) return 0;
@@ -2144,7 +1505,8 @@ int hope_env_pool_staging_ready(hope_env_t* h) {
 
 static int effective_generation(hope_env_t* h, uint64_t* generation);
 int hope_env_pool_generation(hope_env_t* h, uint64_t* generation) {
-    if (!h || !generation) return fail(HOPE_EINVAL, "hope_env_pool_generation: null argument");
+    HOPE_ENTER_AS(h, "hope_env_pool_generation", "null argument");
+    if (!generation) return fail(HOPE_EINVAL, "hope_env_pool_generation: null argument");
     { DeviceGuard guard(h->device); int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
     return effective_generation(h, generation);
 }
@@ -2182,17 +1544,23 @@ static int apply_pending_pool(hope_env_t* h, bool wait) {
 }
 
 static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed);
-int hope_env_commit_pool(hope_env_t* h, int n_pool, void* stream) { (void)stream; return commit_pool_impl(h, n_pool, false); }
-int hope_env_commit_pool_relaxed(hope_env_t* h, int n_pool) { return commit_pool_impl(h, n_pool, true); }
+int hope_env_commit_pool(hope_env_t* h, int n_pool, void* stream) {
+    (void)stream;
+    HOPE_ENTER_AS(h, "hope_env_commit_pool", "bad argument");
+    return commit_pool_impl(h, n_pool, false);
+}
+int hope_env_commit_pool_relaxed(hope_env_t* h, int n_pool) {
+    HOPE_ENTER_AS(h, "hope_env_commit_pool_relaxed", "bad argument");
+    return commit_pool_impl(h, n_pool, true);
+}
 
 static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
     // (no join of an unjoined Reeds-Shepp chain here: only the motion launches read the pool, and ev_last_step covers them)
-    if (!h || n_pool <= 0) return fail(HOPE_EINVAL, "hope_env_commit_pool: bad argument");
+    if (n_pool <= 0) return fail(HOPE_EINVAL, "hope_env_commit_pool: bad argument");
     if (n_pool > h->pstage.cap) return fail(HOPE_ESTATE, "hope_env_commit_pool: more entries than hope_env_pool_staging provided");
     for (int k = 0; k < n_pool; k++)
         if (h->pstage.nobst[k] < 0 || h->pstage.nobst[k] > h->max_obst) return fail(HOPE_EINVAL, "hope_env_commit_pool: n_obst exceeds max_obstacles");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     std::vector<int32_t> l0, l1;
     build_pool_lists(h, h->pstage.nobst, n_pool, l0, l1);
     if ((int)(l0.size() + l1.size()) > h->pstage.cap + 4096) return fail(HOPE_EINVAL, "hope_env_commit_pool: too many Dragon-Lake cases for the list staging");
@@ -2290,8 +1658,9 @@ static int commit_pool_impl(hope_env_t* h, int n_pool, bool relaxed) {
 
 int hope_env_set_pool(hope_env_t* h, int n_pool, const double* start, const double* dest, const double* bbox,
                       const double* verts, const int32_t* n_obst) {
+    HOPE_ENTER_AS(h, "hope_env_set_pool", "bad argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || n_pool <= 0 || !start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_env_set_pool: bad argument");
+    if (n_pool <= 0 || !start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_env_set_pool: bad argument");
     for (int k = 0; k < n_pool; k++)
         if (n_obst[k] < 0 || n_obst[k] > h->max_obst) return fail(HOPE_EINVAL, "hope_env_set_pool: n_obst exceeds max_obstacles");
     double *ps, *pd, *pb, *pv;
@@ -2315,8 +1684,7 @@ int hope_scenegen_generate_device(int device_id, int level, int bay_mode, int n,
     if (max_obstacles < SG_MAX_RINGS + 1) return fail(HOPE_EINVAL, "hope_scenegen_generate_device: max_obstacles < 18 (a generated lot holds up to 17 obstacles)");
     if (n == 0) return HOPE_OK;
     if (!start || !dest || !bbox || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_scenegen_generate_device: null output buffer");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(HOPE_ENODEV, "hope_scenegen_generate_device: hipSetDevice failed");
+    HOPE_ON_DEVICE_AS(device_id, HOPE_ENODEV, "hope_scenegen_generate_device: ");
     SgJob job{};
     for (int l = 0; l < 4; l++) job.off[l] = l > level ? n : 0;
     for (int l = 0; l < 3; l++) job.seed[l] = seed;
@@ -2334,8 +1702,7 @@ int hope_map_level_device(int device_id, int n, int max_obstacles, const double*
     if (max_obstacles <= 0 || max_obstacles > HOPE_MAX_OBSTACLES) return fail(HOPE_EINVAL, "hope_map_level_device: max_obstacles out of range (1 .. 255)");
     if (!level) return fail(HOPE_EINVAL, "hope_map_level_device: null level buffer");
     if (!start || !dest || !verts || !n_obst) return fail(HOPE_EINVAL, "hope_map_level_device: null input buffer");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(HOPE_ENODEV, "hope_map_level_device: hipSetDevice failed");
+    HOPE_ON_DEVICE_AS(device_id, HOPE_ENODEV, "hope_map_level_device: ");
     hipLaunchKernelGGL(k_map_level, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, n, max_obstacles, start, 3, dest, 3, verts, n_obst,
                        (const uint8_t*)nullptr, level, detail);
     HIPCHK(hipGetLastError());
@@ -2343,12 +1710,10 @@ int hope_map_level_device(int device_id, int n, int max_obstacles, const double*
 }
 
 int hope_env_map_level(hope_env_t* h, const uint8_t* active, uint8_t* level, int32_t* detail, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_map_level: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_map_level: not a live handle (destroyed?)");
+    HOPE_ENTER(h, "hope_env_map_level");
     if (!level) return fail(HOPE_EINVAL, "hope_env_map_level: null level buffer");
     if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_map_level: hope_env_set_scenes has not been called");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }   // ordered like every entry that reads the handle's state
     hipLaunchKernelGGL(k_map_level, dim3(h->n), dim3(WAVE), 0, (hipStream_t)stream, h->n, h->max_obst, (const double*)(h->scene_c + SC_START),
                        (int)SC_WORDS, (const double*)(h->scene_c + SC_DEST), (int)SC_WORDS, (const double*)h->verts, (const int32_t*)h->n_obst, active,
@@ -2358,7 +1723,8 @@ int hope_env_map_level(hope_env_t* h, const uint8_t* active, uint8_t* level, int
 }
 
 int hope_env_generate_pool(hope_env_t* h, int n_pool, const int32_t* n_per_level, uint64_t seed, int64_t first_index, int relaxed) {
-    if (!h || n_pool <= 0 || !n_per_level) return fail(HOPE_EINVAL, "hope_env_generate_pool: bad argument");
+    HOPE_ENTER_AS(h, "hope_env_generate_pool", "bad argument");
+    if (n_pool <= 0 || !n_per_level) return fail(HOPE_EINVAL, "hope_env_generate_pool: bad argument");
     {
         int64_t sum = 0;
         for (int l = 0; l < 3; l++) {
@@ -2369,8 +1735,7 @@ int hope_env_generate_pool(hope_env_t* h, int n_pool, const int32_t* n_per_level
     }
     if (h->max_obst < SG_MAX_RINGS + 1) return fail(HOPE_EINVAL, "hope_env_generate_pool: max_obstacles < 18 (a generated lot holds up to 17 obstacles)");
     if (h->pstage.staged) return fail(HOPE_ESTATE, "hope_env_generate_pool: a hope_env_pool_staging fill has not been committed (hope_env_commit_pool first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     int rc = pool_init_streams(h);
     if (rc != HOPE_OK) return rc;
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }     // (a relaxed swap still in flight: it comes first)
@@ -2462,16 +1827,16 @@ static int refresh_pool_lists_sync(hope_env_t* h) {
 
 int hope_env_set_dlp_cases(hope_env_t* h, int n_cases, const double* dest, const int32_t* cand_off, const double* cand,
                            const int32_t* case_set, int n_sets, const int32_t* set_off, const double* set_verts) {
+    HOPE_ENTER_AS(h, "hope_env_set_dlp_cases", "bad argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || n_cases < 0 || (n_cases > 0 && (!dest || !cand_off || !cand || !case_set || n_sets <= 0 || !set_off || !set_verts)))
+    if (n_cases < 0 || (n_cases > 0 && (!dest || !cand_off || !cand || !case_set || n_sets <= 0 || !set_off || !set_verts)))
         return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: bad argument");
     if (h->cur.on) return fail(HOPE_ESTATE, "hope_env_set_dlp_cases: the curriculum is on and its buckets are sized by the cases (hope_env_curriculum_disable first)");
     for (int c = 0; c < n_cases; c++) {
         if (cand_off[c + 1] <= cand_off[c]) return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: a case without start candidates");
         if (case_set[c] < 0 || case_set[c] >= n_sets) return fail(HOPE_EINVAL, "hope_env_set_dlp_cases: case_set out of range");
     }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     // a relaxed commit still pending takes over FIRST: its class lists were built with the old cases, and refresh_pool_lists_sync
     // below rebuilds the lists of the set that is active when it runs
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
@@ -2500,11 +1865,11 @@ int hope_env_set_dlp_cases(hope_env_t* h, int n_cases, const double* dest, const
 }
 
 int hope_env_set_draw_class(hope_env_t* h, const int32_t* scene_ids, int n, const uint8_t* cls) {
+    HOPE_ENTER_AS(h, "hope_env_set_draw_class", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || n < 0 || (n > 0 && (!scene_ids || !cls))) return fail(HOPE_EINVAL, "hope_env_set_draw_class: null argument");
+    if (n < 0 || (n > 0 && (!scene_ids || !cls))) return fail(HOPE_EINVAL, "hope_env_set_draw_class: null argument");
     if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_set_draw_class: hope_env_set_scenes has not been called");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     // the obstacle counts as they are NOW: device-side draws (HOPE_AUTO_REDRAW, hope_env_redraw) change them behind the host copy
     HIPCHK(hipMemcpy(h->n_obst_host.data(), h->n_obst, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2521,10 +1886,10 @@ int hope_env_set_draw_class(hope_env_t* h, const int32_t* scene_ids, int n, cons
 }
 
 int hope_env_pool_overflow(hope_env_t* h, int32_t* count) {
+    HOPE_ENTER_AS(h, "hope_env_pool_overflow", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !count) return fail(HOPE_EINVAL, "hope_env_pool_overflow: null argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (!count) return fail(HOPE_EINVAL, "hope_env_pool_overflow: null argument");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(count, h->pool_overflow, sizeof(int32_t), hipMemcpyDeviceToHost));
     return HOPE_OK;
@@ -2533,10 +1898,10 @@ int hope_env_pool_overflow(hope_env_t* h, int32_t* count) {
 // the maps the scenes hold NOW (after device-side draws they exist on the device only): host-synchronous
 int hope_env_download_scenes(hope_env_t* h, const int32_t* scene_ids, int n, double* start, double* dest, double* bbox, double* verts,
                              int32_t* n_obst) {
+    HOPE_ENTER_AS(h, "hope_env_download_scenes", "bad argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || n < 0 || (n > 0 && !scene_ids)) return fail(HOPE_EINVAL, "hope_env_download_scenes: bad argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (n < 0 || (n > 0 && !scene_ids)) return fail(HOPE_EINVAL, "hope_env_download_scenes: bad argument");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     const size_t tile = (size_t)h->max_obst * 8;
     std::vector<double> c(SC_WORDS);
@@ -2553,20 +1918,20 @@ int hope_env_download_scenes(hope_env_t* h, const int32_t* scene_ids, int n, dou
 }
 
 int hope_env_set_redraw_seed(hope_env_t* h, uint64_t seed) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_set_redraw_seed: null handle");
+    HOPE_ENTER(h, "hope_env_set_redraw_seed");
     h->redraw_seed = seed;
     return HOPE_OK;
 }
 
 int hope_env_redraw(hope_env_t* h, const uint8_t* mask, uint64_t seed, void* stream) {
-    if (h) { DeviceGuard g0(h->device); int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !mask) return fail(HOPE_EINVAL, "hope_env_redraw: null argument");
+    HOPE_ENTER_AS(h, "hope_env_redraw", "null argument");
+    { DeviceGuard g0(h->device); int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
+    if (!mask) return fail(HOPE_EINVAL, "hope_env_redraw: null argument");
     if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_redraw: hope_env_set_scenes has not been called");
     if (h->pool_n <= 0 && h->dlp.n_cases <= 0) return fail(HOPE_ESTATE, "hope_env_redraw: no scene pool (hope_env_set_pool / hope_env_set_dlp_cases)");
     int rc0 = check_pool_classes(h, "hope_env_redraw");
     if (rc0 != HOPE_OK) return rc0;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, false); if (rcp != HOPE_OK) return rcp; }
     if (h->pool_wait_pending) { HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_pool_ready, 0)); h->pool_wait_pending = false; }
     const int32_t* dl[2]; int dn[2];
@@ -2591,10 +1956,9 @@ int hope_env_redraw(hope_env_t* h, const uint8_t* mask, uint64_t seed, void* str
 // counter) and of the pool / case lists, so a map is restored by repeating its draw: the counters go back by one and k_redraw runs
 // for the scenes that held a drawn map.  Pose / t / accumulator are restored separately (hope_env_upload_state, afterwards).
 int hope_env_download_pool_state(hope_env_t* h, int32_t* pool_index, uint32_t* episode) {
+    HOPE_ENTER(h, "hope_env_download_pool_state");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_download_pool_state: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }     // the snapshot belongs to the pool the next step draws from
     HIPCHK(hipDeviceSynchronize());
     if (pool_index) HIPCHK(hipMemcpy(pool_index, h->cur_pool, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2604,8 +1968,9 @@ int hope_env_download_pool_state(hope_env_t* h, int32_t* pool_index, uint32_t* e
 
 int hope_env_restore_maps(hope_env_t* h, const uint8_t* drawn /* host [N]: the scene held a drawn map */, const uint32_t* episode, uint64_t seed,
                           uint64_t pool_generation) {
+    HOPE_ENTER_AS(h, "hope_env_restore_maps", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !drawn || !episode) return fail(HOPE_EINVAL, "hope_env_restore_maps: null argument");
+    if (!drawn || !episode) return fail(HOPE_EINVAL, "hope_env_restore_maps: null argument");
     { DeviceGuard guard0(h->device); int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }   // (compare generations after a pending swap)
     if (h->pool_n <= 0 && h->dlp.n_cases <= 0) return fail(HOPE_ESTATE, "hope_env_restore_maps: no scene pool");
     uint64_t gen_now = 0;
@@ -2614,8 +1979,7 @@ int hope_env_restore_maps(hope_env_t* h, const uint8_t* drawn /* host [N]: the s
         return fail(HOPE_ESTATE, "hope_env_restore_maps: the scene pool or the curriculum's draw lists have been replaced since the snapshot (pool generation " +
                                  std::to_string(gen_now) + " now, " + std::to_string(pool_generation) + " in the snapshot): repeating the draws "
                                  "would give other maps -- snapshot refreshed runs with hope_env_download_scenes / hope_env_set_scenes");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     std::vector<uint32_t> ep(episode, episode + h->n);
     for (int i = 0; i < h->n; i++) if (drawn[i]) { if (ep[i] == 0) return fail(HOPE_EINVAL, "hope_env_restore_maps: a drawn scene with episode counter 0"); ep[i] -= 1; }
@@ -2630,10 +1994,10 @@ int hope_env_restore_maps(hope_env_t* h, const uint8_t* drawn /* host [N]: the s
 }
 
 int hope_env_download_pool_index(hope_env_t* h, int32_t* out) {
+    HOPE_ENTER_AS(h, "hope_env_download_pool_index", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !out) return fail(HOPE_EINVAL, "hope_env_download_pool_index: null argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (!out) return fail(HOPE_EINVAL, "hope_env_download_pool_index: null argument");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, h->cur_pool, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return HOPE_OK;
@@ -2753,14 +2117,13 @@ static void cur_layout(hope_env::Curriculum& cu) {
 static size_t cur_mem_bytes(int nb) { return ((size_t)nb * 7 + 2 + 4) * 8; }
 
 int hope_env_curriculum_enable(hope_env_t* h, const hope_curriculum_params* params) {
+    HOPE_ENTER(h, "hope_env_curriculum_enable");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_enable: null handle");
     const hope_curriculum_params P = params ? *params : CW_DEFAULTS;
     if (!(P.type_window > 0.0) || !(P.case_window > 0.0) || !(P.type_fail_min > 0.0) || !(P.case_fail_min > 0.0) ||
         !(P.worst_share >= 0.0 && P.worst_share <= 1.0) || !(P.case_uniform >= 0.0 && P.case_uniform <= 1.0))
         return fail(HOPE_EINVAL, "hope_env_curriculum_enable: windows and failure floors must be positive, shares in [0, 1]");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
     if ((h->pool_n <= 0 && h->dlp.n_cases <= 0) || h->pactive < 0)
         return fail(HOPE_ESTATE, "hope_env_curriculum_enable: no scene pool and no Dragon-Lake cases (hope_env_set_pool / hope_env_generate_pool / hope_env_set_dlp_cases first)");
@@ -2796,20 +2159,19 @@ int hope_env_curriculum_enable(hope_env_t* h, const hope_curriculum_params* para
 }
 
 int hope_env_curriculum_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_curriculum_disable");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_disable: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());                         // steps in flight read the weighted lists
     cur_free(h);
     return HOPE_OK;
 }
 
 int hope_env_set_pool_buckets(hope_env_t* h, int n_pool, const uint8_t* bucket) {
+    HOPE_ENTER_AS(h, "hope_env_set_pool_buckets", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !bucket) return fail(HOPE_EINVAL, "hope_env_set_pool_buckets: null argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (!bucket) return fail(HOPE_EINVAL, "hope_env_set_pool_buckets: null argument");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
     if (h->pool_n <= 0 || h->pactive < 0) return fail(HOPE_ESTATE, "hope_env_set_pool_buckets: no scene pool");
     if (n_pool != h->pool_n)
@@ -2851,11 +2213,10 @@ int hope_env_set_pool_buckets(hope_env_t* h, int n_pool, const uint8_t* bucket) 
 }
 
 int hope_env_curriculum_tally(hope_env_t* h, const int32_t* status, const uint8_t* done, void* stream) {
-    if (!h || !status || !done) return fail(HOPE_EINVAL, "hope_env_curriculum_tally: null argument");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_curriculum_tally: not a live handle (destroyed?)");
+    HOPE_ENTER_AS(h, "hope_env_curriculum_tally", "null argument");
+    if (!status || !done) return fail(HOPE_EINVAL, "hope_env_curriculum_tally: null argument");
     if (!h->cur.on) return fail(HOPE_ESTATE, "hope_env_curriculum_tally: the curriculum is off (hope_env_curriculum_enable first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     // the labels of the set the step just drew from: a relaxed commit may have swapped sets at that step, never after it
     const int t = h->draw_set >= 0 ? h->draw_set : h->pactive;
     const hope_env::PoolSet& ps = h->pset[t];
@@ -2869,11 +2230,9 @@ int hope_env_curriculum_tally(hope_env_t* h, const int32_t* status, const uint8_
 }
 
 int hope_env_curriculum_update(hope_env_t* h, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_update: null handle");
-    if (!is_live(h)) return fail(HOPE_EINVAL, "hope_env_curriculum_update: not a live handle (destroyed?)");
+    HOPE_ENTER(h, "hope_env_curriculum_update");
     if (!h->cur.on) return fail(HOPE_ESTATE, "hope_env_curriculum_update: the curriculum is off (hope_env_curriculum_enable first)");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, false); if (rcp != HOPE_OK) return rcp; }   // (lists are built for the set the next step draws from)
     int rc = cur_build_lists(h, true, (hipStream_t)stream);
     if (rc == HOPE_OK) h->cur.updates++;
@@ -2882,8 +2241,8 @@ int hope_env_curriculum_update(hope_env_t* h, void* stream) {
 
 int hope_env_curriculum_state(hope_env_t* h, int32_t* n_buckets, uint64_t* episodes, uint64_t* successes, double* win_n, double* win_s,
                               double* prob, double* pw, uint64_t* misc) {
+    HOPE_ENTER(h, "hope_env_curriculum_state");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_state: null handle");
     const hope_env::Curriculum& cu = h->cur;
     if (n_buckets) *n_buckets = cu.on ? cu.nb : 4 + h->dlp.n_cases;
     if (!cu.on) {
@@ -2891,8 +2250,7 @@ int hope_env_curriculum_state(hope_env_t* h, int32_t* n_buckets, uint64_t* episo
         if (misc) misc[0] = misc[1] = misc[2] = misc[3] = 0;
         return HOPE_OK;
     }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     const size_t nb = (size_t)cu.nb;
     std::vector<uint64_t> e(nb + 1), s(nb + 1);
@@ -2910,16 +2268,16 @@ int hope_env_curriculum_state(hope_env_t* h, int32_t* n_buckets, uint64_t* episo
 
 int hope_env_curriculum_set_windows(hope_env_t* h, int n_buckets, const double* win_n, const double* win_s, const uint64_t* episodes,
                                     const uint64_t* successes) {
+    HOPE_ENTER_AS(h, "hope_env_curriculum_set_windows", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !win_n || !win_s || !episodes || !successes) return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: null argument");
+    if (!win_n || !win_s || !episodes || !successes) return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: null argument");
     hope_env::Curriculum& cu = h->cur;
     if (!cu.on) return fail(HOPE_ESTATE, "hope_env_curriculum_set_windows: the curriculum is off (hope_env_curriculum_enable first)");
     if (n_buckets != cu.nb) return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: " + std::to_string(n_buckets) + " buckets given, the handle has " + std::to_string(cu.nb));
     for (int b = 0; b < n_buckets; b++)
         if (!(win_n[b] >= 0.0) || !(win_s[b] >= 0.0) || win_s[b] > win_n[b] || successes[b] > episodes[b])
             return fail(HOPE_EINVAL, "hope_env_curriculum_set_windows: bucket " + std::to_string(b) + " needs 0 <= s <= n");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
     HIPCHK(hipDeviceSynchronize());
     const size_t nb = (size_t)cu.nb;
@@ -2936,12 +2294,11 @@ int hope_env_curriculum_set_windows(hope_env_t* h, int n_buckets, const double* 
 }
 
 int hope_env_curriculum_download_lists(hope_env_t* h, int32_t* list0, int32_t* list1, int32_t* positions) {
+    HOPE_ENTER(h, "hope_env_curriculum_download_lists");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_curriculum_download_lists: null handle");
     const hope_env::Curriculum& cu = h->cur;
     if (!cu.on || cu.wactive < 0) return fail(HOPE_ESTATE, "hope_env_curriculum_download_lists: the curriculum is off");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     { int rcp = apply_pending_pool(h, true); if (rcp != HOPE_OK) return rcp; }
     HIPCHK(hipDeviceSynchronize());
     int32_t* out[2] = {list0, list1};
@@ -2962,8 +2319,7 @@ static int effective_generation(hope_env_t* h, uint64_t* generation) {
     *generation = h->pool_generation;
     const hope_env::Curriculum& cu = h->cur;
     if (!cu.on || cu.wactive < 0 || h->pactive < 0) return HOPE_OK;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipStreamSynchronize(h->pool_stream));
     std::vector<int32_t> pf(2 * (CW_MAX_GROUPS + 1));
     HIPCHK(hipMemcpy(pf.data(), cu.prefix[cu.wactive], pf.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -3028,49 +2384,44 @@ int hope_curriculum_lists_host(const hope_curriculum_params* params, int n_pool,
 }
 
 int hope_env_restart(hope_env_t* h, const uint8_t* mask, void* stream) {
-    if (h) { DeviceGuard g0(h->device); int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !mask) return fail(HOPE_EINVAL, "hope_env_restart: null argument");
+    HOPE_ENTER_AS(h, "hope_env_restart", "null argument");
+    { DeviceGuard g0(h->device); int rcs = join_rs(h, (hipStream_t)stream); if (rcs != HOPE_OK) return rcs; }
+    if (!mask) return fail(HOPE_EINVAL, "hope_env_restart: null argument");
     if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_restart: hope_env_set_scenes has not been called");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     hipLaunchKernelGGL(k_restart, dim3((h->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->n, mask, h->scene_c,
                        h->state, h->tstep, h->traj, h->traj_len, h->traj_valid);
     HIPCHK(hipGetLastError());
     return HOPE_OK;
 }
 
-int hope_env_kernel_ms(hope_env_t* h, double* ms, int64_t* launches, int reset) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_kernel_ms: null handle");
-    if (!(h->flags & HOPE_F_PROFILE)) return fail(HOPE_ESTATE, "hope_env_kernel_ms: handle was not created with HOPE_F_PROFILE");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+// HOPE_F_PROFILE: drains the recorded event pairs, then copies (and clears) one pair of per-kernel accumulators
+static int profile_read(hope_env_t* h, double* acc_ms, int64_t* acc_n, double* ms, int64_t* counts, int reset) {
+    HOPE_ON_DEVICE(h);
     int rc = drain_events(h);
     if (rc) return rc;
     for (int k = 0; k < HOPE_N_KERNELS; k++) {
-        if (ms) ms[k] = h->ms[k];
-        if (launches) launches[k] = h->launches[k];
-        if (reset) { h->ms[k] = 0; h->launches[k] = 0; }
+        if (ms) ms[k] = acc_ms[k];
+        if (counts) counts[k] = acc_n[k];
+        if (reset) { acc_ms[k] = 0; acc_n[k] = 0; }
     }
     return HOPE_OK;
+}
+
+int hope_env_kernel_ms(hope_env_t* h, double* ms, int64_t* launches, int reset) {
+    HOPE_ENTER(h, "hope_env_kernel_ms");
+    if (!(h->flags & HOPE_F_PROFILE)) return fail(HOPE_ESTATE, "hope_env_kernel_ms: handle was not created with HOPE_F_PROFILE");
+    return profile_read(h, h->ms, h->launches, ms, launches, reset);
 }
 
 int hope_env_kernel_union_ms(hope_env_t* h, double* ms, int64_t* calls, int reset) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_kernel_union_ms: null handle");
+    HOPE_ENTER(h, "hope_env_kernel_union_ms");
     if (!(h->flags & HOPE_F_PROFILE)) return fail(HOPE_ESTATE, "hope_env_kernel_union_ms: handle was not created with HOPE_F_PROFILE");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
-    int rc = drain_events(h);
-    if (rc) return rc;
-    for (int k = 0; k < HOPE_N_KERNELS; k++) {
-        if (ms) ms[k] = h->union_ms[k];
-        if (calls) calls[k] = h->union_calls[k];
-        if (reset) { h->union_ms[k] = 0; h->union_calls[k] = 0; }
-    }
-    return HOPE_OK;
+    return profile_read(h, h->union_ms, h->union_calls, ms, calls, reset);
 }
 
 int hope_env_profile_kernels(hope_env_t* h, uint32_t kernel_mask) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_profile_kernels: null handle");
+    HOPE_ENTER(h, "hope_env_profile_kernels");
     if (!(h->flags & HOPE_F_PROFILE)) return fail(HOPE_ESTATE, "hope_env_profile_kernels: handle was not created with HOPE_F_PROFILE");
     h->profile_mask = kernel_mask;
     return HOPE_OK;
@@ -3078,44 +2429,45 @@ int hope_env_profile_kernels(hope_env_t* h, uint32_t kernel_mask) {
 
 int hope_env_step(hope_env_t* h, const void* actions, const uint8_t* active, uint32_t stages,
                   const hope_step_out* out, void* stream) {
+    HOPE_ENTER_AS(h, "hope_env_step", "null argument");
     return launch_step(h, actions, active, stages, out, stream, 1);
 }
 
 int hope_env_wait_rs(hope_env_t* h, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_wait_rs: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ENTER(h, "hope_env_wait_rs");
+    HOPE_ON_DEVICE(h);
     return join_rs(h, (hipStream_t)stream);
 }
 
 int hope_env_last_step(hope_env_t* h, uint64_t* step) {
-    if (!h || !step) return fail(HOPE_EINVAL, "hope_env_last_step: null argument");
+    HOPE_ENTER_AS(h, "hope_env_last_step", "null argument");
+    if (!step) return fail(HOPE_EINVAL, "hope_env_last_step: null argument");
     *step = h->step_seq;
     return HOPE_OK;
 }
 
 int hope_env_wait_rs_step(hope_env_t* h, uint64_t step, void* stream) {
-    if (!h) return fail(HOPE_EINVAL, "hope_env_wait_rs_step: null handle");
+    HOPE_ENTER(h, "hope_env_wait_rs_step");
     if (step == 0 || step > h->step_seq) return fail(HOPE_EINVAL, "hope_env_wait_rs_step: no such step (hope_env_last_step)");
     if (step != h->step_seq)
         return fail(HOPE_ESTATE, "hope_env_wait_rs_step: step " + std::to_string(step) + " is not the last one (" + std::to_string(h->step_seq) +
                                  "): a later hope_env_step / hope_env_reset_obs has replaced its Reeds-Shepp outputs -- wait before enqueuing the next step");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     return join_rs(h, (hipStream_t)stream);
 }
 
 int hope_env_download_n_obst(hope_env_t* h, int32_t* n_obst) {
+    HOPE_ENTER_AS(h, "hope_env_download_n_obst", "null argument");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h || !n_obst) return fail(HOPE_EINVAL, "hope_env_download_n_obst: null argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    if (!n_obst) return fail(HOPE_EINVAL, "hope_env_download_n_obst: null argument");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(n_obst, h->n_obst, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return HOPE_OK;
 }
 
 int hope_env_reset_obs(hope_env_t* h, const uint8_t* active, uint32_t stages, const hope_step_out* out, void* stream) {
+    HOPE_ENTER_AS(h, "hope_env_reset_obs", "null argument");
     return launch_step(h, nullptr, active, stages & ~HOPE_STAGE_MOTION, out, stream, 0);
 }
 
@@ -3172,10 +2524,9 @@ int hope_debug_traffic(int mode, size_t bytes, void* buf, void* stream) {
 }
 
 int hope_env_download_state(hope_env_t* h, double* pose, int32_t* t, double* accum) {
+    HOPE_ENTER(h, "hope_env_download_state");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_download_state: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     std::vector<double> st((size_t)h->n * ST_WORDS);
     HIPCHK(hipMemcpy(st.data(), h->state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -3188,10 +2539,9 @@ int hope_env_download_state(hope_env_t* h, double* pose, int32_t* t, double* acc
 }
 
 int hope_env_upload_state(hope_env_t* h, const double* pose, const int32_t* t, const double* accum) {
+    HOPE_ENTER(h, "hope_env_upload_state");
     { int rcs = settle_rs(h); if (rcs != HOPE_OK) return rcs; }
-    if (!h) return fail(HOPE_EINVAL, "hope_env_upload_state: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(HOPE_EHIP, "hipSetDevice failed");
+    HOPE_ON_DEVICE(h);
     HIPCHK(hipDeviceSynchronize());
     std::vector<double> st((size_t)h->n * ST_WORDS);
     HIPCHK(hipMemcpy(st.data(), h->state, st.size() * sizeof(double), hipMemcpyDeviceToHost));

@@ -85,6 +85,57 @@ struct RsParams {
     int2* surv_list;          // [max_queue]
 };
 
+// ---- plain records that a kernel header passes to its kernels AND the handle (hope_handle.h) holds by value ----
+// Dragon-Lake-Parking cases resident on the device (hope_env_set_dlp_cases): what ParkingMapDLP.reset draws from
+// (src/env/parking_map_dlp.py:38-86).  A pool list entry j <= -2 names case -2 - j.
+struct DlpCases {
+    int n_cases;
+    const double* dest;       // [n_cases][3]
+    const int32_t* cand_off;  // [n_cases + 1] start candidates of case c: cand[cand_off[c] .. cand_off[c + 1])
+    const double* cand;       // [][3]
+    const int32_t* case_set;  // [n_cases] obstacle set of the case
+    const int32_t* set_off;   // [n_sets + 1]
+    const double* set_verts;  // [][4][2] obstacle rings of all sets (a triangle repeats its last vertex)
+};
+
+// What the step kernel touches rarely (episode turnover, image bookkeeping): read through ONE pointer at the point of use.
+// As by-value kernel arguments these ~25 pointers were all loaded at kernel entry and stayed live in SGPRs to their (rare) use:
+// 106 SGPRs, 68 of them spilled to VGPR lanes, in a kernel that sits on the 128-VGPR occupancy step.  The record lives in
+// device memory (a small ring in the handle, re-uploaded stream-ordered when its content changes: a pool commit, a new seed).
+struct StepCold {
+    double* traj;             // HOPE_F_IMAGE: [n][20][3] ring of vehicle.trajectory (entry e in slot e % 20), else null
+    int32_t* traj_len;        // HOPE_F_IMAGE: [n] len(vehicle.trajectory)
+    int32_t* traj_valid;      // HOPE_F_IMAGE: [n] span-table watermark of the image kernels (0 after a reset)
+    int32_t* layer_valid;     // HOPE_F_IMAGE: [n] the static image layer matches the scene's map (0 after a new map)
+    // HOPE_AUTO_REDRAW: the device-resident scene pool (hope_env_set_pool), or null pointers
+    const double* pool_verts; // [pool_n][max_obst][8]
+    const double* pool_c;     // [pool_n][SC_WORDS]
+    const int32_t* pool_nobst;
+    const int32_t* pool_cls[2];
+    int pool_cls_n[2];
+    int32_t* cur_pool;        // [n]
+    uint32_t* episode;        // [n]
+    unsigned long long redraw_seed;
+    DlpCases dlp;             // HOPE_AUTO_REDRAW: Dragon-Lake-Parking cases drawn on the device (hope_env_set_dlp_cases), or n_cases = 0
+    int32_t* pool_overflow;   // [1] draws whose culled obstacle set exceeded max_obst (truncated): must stay 0
+    const uint8_t* slot_cls;  // [n] draw class of every scene slot (0: lots of <= 32 obstacles, 1: larger)
+    float4* fverts;           // [n][max_obst][2] float32 view of the obstacles (obstacle_f32), rewritten with every new map
+    float4* fbox;             // [n][max_obst]
+    uint8_t* eflag;           // [n][eflag_stride(max_obst)]
+};
+
+// device state of the curriculum (one allocation, laid out by cur_layout, hope_env.hip)
+struct CwDev {
+    unsigned long long* episodes;    // [nb + 1] cumulative; [nb]: unlabelled maps
+    unsigned long long* successes;   // [nb + 1]
+    unsigned long long* folded_e;    // [nb] value of episodes at the last update
+    unsigned long long* folded_s;    // [nb]
+    double* win_n;                   // [nb]
+    double* win_s;                   // [nb]
+    double* prob;                    // [nb] q_0 .. q_3, p_c
+    double* pw;                      // [4]
+};
+
 // bird's-eye image observation (hope_bev.hip)
 constexpr int BEV_IMG = HOPE_IMG_SIZE;
 constexpr int BEV_TRAJ_LEN = HOPE_TRAJ_RENDER_LEN;

@@ -62,17 +62,7 @@ __device__ __forceinline__ double mask_fraction(int k) {
     return fma(r, R, q0);
 }
 
-// Dragon-Lake-Parking cases resident on the device (hope_env_set_dlp_cases): what ParkingMapDLP.reset draws from
-// (src/env/parking_map_dlp.py:38-86).  A pool list entry j <= -2 names case -2 - j.
-struct DlpCases {
-    int n_cases;
-    const double* dest;       // [n_cases][3]
-    const int32_t* cand_off;  // [n_cases + 1] start candidates of case c: cand[cand_off[c] .. cand_off[c + 1])
-    const double* cand;       // [][3]
-    const int32_t* case_set;  // [n_cases] obstacle set of the case
-    const int32_t* set_off;   // [n_sets + 1]
-    const double* set_verts;  // [][4][2] obstacle rings of all sets (a triangle repeats its last vertex)
-};
+// (DlpCases, the Dragon-Lake-Parking cases resident on the device, and StepCold, what the step kernel touches rarely: hope_internal.h)
 
 // the per-scene constant record from (start, dest, map box): what hope_env_set_scenes computes per scene
 __device__ __forceinline__ void fill_scene_consts(double* c, const double* start, const double* dest, const double* bbox) {
@@ -164,32 +154,6 @@ __device__ __forceinline__ int draw_dlp_case(const DlpCases& D, int cs, uint64_t
     }
     return cnt;
 }
-
-// What the step kernel touches rarely (episode turnover, image bookkeeping): read through ONE pointer at the point of use.
-// As by-value kernel arguments these ~25 pointers were all loaded at kernel entry and stayed live in SGPRs to their (rare) use:
-// 106 SGPRs, 68 of them spilled to VGPR lanes, in a kernel that sits on the 128-VGPR occupancy step.  The record lives in
-// device memory (a small ring in the handle, re-uploaded stream-ordered when its content changes: a pool commit, a new seed).
-struct StepCold {
-    double* traj;             // HOPE_F_IMAGE: [n][20][3] ring of vehicle.trajectory (entry e in slot e % 20), else null
-    int32_t* traj_len;        // HOPE_F_IMAGE: [n] len(vehicle.trajectory)
-    int32_t* traj_valid;      // HOPE_F_IMAGE: [n] span-table watermark of the image kernels (0 after a reset)
-    int32_t* layer_valid;     // HOPE_F_IMAGE: [n] the static image layer matches the scene's map (0 after a new map)
-    // HOPE_AUTO_REDRAW: the device-resident scene pool (hope_env_set_pool), or null pointers
-    const double* pool_verts; // [pool_n][max_obst][8]
-    const double* pool_c;     // [pool_n][SC_WORDS]
-    const int32_t* pool_nobst;
-    const int32_t* pool_cls[2];
-    int pool_cls_n[2];
-    int32_t* cur_pool;        // [n]
-    uint32_t* episode;        // [n]
-    unsigned long long redraw_seed;
-    DlpCases dlp;             // HOPE_AUTO_REDRAW: Dragon-Lake-Parking cases drawn on the device (hope_env_set_dlp_cases), or n_cases = 0
-    int32_t* pool_overflow;   // [1] draws whose culled obstacle set exceeded max_obst (truncated): must stay 0
-    const uint8_t* slot_cls;  // [n] draw class of every scene slot (0: lots of <= 32 obstacles, 1: larger)
-    float4* fverts;           // [n][max_obst][2] float32 view of the obstacles (obstacle_f32), rewritten with every new map
-    float4* fbox;             // [n][max_obst]
-    uint8_t* eflag;           // [n][eflag_stride(max_obst)]
-};
 
 constexpr uint32_t STEP_HF_TRAJ = 1;   // StepParams::hflags: the handle keeps vehicle.trajectory (HOPE_F_IMAGE)
 

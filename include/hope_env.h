@@ -168,6 +168,8 @@ typedef struct hope_step_out {
 #define HOPE_MAX_OBSTACLES 255
 int hope_env_create(hope_env_t **out, int n_scenes, int max_obstacles, int device_id, uint32_t flags);
 int hope_env_destroy(hope_env_t *h);                       /* CarParking.close (:536) */
+/* Every entry point that takes a handle fails with HOPE_EINVAL and "<name>: not a live handle (destroyed?)" when given a pointer
+ * that hope_env_create did not return or that hope_env_destroy has released, before it reads anything through the pointer. */
 const char *hope_last_error(void);
 int hope_abi_version(void);
 

@@ -259,3 +259,93 @@ def test_n_obst_download_matches_the_per_scene_download():
     assert lib.hope_env_download_n_obst(h, out.ctypes.data) == OK
     assert np.array_equal(out, arrays[4])
     assert lib.hope_env_destroy(h) == OK
+
+
+@pytest.mark.parametrize('feature', ['planner', 'chooser', 'obsnorm', 'eval'])
+def test_enable_disable_enable_starts_from_the_initial_state(feature):
+    """the four policy-side features share one "allocate if absent, initialise, free on failure" path: enable, disable, enable again
+    -- each round starts from the freshly initialised state whatever the last round left in the memory, and between the rounds the
+    feature is off (HOPE_ESTATE, its text)"""
+    from hope_amd import tables as T
+    lib = _lib()
+    n, dev = 64, 'cuda:0'
+    h = _create(n=n, mo=16)
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    g = torch.Generator(device=dev).manual_seed(11)
+    if feature == 'planner':
+        state = np.zeros((L.PLAN_STATE_WORDS, n), np.uint64)
+        word = torch.tensor([[1, 0, 2, 0, 0, 3, 1, 0]] * n, dtype=torch.int8, device=dev)       # L S R, three segments, found
+        lengths = torch.full((n, 5), 10.0, device=dev)
+        enable = lambda r: lib.hope_env_planner_enable(h, 0.0)  # noqa: E731
+        disable = lambda: lib.hope_env_planner_disable(h)  # noqa: E731
+        probe = lambda: lib.hope_env_planner_download_state(h, state.ctypes.data)  # noqa: E731
+        off = 'hope_env_planner_download_state: the planner is off (hope_env_planner_enable first)'
+
+        def fresh(r):
+            assert probe() == OK and not state.any()
+
+        def dirty():
+            assert lib.hope_env_planner_step(h, P(word), P(lengths), None, L.PLAN_NO_POP, 0, None, None, None, 0, None) == OK, _err()
+            assert probe() == OK and state[5].all()                  # every scene replays a path
+    elif feature == 'chooser':
+        tabs = [np.ascontiguousarray(T.discrete_actions() / [T.VALID_STEER[1], 1.0] * [1.0, sc], dtype=np.float64) for sc in (1.0, 0.5)]
+        mean, log_std = torch.zeros((n, 2), device=dev), torch.zeros((1, 2), device=dev)
+        mask, action, idx = torch.ones((n, 42), device=dev), torch.zeros((n, 2), device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        enable = lambda r: lib.hope_env_chooser_enable(h, tabs[r % 2].ctypes.data)  # noqa: E731
+        disable = lambda: lib.hope_env_chooser_disable(h)  # noqa: E731
+        probe = lambda: lib.hope_env_choose(h, P(mean), P(log_std), 0, 0, P(mask), None, None, None, 7, 1, P(action), None, P(idx), None, None, None)  # noqa: E731
+        off = 'hope_env_choose: the chooser is off (hope_env_chooser_enable first)'
+
+        def fresh(r):                                                # the table on the device is this round's: the host twin's choice
+            z, o = np.zeros((n, 2), np.float32), np.ones((n, 42), np.float32)
+            a, i = np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
+            assert lib.hope_chooser_host(n, tabs[r % 2].ctypes.data, z.ctypes.data, z.ctypes.data, 0, 0, o.ctypes.data, 0, None, None, None, 7, 1, 0,
+                                         a.ctypes.data, 0, None, i.ctypes.data, None, None) == OK, _err()
+            assert probe() == OK, _err()
+            torch.cuda.synchronize()
+            assert np.array_equal(action.cpu().numpy().view(np.uint32), a.view(np.uint32)) and np.array_equal(idx.cpu().numpy(), i)
+
+        def dirty():
+            pass                                                     # (the other round's table is what the memory holds)
+    elif feature == 'obsnorm':
+        nst = C.c_int64(-1)
+        got = [np.full(L.OBSNORM_COLS, np.nan) for _ in range(3)]
+        enable = lambda r: lib.hope_env_obsnorm_enable(h)  # noqa: E731
+        disable = lambda: lib.hope_env_obsnorm_disable(h)  # noqa: E731
+        probe = lambda: lib.hope_env_obsnorm_get(h, C.byref(nst), *[a.ctypes.data for a in got])  # noqa: E731
+        off = 'hope_env_obsnorm_get: the normalisation is off (hope_env_obsnorm_enable first)'
+
+        def fresh(r):
+            assert probe() == OK and nst.value == 0 and not any(a.any() for a in got)
+
+        def dirty():
+            v = np.arange(1.0, 1.0 + L.OBSNORM_COLS)
+            assert lib.hope_env_obsnorm_set(h, 5, v.ctypes.data, (2 * v).ctypes.data, (3 * v).ctypes.data) == OK, _err()
+            assert probe() == OK and nst.value == 5 and np.array_equal(got[2], 3 * v)
+    else:
+        state = np.zeros((L.EVAL_STATE_WORDS, n), np.uint64)
+        box = np.array([T.VALID_STEER[0], T.VALID_STEER[1], T.VALID_SPEED[0], T.VALID_SPEED[1]], dtype=np.float64)
+        target = torch.rand((n, 5), device=dev, generator=g) + 1.0
+        pose = torch.rand((n, 3), dtype=torch.float64, device=dev, generator=g) + 1.0
+        enable = lambda r: lib.hope_env_eval_enable(h, box.ctypes.data)  # noqa: E731
+        disable = lambda: lib.hope_env_eval_disable(h)  # noqa: E731
+        probe = lambda: lib.hope_env_eval_download_state(h, state.ctypes.data)  # noqa: E731
+        off = 'hope_env_eval_download_state: the evaluation tracker is off (hope_env_eval_enable first)'
+
+        def fresh(r):
+            assert probe() == OK and not state.any()
+
+        def dirty():
+            assert lib.hope_env_eval_begin(h, P(target), P(pose), None) == OK, _err()
+            assert probe() == OK and state[:7].all()                 # previous target and position of every scene
+    assert probe() == ESTATE and _err() == off                       # off by default
+    for r in range(2):
+        assert enable(r) == OK, _err()
+        fresh(r)
+        dirty()
+        assert disable() == OK, _err()
+        assert probe() == ESTATE and _err() == off
+    assert enable(2) == OK, _err()
+    fresh(2)
+    assert disable() == OK and disable() == OK                       # (idempotent)
+    assert lib.hope_env_destroy(h) == OK

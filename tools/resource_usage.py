@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from hope_amd.build import FLAGS  # noqa: E402
+from hope_amd.build import FLAGS, SOURCES  # noqa: E402
 
 CS = os.path.join(ROOT, 'hope_amd', 'csrc')
 KEYS = ['VGPRs', 'AGPRs', 'ScratchSize [bytes/lane]', 'SGPRs', 'VGPRs Spill', 'SGPRs Spill', 'Occupancy [waves/SIMD]', 'LDS Size [bytes/block]']
@@ -23,7 +23,7 @@ def demangle(names):
 def main():
     show_all = '--all' in sys.argv
     rows = []
-    for src in ('hope_env.hip', 'hope_rs.hip', 'hope_bev.hip'):
+    for src in (s for s in SOURCES if s.endswith('.hip')):
         flags = [f for f in FLAGS if f not in ('-shared', '-pthread')] + os.environ.get('HOPE_BUILD_DEFS', '').split()
         cmd = ['/opt/rocm/bin/hipcc'] + flags + ['-I' + os.path.join(ROOT, 'include'), '-I' + CS, '--cuda-device-only',
                '-Rpass-analysis=kernel-resource-usage', '-c', os.path.join(CS, src), '-o', '/dev/null']
