@@ -37,6 +37,9 @@ def main():
     ap.add_argument('--device-norm', action='store_true',
                     help='also run a short PPO loop and the evaluation with the observation normalisation on the device '
                          "(obs_norm='device': k_obsnorm_partial / _merge / _apply per step instead of BatchedStateNorm's torch code)")
+    ap.add_argument('--device-gae', action='store_true',
+                    help="also run a short PPO loop with the advantage block on the device (gae='device': k_gae_scan / k_gae_merge / "
+                         "k_adv_apply per update instead of batched_gae's Python loop along the horizon and _global_mean_std)")
     ap.add_argument('--device-eval', action='store_true',
                     help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
                          'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
@@ -105,6 +108,21 @@ def main():
             sn = tr.obs_norm
             print(f'  device norm: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f"{sn.n_state} observations folded in, mean lidar std {float(sn.std['lidar'].mean()):.3f} m")
+    if args.device_gae:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
+                        seed=rank, use_planner='device' if args.device_planner else True,
+                        chooser='device' if args.device_chooser else None, obs_norm='device' if args.device_norm else None, gae='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(16):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            m, s = tr.gae.mean_std()
+            print(f'  device gae: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f'advantages of the last update: mean {m:.4f}, std {s:.4f} over {int(tr.gae.sums[2])} transitions')
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

@@ -21,13 +21,14 @@ ABI_VERSION = 8
 
 EXPORTS = ['hope_env_create', 'hope_env_destroy', 'hope_last_error', 'hope_abi_version', 'hope_env_upload_tables',
            'hope_env_set_scenes', 'hope_env_step', 'hope_env_wait_rs', 'hope_env_last_step', 'hope_env_wait_rs_step', 'hope_env_download_n_obst', 'hope_env_queue_check', 'hope_env_reset_obs', 'hope_env_download_state',
-           'hope_env_upload_state', 'hope_env_restart', 'hope_env_set_pool', 'hope_env_pool_staging', 'hope_env_commit_pool', 'hope_env_commit_pool_relaxed', 'hope_env_pool_staging_ready', 'hope_env_pool_generation', 'hope_env_redraw', 'hope_env_set_redraw_seed', 'hope_env_download_pool_index', 'hope_env_set_dlp_cases', 'hope_env_pool_overflow', 'hope_env_set_draw_class', 'hope_env_download_scenes', 'hope_env_download_pool_state', 'hope_env_restore_maps', 'hope_env_kernel_ms', 'hope_env_kernel_union_ms', 'hope_env_profile_kernels', 'hope_debug_math', 'hope_debug_geom', 'hope_debug_traffic', 'hope_debug_mask_lut', 'hope_debug_rs_prof', 'hope_debug_rs_log', 'hope_debug_rs_filter_stats', 'hope_debug_rs_filter_dump', 'hope_debug_step_prof', 'hope_debug_census', 'hope_scenegen_generate', 'hope_scenegen_default_threads', 'hope_scenegen_generate_det', 'hope_scenegen_generate_device', 'hope_scenegen_log_det', 'hope_env_generate_pool', 'hope_env_curriculum_enable', 'hope_env_curriculum_disable', 'hope_env_set_pool_buckets', 'hope_env_curriculum_tally', 'hope_env_curriculum_update', 'hope_env_curriculum_state', 'hope_env_curriculum_set_windows', 'hope_env_curriculum_download_lists', 'hope_curriculum_lists_host', 'hope_curriculum_fold_host', 'hope_map_level_host', 'hope_map_level_device', 'hope_env_map_level', 'hope_env_planner_enable', 'hope_env_planner_disable', 'hope_env_planner_reset', 'hope_env_planner_step', 'hope_planner_step_host', 'hope_env_planner_download_state', 'hope_env_chooser_enable', 'hope_env_chooser_disable', 'hope_env_choose', 'hope_chooser_host', 'hope_env_obsnorm_enable', 'hope_env_obsnorm_disable', 'hope_env_obsnorm_set', 'hope_env_obsnorm_get', 'hope_env_obsnorm', 'hope_obsnorm_host', 'hope_env_eval_enable', 'hope_env_eval_disable', 'hope_env_eval_begin', 'hope_env_eval_override', 'hope_env_eval_track', 'hope_env_eval_records', 'hope_env_eval_download_state', 'hope_eval_begin_host', 'hope_eval_override_host', 'hope_eval_track_host', 'hope_env_num_scenes', 'hope_env_max_obstacles', 'hope_env_device_arch']
+           'hope_env_upload_state', 'hope_env_restart', 'hope_env_set_pool', 'hope_env_pool_staging', 'hope_env_commit_pool', 'hope_env_commit_pool_relaxed', 'hope_env_pool_staging_ready', 'hope_env_pool_generation', 'hope_env_redraw', 'hope_env_set_redraw_seed', 'hope_env_download_pool_index', 'hope_env_set_dlp_cases', 'hope_env_pool_overflow', 'hope_env_set_draw_class', 'hope_env_download_scenes', 'hope_env_download_pool_state', 'hope_env_restore_maps', 'hope_env_kernel_ms', 'hope_env_kernel_union_ms', 'hope_env_profile_kernels', 'hope_debug_math', 'hope_debug_geom', 'hope_debug_traffic', 'hope_debug_mask_lut', 'hope_debug_rs_prof', 'hope_debug_rs_log', 'hope_debug_rs_filter_stats', 'hope_debug_rs_filter_dump', 'hope_debug_step_prof', 'hope_debug_census', 'hope_scenegen_generate', 'hope_scenegen_default_threads', 'hope_scenegen_generate_det', 'hope_scenegen_generate_device', 'hope_scenegen_log_det', 'hope_env_generate_pool', 'hope_env_curriculum_enable', 'hope_env_curriculum_disable', 'hope_env_set_pool_buckets', 'hope_env_curriculum_tally', 'hope_env_curriculum_update', 'hope_env_curriculum_state', 'hope_env_curriculum_set_windows', 'hope_env_curriculum_download_lists', 'hope_curriculum_lists_host', 'hope_curriculum_fold_host', 'hope_map_level_host', 'hope_map_level_device', 'hope_env_map_level', 'hope_env_planner_enable', 'hope_env_planner_disable', 'hope_env_planner_reset', 'hope_env_planner_step', 'hope_planner_step_host', 'hope_env_planner_download_state', 'hope_env_chooser_enable', 'hope_env_chooser_disable', 'hope_env_choose', 'hope_chooser_host', 'hope_env_obsnorm_enable', 'hope_env_obsnorm_disable', 'hope_env_obsnorm_set', 'hope_env_obsnorm_get', 'hope_env_obsnorm', 'hope_obsnorm_host', 'hope_env_eval_enable', 'hope_env_eval_disable', 'hope_env_eval_begin', 'hope_env_eval_override', 'hope_env_eval_track', 'hope_env_eval_records', 'hope_env_eval_download_state', 'hope_eval_begin_host', 'hope_eval_override_host', 'hope_eval_track_host', 'hope_env_gae_enable', 'hope_env_gae_disable', 'hope_env_gae', 'hope_env_adv_normalize', 'hope_gae_host', 'hope_adv_normalize_host', 'hope_env_num_scenes', 'hope_env_max_obstacles', 'hope_env_device_arch']
 
 
 CURRICULUM_LIST_LEN = 1 << 20
 PLAN_STATE_WORDS, PLAN_STEP_RATIO, PLAN_FORCED, PLAN_NO_POP = 6, 1.25, 0x1, 0x2
 CHOOSE_NOMASK, CHOOSE_FIXED, CHOOSE_FALLBACK = 64, 128, 10     # flag bits of the chooser's index output; the fixed index
 OBSNORM_LIDAR, OBSNORM_TARGET, OBSNORM_COLS, OBSNORM_UPDATE, OBSNORM_NORMALIZE = 120, 5, 125, 0x1, 0x2
+GAE_SUMS, GAE_NORMALIZE, GAE_MAX_T = 0x1, 0x2, 4096
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
 
@@ -171,6 +172,12 @@ def load_library():
     L.hope_eval_begin_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hope_eval_override_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_uint64] * 3 + [C.c_void_p]
     L.hope_eval_track_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.hope_env_gae_enable.argtypes = [C.c_void_p]
+    L.hope_env_gae_disable.argtypes = [C.c_void_p]
+    L.hope_env_gae.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 4
+    L.hope_env_adv_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hope_gae_host.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 4
+    L.hope_adv_normalize_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hope_env_num_scenes.argtypes = [C.c_void_p]
     L.hope_env_max_obstacles.argtypes = [C.c_void_p]
     if L.hope_abi_version() != ABI_VERSION:

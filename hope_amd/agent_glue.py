@@ -631,6 +631,91 @@ def batched_gae(reward, value, next_value, done, gamma=0.98, lam=0.95, use_gae=T
     return adv.to(value.dtype), delta.to(value.dtype)
 
 
+class DeviceGae:
+    """What BatchedPPO.advantages does after the critic forwards -- batched_gae, the critic's target, agents._global_mean_std and the
+    normalisation -- over the library's advantage block (include/hope_env.h "PPO's advantage block"; rule: csrc/hope_gae_core.h), so
+    that it can stand in as `agent.gae`: one fused call of three launches (k_gae_scan, k_gae_merge, k_adv_apply) instead of a Python
+    loop along T.  With torch.distributed and more than one rank the call is split: scan and sums, an all-reduce of the three
+    doubles {sum adv, sum adv^2, count}, then the normalisation -- what _global_mean_std does.  The sums' arithmetic order is fixed,
+    so mean and std do not depend on the launch geometry; they differ from the torch path's in the last bits only, adv before the
+    normalisation and v_target not at all.  On the device adv and v_target are (views of) persistent tensors of the env that the next
+    call overwrites.  On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same runs on the host through
+    hope_gae_host / hope_adv_normalize_host: the rule is one source for both.
+    `sums`: the float64 [3] tensor of the last call that reduced them (after the all-reduce, if there was one)."""
+
+    def __init__(self, env):
+        from . import _lib as L
+        self.env, self._L = env, L
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'gae')
+        self.sums = None
+        if self.on_device:
+            env.enable_gae()
+        else:
+            assert self.device.type == 'cpu', 'an env without gae must hold CPU tensors'
+            self._lib = L.load_library()
+
+    @staticmethod
+    def _world():
+        import torch.distributed as dist
+        return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+    def mean_std(self, sums=None):
+        """the float32 (mean, std) the normalisation takes from `sums` (default: the last call's), as Python floats; downloads the
+        three doubles (host-synchronous)"""
+        import ctypes as C
+        L = self._L
+        s = (self.sums if sums is None else sums).detach().to('cpu', torch.float64).contiguous()
+        ms = (C.c_float * 2)()
+        L.check(L.load_library().hope_adv_normalize_host(None, 0, s.data_ptr(), None, ms), 'hope_adv_normalize_host')
+        return float(ms[0]), float(ms[1])
+
+    def _host(self, x, gamma, lam, flags):
+        L = self._L
+        rows, t = x[0].shape
+        adv, v_target = torch.empty((rows, t), dtype=torch.float32), torch.empty((rows, t), dtype=torch.float32)
+        sums = torch.zeros(3, dtype=torch.float64)
+        L.check(self._lib.hope_gae_host(*(a.data_ptr() for a in x), rows, t, float(gamma), float(lam), flags, adv.data_ptr(), v_target.data_ptr(),
+                                        sums.data_ptr(), None), 'hope_gae_host')
+        return adv, v_target, sums
+
+    def __call__(self, reward, done, value, v_last, value_target, gamma, lam, normalize=True):
+        """reward / done / value / value_target [N, T], v_last [N] -> (adv [N, T], v_target [N, T]), float32.  normalize=False
+        (adv_norm=False): the scan alone, adv is the plain estimate."""
+        import torch.distributed as dist
+        L = self._L
+        x = [a.detach().to(torch.float32).contiguous() for a in (reward, done, value, v_last, value_target)]
+        split = normalize and self._world() > 1
+        if self.on_device:
+            adv, v_target, sums = self.env.gae(*x, gamma, lam, normalize=(None if not normalize else not split))
+            if split:
+                dist.all_reduce(sums)
+                self.env.adv_normalize(adv, sums)
+        else:
+            adv, v_target, sums = self._host(x, gamma, lam, 0 if not normalize else (L.GAE_SUMS if split else L.GAE_NORMALIZE))
+            if split:
+                dist.all_reduce(sums)
+                L.check(self._lib.hope_adv_normalize_host(adv.data_ptr(), adv.numel(), sums.data_ptr(), adv.data_ptr(), None), 'hope_adv_normalize_host')
+        if normalize:
+            self.sums = sums
+        return adv, v_target
+
+
+def make_gae(gae, env, agent):
+    """the trainers' `gae` argument: None (today's torch path: batched_gae and _global_mean_std), or 'device' -- the agent's `gae` becomes
+    a DeviceGae over `env`.  -> the DeviceGae or None."""
+    if gae is None:
+        return None
+    if gae != 'device':
+        raise ValueError(f"gae must be None or 'device', not {gae!r}")
+    if not hasattr(agent, 'advantages'):
+        raise ValueError("gae='device' needs an agent with an advantage block (BatchedPPO)")
+    cur = getattr(agent, 'gae', None)
+    if not (isinstance(cur, DeviceGae) and cur.env is env):
+        agent.gae = DeviceGae(env)
+    return agent.gae
+
+
 class RolloutStorage:
     """Device-resident [N, T] ring of transitions: the batched stand-in for ReplayMemory (src/model/replay_memory.py)
     as both agents use it -- PPO reads everything in time order (get_items(arange), ppo_agent.py:241), SAC samples

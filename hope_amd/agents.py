@@ -171,9 +171,12 @@ class _AgentCommon:
 class BatchedPPO(_AgentCommon):
     def __init__(self, device='cpu', use_img=False, lr=LR, gamma=GAMMA, lam=0.95, clip_epsilon=0.2, mini_epoch=10,
                  mini_batch=32, tau=TAU, adv_norm=True, state_norm=True, adam_epsilon=1e-8, img_use_tanh=True,
-                 actor_cfg=None, critic_cfg=None):
+                 actor_cfg=None, critic_cfg=None, gae=None):
+        """gae: None -- the advantage block after the critic forwards is torch code (agent_glue.batched_gae, _global_mean_std); an
+        `agent_glue.DeviceGae` -- it is one call of the library (three launches), see `advantages`."""
         self.device = torch.device(device)
         self.keys = _obs_keys(use_img)
+        self.gae = gae
         self.gamma, self.lam, self.clip, self.mini_epoch, self.mini_batch, self.tau, self.adv_norm = \
             gamma, lam, clip_epsilon, mini_epoch, mini_batch, tau, adv_norm
         self.actor = P.HopeNet(actor_cfg or P.actor_configs(use_img=use_img), img_use_tanh).to(self.device)
@@ -192,7 +195,9 @@ class BatchedPPO(_AgentCommon):
     @torch.no_grad()
     def advantages(self, obs, reward, done, last_obs, chunk=65536):
         """GAE block of PPO.update (:255-273).  obs: normalised observations {k: [N,T,...]}, last_obs {k: [N,...]}
-        (the observation after the newest transition), reward / done [N,T].  Returns (adv [N,T], v_target [N,T])."""
+        (the observation after the newest transition), reward / done [N,T].  Returns (adv [N,T], v_target [N,T]).
+        With `self.gae` set the three critic forwards stay here and everything after them is its call; on the device the results
+        are then persistent tensors of the env, valid until the next call."""
         n, t = reward.shape
         flat = {k: v.reshape((n * t,) + v.shape[2:]) for k, v in obs.items()}
 
@@ -201,6 +206,8 @@ class BatchedPPO(_AgentCommon):
             return torch.cat([net({k: v[i:i + chunk] for k, v in x.items()}) for i in range(0, m, chunk)]).squeeze(1)
         value = run(self.critic, flat).view(n, t)
         v_last = run(self.critic, last_obs)
+        if self.gae is not None:
+            return self.gae(reward, done, value, v_last, run(self.critic_target, flat).view(n, t), self.gamma, self.lam, normalize=self.adv_norm)
         next_value = torch.cat([value[:, 1:], v_last.unsqueeze(1)], dim=1)
         adv, _ = G.batched_gae(reward, value, next_value, done, self.gamma, self.lam)
         v_target = adv + run(self.critic_target, flat).view(n, t)

@@ -549,6 +549,60 @@ class ParkingBatch:
         L.check(self.lib.hope_env_obsnorm_set(self.h, int(n_state), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data), 'hope_env_obsnorm_set')
         return self
 
+    # -- PPO's advantage block on the device (hope_env.h; rule: csrc/hope_gae_core.h) -----------------------------------
+    def enable_gae(self):
+        """GAE along T, the critic's target and the advantages' normalisation as three kernels (k_gae_scan, k_gae_merge,
+        k_adv_apply) over [rows, T] float32 tensors.  Off by default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_gae_enable(self.h), 'hope_env_gae_enable')
+        if getattr(self, 'gae_sums', None) is None:
+            self.gae_sums = torch.zeros(3, dtype=torch.float64, device=self.device)
+            self._gae_out = None                                   # (adv, v_target): [N, T], allocated at the first call for its T
+        return self
+
+    def disable_gae(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_gae_disable(self.h), 'hope_env_gae_disable')
+        return self
+
+    def gae(self, reward, done, value, v_last, value_target, gamma, lam, normalize=True, sums=None):
+        """reward / done / value / value_target [rows, T], v_last [rows]: float32, contiguous, on the env's device; 1 <= rows <= N,
+        1 <= T <= 4096.  At most three launches on the current stream, no host synchronisation.
+        normalize: True -- scan, sums and the normalisation of adv; False -- scan and sums only (the split call: all-reduce `sums`,
+        then adv_normalize); None -- the scan alone (adv_norm=False).
+        sums: a float64 [3] device tensor that takes {sum adv, sum adv^2, rows T}; None: this object's `gae_sums`.
+        -> (adv [rows, T], v_target [rows, T], sums): (views of) persistent tensors of this object, overwritten by the next call."""
+        dev = self.device
+        assert reward.dim() == 2 and v_last.dim() == 1
+        rows, t = reward.shape
+        for x in (reward, done, value, value_target):
+            assert x.shape == (rows, t)
+        assert v_last.shape == (rows,)
+        for x in (reward, done, value, v_last, value_target):
+            assert x.dtype == torch.float32 and x.device == dev and x.is_contiguous()
+        sums = getattr(self, 'gae_sums', None) if sums is None else sums
+        if sums is not None:
+            assert sums.dtype == torch.float64 and sums.shape == (3,) and sums.device == dev and sums.is_contiguous()
+        out = getattr(self, '_gae_out', None)
+        if out is None or out[0].shape[1] != t:                    # (before enable_gae the library reports that it is off)
+            out = self._gae_out = tuple(torch.zeros((max(self.n, rows), t), dtype=torch.float32, device=dev) for _ in range(2))
+        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        flags = 0 if normalize is None else (L.GAE_SUMS | (L.GAE_NORMALIZE if normalize else 0))
+        L.check(self.lib.hope_env_gae(self.h, P(reward), P(done), P(value), P(v_last), P(value_target), rows, t, float(gamma), float(lam), flags,
+                                      P(out[0]), P(out[1]), P(sums), self._stream()), 'hope_env_gae')
+        return out[0][:rows], out[1][:rows], sums
+
+    def adv_normalize(self, adv, sums, out=None):
+        """out = (adv - mean) / (std + 1e-5) from sums = {sum, sum of squares, count} (float64 [3] on the device, e.g. all-reduced);
+        out=None: in place.  One launch on the current stream."""
+        out = adv if out is None else out
+        assert adv.dtype == torch.float32 and adv.is_contiguous() and adv.device == self.device
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device and out.shape == adv.shape
+        assert sums.dtype == torch.float64 and sums.shape == (3,) and sums.device == self.device and sums.is_contiguous()
+        L.check(self.lib.hope_env_adv_normalize(self.h, C.c_void_p(adv.data_ptr()), adv.numel(), C.c_void_p(sums.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), self._stream()), 'hope_env_adv_normalize')
+        return out
+
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
     def enable_eval_tracker(self):
         """eval()'s per-episode tally (eval_utils.py:35-57) as device state of the handle (80 B per scene) and three kernels:

@@ -1,5 +1,5 @@
 // hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
-// action, normalisation of the observations, bookkeeping of an evaluation run -- and their host twins.  They share nothing with the
+// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block -- and their host twins.  They share nothing with the
 // step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 #include "hope_chooser_kernel.h"
 #include "hope_obsnorm_kernel.h"
 #include "hope_evaltrack_kernel.h"
+#include "hope_gae_kernel.h"
 
 using namespace hope;
 
@@ -17,6 +18,7 @@ using namespace hope;
 #define CHOOSER_ON(h, name) HOPE_NEED((h)->choose.on, name, "the chooser is off (hope_env_chooser_enable first)")
 #define OBSNORM_ON(h, name) HOPE_NEED((h)->onorm.on, name, "the normalisation is off (hope_env_obsnorm_enable first)")
 #define EVAL_ON(h, name) HOPE_NEED((h)->evalt.on, name, "the evaluation tracker is off (hope_env_eval_enable first)")
+#define GAE_ON(h, name) HOPE_NEED((h)->gae.on, name, "the advantage block is off (hope_env_gae_enable first)")
 
 // What every hope_env_*_enable does with a feature's device buffer: allocate it if absent, fill it (from `src`, or with zeros) and
 // wait.  On any failure the buffer is freed and *buf is null; the caller then puts the feature's struct back to "off" (*_free).
@@ -67,6 +69,12 @@ void hope::onorm_free(hope_env_t* h) {
 void hope::evalt_free(hope_env_t* h) {
     if (h->evalt.state) hipFree(h->evalt.state);
     h->evalt = hope_env::EvalTrack{};
+}
+
+void hope::gae_free(hope_env_t* h) {
+    if (h->gae.part) hipFree(h->gae.part);
+    if (h->gae.sums) hipFree(h->gae.sums);
+    h->gae = hope_env::Gae{};
 }
 
 template <class T>
@@ -402,6 +410,85 @@ int hope_eval_track_host(int64_t n, int64_t state_stride, void* state, const voi
     const int rc = et_track_host(n, state_stride, state, target, obs_f64, pose, reward, status, done, rs_word, word_out, done_out);
     if (rc != HOPE_OK)
         return fail(rc, "hope_eval_track_host: bad argument (n <= 0, state_stride < n, or a null state / target / pose / reward / status / done / rs_word / word_out / done_out)");
+    return HOPE_OK;
+}
+
+// ---- PPO's advantage block (include/hope_env.h; kernels: hope_gae_kernel.h, rule: hope_gae_core.h) ----
+int hope_env_gae_enable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_gae_enable");
+    if (h->gae.on) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    int rc = device_buffer("hope_env_gae_enable", &h->gae.part, (size_t)2 * (size_t)ga_chunks(h->n) * sizeof(double));
+    if (rc == HOPE_OK) rc = device_buffer("hope_env_gae_enable", &h->gae.sums, 3 * sizeof(double));
+    if (rc != HOPE_OK) { gae_free(h); return rc; }
+    h->gae.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_gae_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_gae_disable");
+    return feature_disable(h, gae_free);
+}
+
+int hope_env_gae(hope_env_t* h, const float* reward, const float* done, const float* value, const float* v_last, const float* value_target, int rows, int T,
+                 double gamma, double lam, uint32_t flags, float* adv, float* v_target, double* sums, void* stream) {
+    HOPE_ENTER(h, "hope_env_gae");
+    GAE_ON(h, "hope_env_gae");
+    if (!reward || !done || !value || !v_last || !value_target || !adv || !v_target)
+        return fail(HOPE_EINVAL, "hope_env_gae: null reward / done / value / v_last / value_target / adv / v_target");
+    if (rows < 1 || rows > h->n) return fail(HOPE_EINVAL, "hope_env_gae: rows must be 1 .. the handle's scenes");
+    if (T < 1 || T > HOPE_GAE_MAX_T) return fail(HOPE_EINVAL, "hope_env_gae: T must be 1 .. " + std::to_string(HOPE_GAE_MAX_T));
+    if (flags & ~(uint32_t)(HOPE_GAE_SUMS | HOPE_GAE_NORMALIZE)) return fail(HOPE_EINVAL, "hope_env_gae: flags are HOPE_GAE_SUMS | HOPE_GAE_NORMALIZE");
+    if (!ga_finite(gamma) || !ga_finite(lam)) return fail(HOPE_EINVAL, "hope_env_gae: gamma / lam is not finite");
+    const uintptr_t all = (uintptr_t)reward | (uintptr_t)done | (uintptr_t)value | (uintptr_t)value_target | (uintptr_t)adv | (uintptr_t)v_target;
+    if ((all & 3) || ((uintptr_t)v_last & 3) || ((uintptr_t)sums & 7))
+        return fail(HOPE_EINVAL, "hope_env_gae: misaligned buffer (float32 tensors 4 bytes, sums 8 bytes)");
+    HOPE_ON_DEVICE(h);
+    const bool want_sums = flags & (HOPE_GAE_SUMS | HOPE_GAE_NORMALIZE);
+    const long long nk = ga_chunks(rows);                         // <= the partials' room: rows <= N
+    double* part = want_sums ? h->gae.part : nullptr;
+    double* s = sums ? sums : h->gae.sums;
+    const dim3 grid((unsigned)nk), block(64);
+    if (T % 4 == 0 && !(all & 15))
+        hipLaunchKernelGGL(k_gae_scan<4>, grid, block, 0, (hipStream_t)stream, reward, done, value, v_last, value_target, rows, T, gamma, lam, adv, v_target, nk,
+                           part);
+    else
+        hipLaunchKernelGGL(k_gae_scan<1>, grid, block, 0, (hipStream_t)stream, reward, done, value, v_last, value_target, rows, T, gamma, lam, adv, v_target, nk,
+                           part);
+    const long long count = (long long)rows * T;
+    if (want_sums) hipLaunchKernelGGL(k_gae_merge, dim3(1), block, 0, (hipStream_t)stream, nk, (double)count, part, s);
+    if (flags & HOPE_GAE_NORMALIZE)
+        hipLaunchKernelGGL(k_adv_apply, dim3((unsigned)((count + 63) / 64)), block, 0, (hipStream_t)stream, (const float*)adv, count, (const double*)s, adv);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_adv_normalize(hope_env_t* h, const float* adv, int64_t count, const double* sums, float* out, void* stream) {
+    HOPE_ENTER(h, "hope_env_adv_normalize");
+    GAE_ON(h, "hope_env_adv_normalize");
+    if (!adv || !out) return fail(HOPE_EINVAL, "hope_env_adv_normalize: null adv / out");
+    if (count < 1 || count > (int64_t)h->n * HOPE_GAE_MAX_T) return fail(HOPE_EINVAL, "hope_env_adv_normalize: count must be 1 .. the handle's scenes x " + std::to_string(HOPE_GAE_MAX_T));
+    if (((uintptr_t)adv & 3) || ((uintptr_t)out & 3) || ((uintptr_t)sums & 7))
+        return fail(HOPE_EINVAL, "hope_env_adv_normalize: misaligned buffer (adv and out 4 bytes, sums 8 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_adv_apply, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, (hipStream_t)stream, adv, (long long)count,
+                       sums ? sums : (const double*)h->gae.sums, out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_gae_host(const float* reward, const float* done, const float* value, const float* v_last, const float* value_target, int64_t rows, int64_t T,
+                  double gamma, double lam, uint32_t flags, float* adv, float* v_target, double* sums, float* delta) {
+    const int rc = ga_host(reward, done, value, v_last, value_target, rows, T, gamma, lam, flags, adv, v_target, sums, delta);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_gae_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_gae_host: bad argument (a null reward / done / value / v_last / value_target / adv / v_target, rows or T < 1, an unknown flag, or a gamma / lam that is not finite)");
+    return HOPE_OK;
+}
+
+int hope_adv_normalize_host(const float* adv, int64_t count, const double* sums, float* out, float* mean_std) {
+    const int rc = ga_normalize_host(adv, count, sums, out, mean_std);
+    if (rc != HOPE_OK) return fail(rc, "hope_adv_normalize_host: bad argument (null sums, a negative count, or a null adv / out with count > 0)");
     return HOPE_OK;
 }
 

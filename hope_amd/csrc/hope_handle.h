@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -223,6 +223,9 @@ struct hope_env {
     // bookkeeping of an evaluation run (hope_evaltrack_kernel.h): [ET_WORDS][n] state words, nullptr while it is off; the action box
     // of the stuck detector's draw reaches k_eval_override as an argument
     struct EvalTrack { bool on = false; EtBox box = {}; uint64_t* state = nullptr; } evalt;
+    // PPO's advantage block (hope_gae_kernel.h): part = the chunk partials of the two sums ([2][chunks of the call], room for
+    // ceil(n / 64) chunks), sums = the handle's own {sum adv, sum adv^2, count}
+    struct Gae { bool on = false; double* part = nullptr; double* sums = nullptr; } gae;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -236,4 +239,5 @@ void plan_free(hope_env_t* h);
 void choose_free(hope_env_t* h);
 void onorm_free(hope_env_t* h);
 void evalt_free(hope_env_t* h);
+void gae_free(hope_env_t* h);
 }  // namespace hope

@@ -302,13 +302,16 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None, obs_norm=None):
-        """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update"""
+                 curriculum=None, chooser=None, obs_norm=None, gae=None):
+        """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update
+        gae: None -- the agent's advantage block is torch code (a Python loop along the horizon); 'device' -- the agent's `gae` becomes
+        an agent_glue.DeviceGae over `env`: GAE, the critic's target and the advantages' normalisation in three launches."""
         self._curriculum_per_update = curriculum is not None and 'update_every' not in curriculum
         if self._curriculum_per_update:
             curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm)
+        self.gae = G.make_gae(gae, env, agent)
         self.updates = 0
 
     def step(self):

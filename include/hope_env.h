@@ -747,6 +747,49 @@ int hope_eval_track_host(int64_t n, int64_t state_stride, void *state, const voi
                          const void *reward, const int32_t *status, const uint8_t *done, const int8_t *rs_word, int8_t *word_out,
                          uint8_t *done_out);
 
+/* ---- PPO's advantage block (additive to ABI 8) ----------------------------------------------------------------------------------
+ * What BatchedPPO.advantages does after the critic forwards (the reference's PPO.update, src/model/agent/ppo_agent.py:255-273), for
+ * every scene at once: the generalised advantage estimate along T, the critic's target adv + V_target(s), and the advantages'
+ * normalisation by their global mean and unbiased standard deviation.  Three kernels: k_gae_scan (one lane per row: the backward
+ * scan and the row's share of the two sums), k_gae_merge (the chunk partials' tree), k_adv_apply.  The sums have one arithmetic
+ * order, independent of the launch geometry, and are plain sums {sum adv, sum adv^2, count}: ranks add theirs between
+ * hope_env_gae(HOPE_GAE_SUMS) and hope_env_adv_normalize.  Off until enabled; with it off no launch, pointer or output of any other
+ * entry point differs.  The rule and the bit-equal host twins: hope_amd/csrc/hope_gae_core.h, DESIGN.md 5i. */
+#define HOPE_GAE_SUMS 0x1u          /* also reduce {sum adv, sum adv^2, rows * T} into `sums` */
+#define HOPE_GAE_NORMALIZE 0x2u     /* implies HOPE_GAE_SUMS; then adv = (adv - mean) / (std + 1e-5f) in place */
+#define HOPE_GAE_MAX_T 4096
+/* allocate the chunk partials (2 x ceil(N / 64) doubles) and the handle's own sums[3].  Enabling an enabled handle changes nothing.
+ * Host-synchronous. */
+int hope_env_gae_enable(hope_env_t *h);
+/* free both.  Host-synchronous (calls in flight use them). */
+int hope_env_gae_disable(hope_env_t *h);
+/* asynchronous on `stream`; waits for nothing, never synchronises the host and does not join a deferred search.  DEVICE buffers,
+ * float32, contiguous, 4-byte aligned (with T % 4 == 0 and every [rows][T] base 16-byte aligned the scan moves four time steps per
+ * load and store; the results do not depend on that):
+ *   reward, done, value, value_target [rows][T]   done holds 0 / 1; value_target is the target critic's output
+ *   v_last [rows]                                 the critic's value of the observation after the newest column
+ *   adv, v_target [rows][T]                       outputs
+ *   sums double[3] (8-byte aligned) or NULL       NULL: the handle's own block (what a later hope_env_adv_normalize with NULL reads)
+ * 1 <= rows <= N, 1 <= T <= HOPE_GAE_MAX_T; gamma and lam finite.  flags: 0 (scan only), HOPE_GAE_SUMS, HOPE_GAE_NORMALIZE or
+ * both.  The chunk partials belong to the handle, so calls belong on one stream (or are ordered by the caller).
+ * HOPE_ESTATE before hope_env_gae_enable; HOPE_EINVAL for a NULL required pointer, a misaligned pointer, rows or T out of range, an
+ * unknown flag, a gamma or lam that is not finite.  The handle stays usable after an error. */
+int hope_env_gae(hope_env_t *h, const float *reward, const float *done, const float *value, const float *v_last,
+                 const float *value_target, int rows, int T, double gamma, double lam, uint32_t flags, float *adv, float *v_target,
+                 double *sums, void *stream);
+/* step 3 alone: out[e] = (adv[e] - mean) / (std + 1e-5f) for e < count, mean and std from `sums` (DEVICE double[3], e.g. all-reduced
+ * by the caller; NULL: the handle's own).  out may be adv.  count >= 1.  Asynchronous on `stream`. */
+int hope_env_adv_normalize(hope_env_t *h, const float *adv, int64_t count, const double *sums, float *out, void *stream);
+/* The same over HOST arrays: pure host code from the same source, no handle, no device; bit-equal to the kernels.  No alignment
+ * requirements, no upper bound on rows or T.  hope_gae_host: sums and delta may be NULL; delta [rows][T] takes the float32
+ * one-step residuals (agent_glue.batched_gae's second result).  hope_adv_normalize_host: mean_std (may be NULL) takes the float32
+ * mean and std that the normalisation uses; count == 0 computes those alone (adv and out are then not read).  HOPE_EINVAL for a
+ * NULL required pointer, rows or T < 1, an unknown flag, a gamma or lam that is not finite, a negative count. */
+int hope_gae_host(const float *reward, const float *done, const float *value, const float *v_last, const float *value_target,
+                  int64_t rows, int64_t T, double gamma, double lam, uint32_t flags, float *adv, float *v_target, double *sums,
+                  float *delta);
+int hope_adv_normalize_host(const float *adv, int64_t count, const double *sums, float *out, float *mean_std);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
