@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import numpy as np
+
 from .build import lib_path
 
 # mirror of include/hope_env.h
@@ -18,11 +20,6 @@ IMG_SIZE, IMG_CHANNELS, TRAJ_RENDER_LEN = 64, 3, 20
 AUTO_RESET = 0x20
 KERNELS = ('k_kinematics', 'k_env_step', 'k_rs_words', 'k_rs_validate', 'k_bev_image', 'k_bev_prep', 'k_rs_compact', 'k_post', 'k_rs_segs', 'k_rs_screen')
 ABI_VERSION = 8
-
-EXPORTS = ['hope_env_create', 'hope_env_destroy', 'hope_last_error', 'hope_abi_version', 'hope_env_upload_tables',
-           'hope_env_set_scenes', 'hope_env_step', 'hope_env_wait_rs', 'hope_env_last_step', 'hope_env_wait_rs_step', 'hope_env_download_n_obst', 'hope_env_queue_check', 'hope_env_reset_obs', 'hope_env_download_state',
-           'hope_env_upload_state', 'hope_env_restart', 'hope_env_set_pool', 'hope_env_pool_staging', 'hope_env_commit_pool', 'hope_env_commit_pool_relaxed', 'hope_env_pool_staging_ready', 'hope_env_pool_generation', 'hope_env_redraw', 'hope_env_set_redraw_seed', 'hope_env_download_pool_index', 'hope_env_set_dlp_cases', 'hope_env_pool_overflow', 'hope_env_set_draw_class', 'hope_env_download_scenes', 'hope_env_download_pool_state', 'hope_env_restore_maps', 'hope_env_kernel_ms', 'hope_env_kernel_union_ms', 'hope_env_profile_kernels', 'hope_debug_math', 'hope_debug_geom', 'hope_debug_traffic', 'hope_debug_mask_lut', 'hope_debug_rs_prof', 'hope_debug_rs_log', 'hope_debug_rs_filter_stats', 'hope_debug_rs_filter_dump', 'hope_debug_step_prof', 'hope_debug_census', 'hope_scenegen_generate', 'hope_scenegen_default_threads', 'hope_scenegen_generate_det', 'hope_scenegen_generate_device', 'hope_scenegen_log_det', 'hope_env_generate_pool', 'hope_env_curriculum_enable', 'hope_env_curriculum_disable', 'hope_env_set_pool_buckets', 'hope_env_curriculum_tally', 'hope_env_curriculum_update', 'hope_env_curriculum_state', 'hope_env_curriculum_set_windows', 'hope_env_curriculum_download_lists', 'hope_curriculum_lists_host', 'hope_curriculum_fold_host', 'hope_map_level_host', 'hope_map_level_device', 'hope_env_map_level', 'hope_env_planner_enable', 'hope_env_planner_disable', 'hope_env_planner_reset', 'hope_env_planner_step', 'hope_planner_step_host', 'hope_env_planner_download_state', 'hope_env_chooser_enable', 'hope_env_chooser_disable', 'hope_env_choose', 'hope_chooser_host', 'hope_env_obsnorm_enable', 'hope_env_obsnorm_disable', 'hope_env_obsnorm_set', 'hope_env_obsnorm_get', 'hope_env_obsnorm', 'hope_obsnorm_host', 'hope_env_eval_enable', 'hope_env_eval_disable', 'hope_env_eval_begin', 'hope_env_eval_override', 'hope_env_eval_track', 'hope_env_eval_records', 'hope_env_eval_download_state', 'hope_eval_begin_host', 'hope_eval_override_host', 'hope_eval_track_host', 'hope_env_gae_enable', 'hope_env_gae_disable', 'hope_env_gae', 'hope_env_adv_normalize', 'hope_gae_host', 'hope_adv_normalize_host', 'hope_env_num_scenes', 'hope_env_max_obstacles', 'hope_env_device_arch']
-
 
 CURRICULUM_LIST_LEN = 1 << 20
 PLAN_STATE_WORDS, PLAN_STEP_RATIO, PLAN_FORCED, PLAN_NO_POP = 6, 1.25, 0x1, 0x2
@@ -60,6 +57,114 @@ class ObsNormState(C.Structure):
     _fields_ = [('n_state', C.c_int64), ('mean', C.c_double * OBSNORM_COLS), ('S', C.c_double * OBSNORM_COLS), ('std', C.c_double * OBSNORM_COLS)]
 
 
+# the prototypes of include/hope_env.h, one entry per exported call: name -> (return type, parameter types).  The parameter kinds:
+# pointer, int / int32_t, uint32_t, int64_t, uint64_t, double, size_t; S is the `const char *` of the two calls that return text.
+# tests/test_host.py compares this table, the constants above and the three structures with the header.
+P, I, U32, I64, U64, D, SZ, S = C.c_void_p, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, C.c_double, C.c_size_t, C.c_char_p
+PP = C.POINTER(C.c_void_p)
+PROTOTYPES = {
+    'hope_env_create': (I, [PP, I, I, I, U32]),
+    'hope_env_destroy': (I, [P]),
+    'hope_last_error': (S, []),
+    'hope_abi_version': (I, []),
+    'hope_env_upload_tables': (I, [P] * 4),
+    'hope_env_set_scenes': (I, [P, P, I] + [P] * 5),
+    'hope_env_step': (I, [P, P, P, U32, C.POINTER(StepOut), P]),
+    'hope_env_wait_rs': (I, [P, P]),
+    'hope_env_last_step': (I, [P, P]),
+    'hope_env_wait_rs_step': (I, [P, U64, P]),
+    'hope_env_reset_obs': (I, [P, P, U32, C.POINTER(StepOut), P]),
+    'hope_env_restart': (I, [P, P, P]),
+    'hope_env_set_pool': (I, [P, I] + [P] * 5),
+    'hope_env_pool_staging': (I, [P, I] + [PP] * 5),
+    'hope_env_commit_pool': (I, [P, I, P]),
+    'hope_env_commit_pool_relaxed': (I, [P, I]),
+    'hope_env_pool_staging_ready': (I, [P]),
+    'hope_env_pool_generation': (I, [P, P]),
+    'hope_env_set_redraw_seed': (I, [P, U64]),
+    'hope_env_redraw': (I, [P, P, U64, P]),
+    'hope_env_download_pool_index': (I, [P, P]),
+    'hope_env_set_dlp_cases': (I, [P, I] + [P] * 4 + [I, P, P]),
+    'hope_env_set_draw_class': (I, [P, P, I, P]),
+    'hope_env_pool_overflow': (I, [P, P]),
+    'hope_env_download_scenes': (I, [P, P, I] + [P] * 5),
+    'hope_env_download_n_obst': (I, [P, P]),
+    'hope_env_download_pool_state': (I, [P, P, P]),
+    'hope_env_restore_maps': (I, [P, P, P, U64, U64]),
+    'hope_env_queue_check': (I, [P] * 4),
+    'hope_env_kernel_ms': (I, [P, P, P, I]),
+    'hope_env_kernel_union_ms': (I, [P, P, P, I]),
+    'hope_env_profile_kernels': (I, [P, U32]),
+    'hope_env_download_state': (I, [P] * 4),
+    'hope_env_upload_state': (I, [P] * 4),
+    'hope_debug_math': (I, [I, I] + [P] * 4),
+    'hope_debug_geom': (I, [I, I, I, P, P, P]),
+    'hope_debug_mask_lut': (I, [P] * 4),
+    'hope_debug_traffic': (I, [I, SZ, P, P]),
+    'hope_debug_rs_prof': (I, [P, I]),
+    'hope_debug_rs_filter_stats': (I, [P, I]),
+    'hope_debug_rs_filter_dump': (I, [P]),
+    'hope_debug_rs_log': (I, [P, I, P, I]),
+    'hope_debug_step_prof': (I, [P, I]),
+    'hope_debug_census': (I, [P, I]),
+    'hope_scenegen_generate': (I, [I, I, I, U64, I64, I] + [P] * 6 + [I]),
+    'hope_scenegen_default_threads': (I, []),
+    'hope_scenegen_generate_det': (I, [I, I, I, U64, I64, I] + [P] * 6 + [I]),
+    'hope_scenegen_generate_device': (I, [I] * 4 + [U64, I64, I] + [P] * 7),
+    'hope_scenegen_log_det': (I, [I, P, P]),
+    'hope_env_generate_pool': (I, [P, I, P, U64, I64, I]),
+    'hope_env_curriculum_enable': (I, [P, P]),
+    'hope_env_curriculum_disable': (I, [P]),
+    'hope_env_set_pool_buckets': (I, [P, I, P]),
+    'hope_env_curriculum_tally': (I, [P] * 4),
+    'hope_env_curriculum_update': (I, [P, P]),
+    'hope_env_curriculum_state': (I, [P] * 9),
+    'hope_env_curriculum_set_windows': (I, [P, I] + [P] * 4),
+    'hope_env_curriculum_download_lists': (I, [P] * 4),
+    'hope_curriculum_lists_host': (I, [P, I, P, P, I, I] + [P] * 8),
+    'hope_curriculum_fold_host': (I, [P, P, D, D, D]),
+    'hope_map_level_host': (I, [I, I] + [P] * 6 + [I]),
+    'hope_map_level_device': (I, [I, I, I] + [P] * 7),
+    'hope_env_map_level': (I, [P] * 5),
+    'hope_env_planner_enable': (I, [P, D]),
+    'hope_env_planner_disable': (I, [P]),
+    'hope_env_planner_reset': (I, [P, P, P]),
+    'hope_env_planner_step': (I, [P] * 4 + [I, U64, P, P, P, I, P]),
+    'hope_planner_step_host': (I, [I, D, P, P, P, I, P, I, P, P, P, I]),
+    'hope_env_planner_download_state': (I, [P, P]),
+    'hope_env_chooser_enable': (I, [P, P]),
+    'hope_env_chooser_disable': (I, [P]),
+    'hope_env_choose': (I, [P, P, P, I, I] + [P] * 4 + [U64, U64] + [P] * 6),
+    'hope_chooser_host': (I, [I, P, P, P, I, I, P, I, P, P, P, U64, U64, U64, P, I] + [P] * 4),
+    'hope_env_obsnorm_enable': (I, [P]),
+    'hope_env_obsnorm_disable': (I, [P]),
+    'hope_env_obsnorm_set': (I, [P, I64, P, P, P]),
+    'hope_env_obsnorm_get': (I, [P, C.POINTER(I64), P, P, P]),
+    'hope_env_obsnorm': (I, [P, P, P, I, I, U32, P, P, P]),
+    'hope_obsnorm_host': (I, [C.POINTER(ObsNormState), P, P, I64, I, U32, P, P]),
+    'hope_env_eval_enable': (I, [P, P]),
+    'hope_env_eval_disable': (I, [P]),
+    'hope_env_eval_begin': (I, [P] * 4),
+    'hope_env_eval_override': (I, [P, P, I, P, U64, U64, P, P]),
+    'hope_env_eval_track': (I, [P] * 10),
+    'hope_env_eval_records': (I, [P, P, P]),
+    'hope_env_eval_download_state': (I, [P, P]),
+    'hope_eval_begin_host': (I, [I64, I64, P, P, I, P]),
+    'hope_eval_override_host': (I, [I64, I64, P, P, P, I, P, U64, U64, U64, P]),
+    'hope_eval_track_host': (I, [I64, I64, P, P, I] + [P] * 7),
+    'hope_env_gae_enable': (I, [P]),
+    'hope_env_gae_disable': (I, [P]),
+    'hope_env_gae': (I, [P] * 6 + [I, I, D, D, U32] + [P] * 4),
+    'hope_env_adv_normalize': (I, [P, P, I64, P, P, P]),
+    'hope_gae_host': (I, [P] * 5 + [I64, I64, D, D, U32] + [P] * 4),
+    'hope_adv_normalize_host': (I, [P, I64, P, P, P]),
+    'hope_env_num_scenes': (I, [P]),
+    'hope_env_max_obstacles': (I, [P]),
+    'hope_env_device_arch': (S, [P]),
+}
+EXPORTS = list(PROTOTYPES)
+
+
 _lib = None
 
 
@@ -80,106 +185,11 @@ def load_library():
         raise HopeError(f'{path} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                         '(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     L = C.CDLL(path)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         if not hasattr(L, name):
             raise HopeError(f'{path} does not export {name}')
-    L.hope_last_error.restype = C.c_char_p
-    L.hope_env_device_arch.restype = C.c_char_p
-    L.hope_env_device_arch.argtypes = [C.c_void_p]
-    L.hope_env_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_uint32]
-    L.hope_env_destroy.argtypes = [C.c_void_p]
-    L.hope_env_upload_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_set_scenes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-    L.hope_env_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(StepOut), C.c_void_p]
-    L.hope_env_wait_rs.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_last_step.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_wait_rs_step.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    L.hope_env_download_n_obst.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_queue_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_reset_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(StepOut), C.c_void_p]
-    L.hope_env_download_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_upload_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_restart.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_set_pool.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_pool_staging.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 5
-    L.hope_env_commit_pool.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.hope_env_commit_pool_relaxed.argtypes = [C.c_void_p, C.c_int]
-    L.hope_env_redraw.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.hope_env_set_redraw_seed.argtypes = [C.c_void_p, C.c_uint64]
-    L.hope_env_download_pool_index.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_set_dlp_cases.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.hope_env_set_draw_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.hope_env_pool_overflow.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_download_scenes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_download_pool_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_restore_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
-    L.hope_env_pool_staging_ready.argtypes = [C.c_void_p]
-    L.hope_env_pool_generation.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_kernel_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.hope_env_kernel_union_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.hope_env_profile_kernels.argtypes = [C.c_void_p, C.c_uint32]
-    L.hope_debug_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_debug_geom.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_debug_traffic.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.hope_debug_mask_lut.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_scenegen_generate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.hope_scenegen_generate_det.argtypes = L.hope_scenegen_generate.argtypes
-    L.hope_scenegen_generate_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_scenegen_log_det.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    L.hope_env_generate_pool.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_int]
-    L.hope_env_curriculum_enable.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_curriculum_disable.argtypes = [C.c_void_p]
-    L.hope_env_set_pool_buckets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.hope_env_curriculum_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_curriculum_update.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_curriculum_state.argtypes = [C.c_void_p] + [C.c_void_p] * 8
-    L.hope_env_curriculum_set_windows.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    L.hope_env_curriculum_download_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_curriculum_lists_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
-    L.hope_curriculum_fold_host.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]
-    L.hope_map_level_host.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
-    L.hope_map_level_device.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
-    L.hope_env_map_level.argtypes = [C.c_void_p] * 5
-    L.hope_env_planner_enable.argtypes = [C.c_void_p, C.c_double]
-    L.hope_env_planner_disable.argtypes = [C.c_void_p]
-    L.hope_env_planner_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_planner_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_int, C.c_void_p]
-    L.hope_planner_step_host.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int]
-    L.hope_env_planner_download_state.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_chooser_enable.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_chooser_disable.argtypes = [C.c_void_p]
-    L.hope_env_choose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6
-    L.hope_chooser_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + \
-                                   [C.c_uint64] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    L.hope_env_obsnorm_enable.argtypes = [C.c_void_p]
-    L.hope_env_obsnorm_disable.argtypes = [C.c_void_p]
-    L.hope_env_obsnorm_set.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_obsnorm_get.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_obsnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_obsnorm_host.argtypes = [C.POINTER(ObsNormState), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.hope_env_eval_enable.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_env_eval_disable.argtypes = [C.c_void_p]
-    L.hope_env_eval_begin.argtypes = [C.c_void_p] * 4
-    L.hope_env_eval_override.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.hope_env_eval_track.argtypes = [C.c_void_p] * 10
-    L.hope_env_eval_records.argtypes = [C.c_void_p] * 3
-    L.hope_env_eval_download_state.argtypes = [C.c_void_p, C.c_void_p]
-    L.hope_eval_begin_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.hope_eval_override_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_uint64] * 3 + [C.c_void_p]
-    L.hope_eval_track_host.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-    L.hope_env_gae_enable.argtypes = [C.c_void_p]
-    L.hope_env_gae_disable.argtypes = [C.c_void_p]
-    L.hope_env_gae.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 4
-    L.hope_env_adv_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_gae_host.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 4
-    L.hope_adv_normalize_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.hope_env_num_scenes.argtypes = [C.c_void_p]
-    L.hope_env_max_obstacles.argtypes = [C.c_void_p]
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     if L.hope_abi_version() != ABI_VERSION:
         raise HopeError(f'ABI mismatch: library {L.hope_abi_version()} vs binding {ABI_VERSION}')
     _lib = L
@@ -190,3 +200,44 @@ def check(rc, what=''):
     if rc != 0:
         msg = load_library().hope_last_error().decode(errors='replace')
         raise HopeError(f'{what} failed (code {rc}): {msg}')
+
+
+def seed64(seed):
+    """a Python int of any size or sign as the uint64_t seed / counter of the draws"""
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+# The library sees addresses only: the two functions below are the one size check between a caller's memory and a kernel or a host
+# loop that runs over it.  Every tensor or array handed to a call goes through one of them, with the call's and the argument's name.
+def tensor_arg(call, name, x, dtype, shape, device, optional=False):
+    """the torch tensor x as a call's pointer argument (c_void_p): x has `dtype` (one torch dtype or a tuple of them) and exactly
+    `shape` (None in it: any extent), lives on `device` and is contiguous -- or HopeError.  optional: None passes as None (NULL)."""
+    if x is None and optional:
+        return None
+    dtypes = dtype if type(dtype) is tuple else (dtype,)
+    try:
+        got = x.shape                                # (the passing case is the hot path: step() comes through here twice)
+        if x.dtype in dtypes and x.device == device and x.is_contiguous() \
+                and (got == shape or (len(got) == len(shape) and all(w is None or w == s for s, w in zip(got, shape)))):
+            return C.c_void_p(x.data_ptr())
+        got = f"{str(x.dtype).replace('torch.', '')} {list(got)}{'' if x.is_contiguous() else ' strided'} on {x.device}"
+    except AttributeError:                           # None, a numpy array, a list: no tensor
+        got = 'None' if x is None else type(x).__name__
+    want = ' or '.join(str(d).replace('torch.', '') for d in dtypes)
+    raise HopeError(f"{call}: {name} must be {want} {str(list(shape)).replace('None', '?')} contiguous on {device}, got {got}")
+
+
+def array_arg(call, name, x, dtype, shape, optional=False):
+    """x as the C-contiguous numpy array of `dtype` (np.ascontiguousarray: lists and other dtypes convert, as they always did) and
+    exactly `shape` (None in it: any extent) that a call reads or writes -- or HopeError.  Returns the array: pass its `.ctypes`, and
+    hold the array until the call has returned.  optional: None passes as None."""
+    if x is None and optional:
+        return None
+    try:
+        a = None if x is None else np.ascontiguousarray(x, dtype=dtype)
+    except (TypeError, ValueError):                  # not convertible to dtype
+        a = None
+    if a is not None and a.ndim == len(shape) and all(w is None or w == s for s, w in zip(a.shape, shape)):
+        return a
+    got = f'{a.dtype.name} {list(a.shape)}' if a is not None else 'None' if x is None else type(x).__name__
+    raise HopeError(f"{call}: {name} must be {np.dtype(dtype).name} {str(list(shape)).replace('None', '?')}, got {got}")

@@ -11,9 +11,12 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
 import math
+from functools import partial
 
+import numpy as np
 import torch
 
+from . import _lib as L
 from . import tables as T
 
 STEP_RATIO = 0.05 * 10 * 2.5            # kinetic_model.step_len * n_step * VALID_SPEED[1] (train_HOPE_sac.py:164)
@@ -96,6 +99,13 @@ class BatchedRsPlanner:
         return a, ex
 
 
+def _host_library(device, method):
+    """the library for a host twin: its loops run over CPU tensors only"""
+    if device.type != 'cpu':
+        raise L.HopeError(f'an env without {method} must hold CPU tensors, not {device}')
+    return L.load_library()
+
+
 class DeviceRsPlanner:
     """BatchedRsPlanner's surface over the library's planner (include/hope_env.h "replay of found Reeds-Shepp paths"): the
     state lives in the env's handle (48 B per scene), one k_plan launch per call, no host synchronisation, no cap on the number
@@ -113,10 +123,7 @@ class DeviceRsPlanner:
             self._zero_word = torch.zeros((self.n, 8), dtype=torch.int8, device=self.device)
             self._lens = torch.zeros((self.n, 5), dtype=env.obs_dtype, device=self.device)
         else:
-            import numpy as np
-            from . import _lib as L
-            assert self.device.type == 'cpu', 'an env without planner_step must hold CPU tensors'
-            self._L, self._lib = L, L.load_library()
+            self._lib = _host_library(self.device, 'planner_step')
             self._state = np.zeros((L.PLAN_STATE_WORDS, self.n), np.uint64)
             self._planned = torch.zeros((self.n, 2), dtype=torch.float64)
             self._exec = torch.zeros(self.n, dtype=torch.uint8)
@@ -131,17 +138,14 @@ class DeviceRsPlanner:
         return torch.from_numpy(busy).to(self.device).bool()
 
     def _host_step(self, word, lens, done, flags, step=None):
-        word = word.contiguous()
-        lens = lens.contiguous()
-        assert word.dtype == torch.int8 and word.shape == (self.n, 8) and lens.shape == (self.n, 5)
-        assert lens.dtype in (torch.float32, torch.float64)
-        dp = None
-        if done is not None:
-            done = done.to(torch.uint8).contiguous()
-            dp = done.data_ptr()
-        self._L.check(self._lib.hope_planner_step_host(self.n, self.step_ratio, self._state.ctypes.data, word.data_ptr(), lens.data_ptr(),
-                                                       int(lens.dtype == torch.float64), dp, flags, self._planned.data_ptr(),
-                                                       self._exec.data_ptr(), None, 0), 'hope_planner_step_host')
+        n, arg = self.n, partial(L.tensor_arg, 'hope_planner_step_host', device=self.device)
+        word, lens = word.contiguous(), lens.contiguous()
+        done = None if done is None else done.to(torch.uint8).contiguous()
+        wp, lp = arg('rs_word', word, torch.int8, (n, 8)), arg('rs_lengths', lens, (torch.float32, torch.float64), (n, 5))
+        dp = arg('done', done, torch.uint8, (n,), optional=True)
+        pp, ep = arg('planned', self._planned, torch.float64, (n, 2)), arg('executing', self._exec, torch.uint8, (n,))
+        L.check(self._lib.hope_planner_step_host(n, self.step_ratio, self._state.ctypes, wp, lp, int(lens.dtype == torch.float64), dp, flags,
+                                                 pp, ep, None, 0), 'hope_planner_step_host')
         return self._planned, self._exec.view(torch.bool)
 
     def reset(self, mask=None):
@@ -158,7 +162,7 @@ class DeviceRsPlanner:
         if self.on_device:
             self.env.planner_step(forced=forced, step=0, rs_word=rs_word, rs_lengths=rs_lengths, done=None, pop=False)
         else:
-            self._host_step(rs_word, rs_lengths, None, (self._L.PLAN_FORCED if forced else 0) | self._L.PLAN_NO_POP)
+            self._host_step(rs_word, rs_lengths, None, (L.PLAN_FORCED if forced else 0) | L.PLAN_NO_POP)
 
     def get_actions(self):
         """pop the next planned action of every executing scene -> ([N,2] float64 actions, bool [N] which rows are valid)"""
@@ -174,7 +178,7 @@ class DeviceRsPlanner:
                                          done=True if done is None else done.to(torch.uint8))
         env = self.env
         return self._host_step(env.rs_word if rs_word is None else rs_word, env.rs_lengths if rs_lengths is None else rs_lengths,
-                               env.done if done is None else done, self._L.PLAN_FORCED if forced else 0)
+                               env.done if done is None else done, L.PLAN_FORCED if forced else 0)
 
 
 class DeviceActionChooser:
@@ -193,11 +197,8 @@ class DeviceActionChooser:
         if self.on_device:
             env.enable_chooser()
         else:
-            import numpy as np
-            from . import _lib as L
-            assert self.device.type == 'cpu', 'an env without choose_actions must hold CPU tensors'
-            self._L, self._lib = L, L.load_library()
-            self._acts = np.ascontiguousarray(T.discrete_actions() / [T.VALID_STEER[1], 1.0], dtype=np.float64)
+            self._lib = _host_library(self.device, 'choose_actions')
+            self._acts = L.array_arg('hope_chooser_host', 'actions', T.discrete_actions() / [T.VALID_STEER[1], 1.0], np.float64, (L.N_ACTION, 2))
             self._adt = getattr(env, 'action_dtype', torch.float32)
             self._a32 = torch.zeros((self.n, 2), dtype=torch.float32)
             self._a = self._a32 if self._adt == torch.float32 else torch.zeros((self.n, 2), dtype=torch.float64)
@@ -205,27 +206,28 @@ class DeviceActionChooser:
             self._lp = torch.zeros((self.n, 2), dtype=torch.float32)
 
     def _host(self, mean, log_std, mask, planned, executing, u):
-        assert mean.dtype in (torch.float32, torch.float64) and mean.shape == (self.n, 2)
+        n, arg = self.n, partial(L.tensor_arg, 'hope_chooser_host', device=self.device)
         mean = mean.contiguous()
+        mp = arg('mean', mean, (torch.float32, torch.float64), (n, 2))
         log_std = log_std.to(mean.dtype).contiguous()
-        assert log_std.shape in ((self.n, 2), (1, 2))
+        one_row = n > 1 and tuple(log_std.shape) == (1, 2)
+        sp = arg('log_std', log_std, mean.dtype, (1, 2) if one_row else (n, 2))
         if mask.dtype not in (torch.float32, torch.float64):
             mask = mask.to(torch.float32)
         mask = mask.contiguous()
-        assert mask.shape == (self.n, 42)
-        pp = ep = up = None
-        if planned is not None:
-            planned = planned.to(torch.float64).contiguous()
-            executing = executing.to(torch.uint8).contiguous()
-            pp, ep = planned.data_ptr(), executing.data_ptr()
-        if u is not None:
-            u = u.to(torch.float64).contiguous()
-            up = u.data_ptr()
-        self._L.check(self._lib.hope_chooser_host(self.n, self._acts.ctypes.data, mean.data_ptr(), log_std.data_ptr(),
-                                                  2 if log_std.shape[0] == self.n and self.n > 1 else 0, int(mean.dtype == torch.float64),
-                                                  mask.data_ptr(), int(mask.dtype == torch.float64), pp, ep, up, self.seed, self.counter, 0,
-                                                  self._a.data_ptr(), int(self._adt == torch.float64), self._a32.data_ptr(), self._idx.data_ptr(),
-                                                  self._lp.data_ptr(), None), 'hope_chooser_host')
+        kp = arg('mask', mask, (torch.float32, torch.float64), (n, L.N_ACTION))
+        if (planned is None) != (executing is None):
+            raise L.HopeError('hope_chooser_host: planned and executing go together')
+        planned = None if planned is None else planned.to(torch.float64).contiguous()
+        executing = None if executing is None else executing.to(torch.uint8).contiguous()
+        u = None if u is None else u.to(torch.float64).contiguous()
+        pp, ep = arg('planned', planned, torch.float64, (n, 2), optional=True), arg('executing', executing, torch.uint8, (n,), optional=True)
+        up = arg('u', u, torch.float64, (n,), optional=True)
+        ap, fp = arg('action', self._a, self._adt, (n, 2)), arg('action_f32', self._a32, torch.float32, (n, 2))
+        ip, lp = arg('idx', self._idx, torch.int32, (n,)), arg('log_prob', self._lp, torch.float32, (n, 2))
+        L.check(self._lib.hope_chooser_host(n, self._acts.ctypes, mp, sp, 0 if one_row or n == 1 else 2, int(mean.dtype == torch.float64), kp,
+                                            int(mask.dtype == torch.float64), pp, ep, up, self.seed, self.counter, 0, ap,
+                                            int(self._adt == torch.float64), fp, ip, lp, None), 'hope_chooser_host')
         return self._a, self._a32, self._idx, self._lp
 
     def choose(self, mean, log_std, mask, planned=None, executing=None, u=None):
@@ -280,12 +282,9 @@ class DeviceEvalTracker:
             env.enable_eval_tracker()
             self.alive, self.word, self.done = env.eval_alive, env.eval_word, env.eval_done
         else:
-            import numpy as np
-            from . import _lib as L
-            assert self.device.type == 'cpu', 'an env without eval_track must hold CPU tensors'
-            self._L, self._lib = L, L.load_library()
+            self._lib = _host_library(self.device, 'eval_track')
             self._state = np.zeros((L.EVAL_STATE_WORDS, self.n), np.uint64)
-            self._box = np.array([T.VALID_STEER[0], T.VALID_STEER[1], T.VALID_SPEED[0], T.VALID_SPEED[1]], dtype=np.float64)
+            self._box = L.array_arg('hope_eval_override_host', 'box', T.VALID_STEER + T.VALID_SPEED, np.float64, (4,))
             self.alive = torch.zeros(self.n, dtype=torch.uint8)
             self.word = torch.zeros((self.n, 8), dtype=torch.int8)
             self.done = torch.zeros(self.n, dtype=torch.uint8)
@@ -298,16 +297,17 @@ class DeviceEvalTracker:
 
     def begin(self):
         """a new episode in every scene, from the env's first observation; the step counter restarts"""
-        self.counter = 0
+        env, n = self.env, self.n
+        if self.on_device:
+            env.eval_begin()
+        else:
+            target, pose = self._obs(env.target), env.pose.to(torch.float64).contiguous()
+            tp = L.tensor_arg('hope_eval_begin_host', 'target', target, (torch.float32, torch.float64), (n, 5), self.device)
+            pp = L.tensor_arg('hope_eval_begin_host', 'pose', pose, torch.float64, (n, 3), self.device)
+            L.check(self._lib.hope_eval_begin_host(n, n, self._state.ctypes, tp, int(target.dtype == torch.float64), pp), 'hope_eval_begin_host')
+        self.counter = 0                              # (after the call: a refused begin leaves the object as it was)
         self.alive.fill_(1)
         self.done.zero_()
-        if self.on_device:
-            self.env.eval_begin()
-            return
-        env = self.env
-        target, pose = self._obs(env.target), env.pose.to(torch.float64).contiguous()
-        self._L.check(self._lib.hope_eval_begin_host(self.n, self.n, self._state.ctypes.data, target.data_ptr(),
-                                                     int(target.dtype == torch.float64), pose.data_ptr()), 'hope_eval_begin_host')
 
     def override(self, action, u=None):
         """the stuck detector's random action, in place on `action` ([N, 2] float32 / float64, contiguous); -> `alive`.  Advances the
@@ -315,14 +315,12 @@ class DeviceEvalTracker:
         if self.on_device:
             self.env.eval_override(action, u, self.seed, self.counter)
         else:
-            assert action.shape == (self.n, 2) and action.dtype in (torch.float32, torch.float64) and action.is_contiguous()
-            up = None
-            if u is not None:
-                u = u.to(torch.float64).contiguous()
-                up = u.data_ptr()
-            self._L.check(self._lib.hope_eval_override_host(self.n, self.n, self._state.ctypes.data, self._box.ctypes.data, action.data_ptr(),
-                                                            int(action.dtype == torch.float64), up, self.seed, self.counter, 0,
-                                                            self.alive.data_ptr()), 'hope_eval_override_host')
+            n, arg = self.n, partial(L.tensor_arg, 'hope_eval_override_host', device=self.device)
+            ap = arg('action', action, (torch.float32, torch.float64), (n, 2))
+            u = None if u is None else u.to(torch.float64).contiguous()
+            up, lp = arg('u', u, torch.float64, (n, 2), optional=True), arg('alive', self.alive, torch.uint8, (n,))
+            L.check(self._lib.hope_eval_override_host(n, n, self._state.ctypes, self._box.ctypes, ap, int(action.dtype == torch.float64), up,
+                                                      self.seed, self.counter, 0, lp), 'hope_eval_override_host')
         self.counter += 1
         return self.alive
 
@@ -331,14 +329,16 @@ class DeviceEvalTracker:
         if self.on_device:
             self.env.eval_track()
             return self.word, self.done
-        env = self.env
+        env, n, arg = self.env, self.n, partial(L.tensor_arg, 'hope_eval_track_host', device=self.device)
         target, pose = self._obs(env.target), env.pose.to(torch.float64).contiguous()
         reward = env.reward.to(target.dtype).contiguous()
         status, done, word = env.status.to(torch.int32).contiguous(), env.done.to(torch.uint8).contiguous(), env.rs_word.contiguous()
-        assert word.dtype == torch.int8 and word.shape == (self.n, 8)
-        self._L.check(self._lib.hope_eval_track_host(self.n, self.n, self._state.ctypes.data, target.data_ptr(), int(target.dtype == torch.float64),
-                                                     pose.data_ptr(), reward.data_ptr(), status.data_ptr(), done.data_ptr(), word.data_ptr(),
-                                                     self.word.data_ptr(), self.done.data_ptr()), 'hope_eval_track_host')
+        tp, pp = arg('target', target, (torch.float32, torch.float64), (n, 5)), arg('pose', pose, torch.float64, (n, 3))
+        rp, sp = arg('reward', reward, target.dtype, (n,)), arg('status', status, torch.int32, (n,))
+        dp, wp = arg('done', done, torch.uint8, (n,)), arg('rs_word', word, torch.int8, (n, 8))
+        ow, od = arg('word', self.word, torch.int8, (n, 8)), arg('done_out', self.done, torch.uint8, (n,))
+        L.check(self._lib.hope_eval_track_host(n, n, self._state.ctypes, tp, int(target.dtype == torch.float64), pp, rp, sp, dp, wp, ow, od),
+                'hope_eval_track_host')
         return self.word, self.done
 
     def any_alive(self):
@@ -354,7 +354,6 @@ class DeviceEvalTracker:
         """-> float32 [N, 4]: status, steps, summed reward, path length"""
         if self.on_device:
             return self.env.eval_records()
-        import numpy as np
         st = self._state
         w = st[9]
         with np.errstate(invalid='ignore', over='ignore'):
@@ -467,28 +466,23 @@ class DeviceStateNorm:
     modal = ('lidar', 'target')
 
     def __init__(self, env, from_norm=None):
-        from . import _lib as L
         self.env, self.n, self.fixed = env, env.n, False
         self.device = torch.device(env.device)
         self.on_device = hasattr(env, 'obsnorm')
-        self._L = L
         if self.on_device:
             env.enable_obsnorm()
         else:
-            assert self.device.type == 'cpu', 'an env without obsnorm must hold CPU tensors'
-            self._lib = L.load_library()
+            self._lib = _host_library(self.device, 'obsnorm')
             self._state = L.ObsNormState()
             self._out = None
         if from_norm is not None:
             self.load(from_norm)
         elif self.on_device:                          # a new object starts from nothing, whatever the handle held
-            import numpy as np
             z = np.zeros(L.OBSNORM_COLS)
             env.obsnorm_load(0, z, z, z)
 
     # -- statistics ----------------------------------------------------------------------------------------------------
     def _stats(self):
-        import numpy as np
         if self.on_device:
             return self.env.obsnorm_state()
         s = self._state
@@ -496,7 +490,7 @@ class DeviceStateNorm:
 
     def _split(self, a):
         t = torch.from_numpy(a).to(self.device)
-        nl = self._L.OBSNORM_LIDAR
+        nl = L.OBSNORM_LIDAR
         return {'lidar': t[:nl], 'target': t[nl:]}
 
     @property
@@ -517,16 +511,15 @@ class DeviceStateNorm:
 
     def load(self, norm):
         """take over n_state, mean, S, std and `fixed` of a BatchedStateNorm / DeviceStateNorm"""
-        import numpy as np
-        assert tuple(norm.modal) == self.modal, 'the device normalisation covers lidar and target'
-        mean, S, std = norm.mean, norm.S, norm.std
-        a = [np.concatenate([d[k].detach().double().cpu().numpy().reshape(-1) for k in self.modal]) for d in (mean, S, std)]
+        if tuple(norm.modal) != self.modal:
+            raise ValueError('the device normalisation covers lidar and target')
+        a = {name: L.array_arg('hope_obsnorm_host', name, np.concatenate([d[k].detach().double().cpu().numpy().reshape(-1) for k in self.modal]),
+                               np.float64, (L.OBSNORM_COLS,)) for name, d in (('mean', norm.mean), ('S', norm.S), ('std', norm.std))}
         if self.on_device:
-            self.env.obsnorm_load(int(norm.n_state), *a)
+            self.env.obsnorm_load(int(norm.n_state), *a.values())
         else:
             self._state.n_state = int(norm.n_state)
-            for name, v in zip(('mean', 'S', 'std'), a):
-                assert v.shape == (self._L.OBSNORM_COLS,)
+            for name, v in a.items():
                 getattr(self._state, name)[:] = v.tolist()
         self.fixed = bool(norm.fixed)
         return self
@@ -535,7 +528,7 @@ class DeviceStateNorm:
         """-> a BatchedStateNorm with these statistics (bit for bit)"""
         n, mean, S, std = self._stats()
         out = BatchedStateNorm(device=self.device if device is None else device)
-        nl = self._L.OBSNORM_LIDAR
+        nl = L.OBSNORM_LIDAR
         for name, a in (('mean', mean), ('S', S), ('std', std)):
             t = torch.from_numpy(a).to(out.mean['lidar'].device)
             setattr(out, name, {'lidar': t[:nl].clone(), 'target': t[nl:].clone()})
@@ -562,17 +555,18 @@ class DeviceStateNorm:
         lidar, target = self._pair(obs)
         if self.on_device:
             return self.env.obsnorm(lidar, target, update, normalize)
-        L = self._L
+        arg = partial(L.tensor_arg, 'hope_obsnorm_host', device=self.device)
+        lp = arg('lidar', lidar, (torch.float32, torch.float64), (None, L.OBSNORM_LIDAR))
         rows = lidar.shape[0]
-        assert lidar.shape == (rows, L.OBSNORM_LIDAR) and target.shape == (rows, L.OBSNORM_TARGET)
+        tp = arg('target', target, lidar.dtype, (rows, L.OBSNORM_TARGET))
         ol = ot = None
         if normalize:
             if self._out is None or self._out[0].shape[0] < rows:
                 self._out = (torch.zeros((max(rows, self.n), L.OBSNORM_LIDAR)), torch.zeros((max(rows, self.n), L.OBSNORM_TARGET)))
-            ol, ot = self._out[0].data_ptr(), self._out[1].data_ptr()
+            ol = arg('out_lidar', self._out[0], torch.float32, (self._out[0].shape[0], L.OBSNORM_LIDAR))
+            ot = arg('out_target', self._out[1], torch.float32, (self._out[0].shape[0], L.OBSNORM_TARGET))
         flags = (L.OBSNORM_UPDATE if update else 0) | (L.OBSNORM_NORMALIZE if normalize else 0)
-        L.check(self._lib.hope_obsnorm_host(self._state, lidar.data_ptr(), target.data_ptr(), rows, int(lidar.dtype == torch.float64), flags,
-                                            ol, ot), 'hope_obsnorm_host')
+        L.check(self._lib.hope_obsnorm_host(self._state, lp, tp, rows, int(lidar.dtype == torch.float64), flags, ol, ot), 'hope_obsnorm_host')
         return (self._out[0][:rows], self._out[1][:rows]) if normalize else (None, None)
 
     def update(self, obs):
@@ -644,16 +638,14 @@ class DeviceGae:
     `sums`: the float64 [3] tensor of the last call that reduced them (after the all-reduce, if there was one)."""
 
     def __init__(self, env):
-        from . import _lib as L
-        self.env, self._L = env, L
+        self.env = env
         self.device = torch.device(env.device)
         self.on_device = hasattr(env, 'gae')
         self.sums = None
         if self.on_device:
             env.enable_gae()
         else:
-            assert self.device.type == 'cpu', 'an env without gae must hold CPU tensors'
-            self._lib = L.load_library()
+            self._lib = _host_library(self.device, 'gae')
 
     @staticmethod
     def _world():
@@ -663,27 +655,30 @@ class DeviceGae:
     def mean_std(self, sums=None):
         """the float32 (mean, std) the normalisation takes from `sums` (default: the last call's), as Python floats; downloads the
         three doubles (host-synchronous)"""
-        import ctypes as C
-        L = self._L
         s = (self.sums if sums is None else sums).detach().to('cpu', torch.float64).contiguous()
-        ms = (C.c_float * 2)()
-        L.check(L.load_library().hope_adv_normalize_host(None, 0, s.data_ptr(), None, ms), 'hope_adv_normalize_host')
+        ms = np.zeros(2, np.float32)
+        sp = L.tensor_arg('hope_adv_normalize_host', 'sums', s, torch.float64, (3,), s.device)
+        L.check(L.load_library().hope_adv_normalize_host(None, 0, sp, None, ms.ctypes), 'hope_adv_normalize_host')
         return float(ms[0]), float(ms[1])
 
     def _host(self, x, gamma, lam, flags):
-        L = self._L
-        rows, t = x[0].shape
+        arg = partial(L.tensor_arg, 'hope_gae_host', dtype=torch.float32, device=self.device)
+        reward, done, value, v_last, value_target = x
+        rp = arg('reward', reward, shape=(None, None))
+        rows, t = reward.shape
         adv, v_target = torch.empty((rows, t), dtype=torch.float32), torch.empty((rows, t), dtype=torch.float32)
         sums = torch.zeros(3, dtype=torch.float64)
-        L.check(self._lib.hope_gae_host(*(a.data_ptr() for a in x), rows, t, float(gamma), float(lam), flags, adv.data_ptr(), v_target.data_ptr(),
-                                        sums.data_ptr(), None), 'hope_gae_host')
+        ptrs = [rp, arg('done', done, shape=(rows, t)), arg('value', value, shape=(rows, t)), arg('v_last', v_last, shape=(rows,)),
+                arg('value_target', value_target, shape=(rows, t))]
+        out = [arg('adv', adv, shape=(rows, t)), arg('v_target', v_target, shape=(rows, t)),
+               L.tensor_arg('hope_gae_host', 'sums', sums, torch.float64, (3,), self.device)]
+        L.check(self._lib.hope_gae_host(*ptrs, rows, t, float(gamma), float(lam), flags, *out, None), 'hope_gae_host')
         return adv, v_target, sums
 
     def __call__(self, reward, done, value, v_last, value_target, gamma, lam, normalize=True):
         """reward / done / value / value_target [N, T], v_last [N] -> (adv [N, T], v_target [N, T]), float32.  normalize=False
         (adv_norm=False): the scan alone, adv is the plain estimate."""
         import torch.distributed as dist
-        L = self._L
         x = [a.detach().to(torch.float32).contiguous() for a in (reward, done, value, v_last, value_target)]
         split = normalize and self._world() > 1
         if self.on_device:
@@ -695,7 +690,9 @@ class DeviceGae:
             adv, v_target, sums = self._host(x, gamma, lam, 0 if not normalize else (L.GAE_SUMS if split else L.GAE_NORMALIZE))
             if split:
                 dist.all_reduce(sums)
-                L.check(self._lib.hope_adv_normalize_host(adv.data_ptr(), adv.numel(), sums.data_ptr(), adv.data_ptr(), None), 'hope_adv_normalize_host')
+                ap = L.tensor_arg('hope_adv_normalize_host', 'adv', adv, torch.float32, tuple(adv.shape), self.device)
+                sp = L.tensor_arg('hope_adv_normalize_host', 'sums', sums, torch.float64, (3,), self.device)
+                L.check(self._lib.hope_adv_normalize_host(ap, adv.numel(), sp, ap, None), 'hope_adv_normalize_host')
         if normalize:
             self.sums = sums
         return adv, v_target

@@ -4,6 +4,7 @@ Tensor-in / tensor-out counterpart of `CarParkingWrapper.step` (src/env/env_wrap
 PyTorch is used for device memory and streams only; all arithmetic is in the HIP kernels.
 """
 import ctypes as C
+from functools import partial
 
 import numpy as np
 import torch
@@ -27,7 +28,8 @@ class ParkingBatch:
         if self.device.index is None:              # 'cuda' -> the current device, so that tensor.device == self.device
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.n, self.max_obst = int(n_scenes), int(max_obstacles)
-        assert obs_dtype in (torch.float32, torch.float64) and action_dtype in (torch.float32, torch.float64)
+        if obs_dtype not in (torch.float32, torch.float64) or action_dtype not in (torch.float32, torch.float64):
+            raise L.HopeError(f'ParkingBatch: obs_dtype and action_dtype must be torch.float32 or torch.float64, got {obs_dtype} and {action_dtype}')
         self.obs_dtype, self.action_dtype = obs_dtype, action_dtype
         if overlap is None:
             overlap = True
@@ -42,10 +44,9 @@ class ParkingBatch:
         self.arch = self.lib.hope_env_device_arch(self.h).decode()
         t = T.all_tables() if tables is None else tables
         self.tables = t
-        ds, hb, ab = (np.ascontiguousarray(t[k], dtype=np.float64) for k in ('dist_star', 'hull_base', 'beam_ab'))
-        assert ds.shape == (1200, 42, 10) and hb.shape == (120,) and ab.shape == (120, 2)
-        L.check(self.lib.hope_env_upload_tables(self.h, ds.ctypes.data, hb.ctypes.data, ab.ctypes.data),
-                'hope_env_upload_tables')
+        ds, hb, ab = (L.array_arg('hope_env_upload_tables', k, t[k], np.float64, shape)
+                      for k, shape in (('dist_star', (1200, 42, 10)), ('hull_base', (120,)), ('beam_ab', (120, 2))))
+        L.check(self.lib.hope_env_upload_tables(self.h, ds.ctypes, hb.ctypes, ab.ctypes), 'hope_env_upload_tables')
         n, dev, od = self.n, self.device, obs_dtype
         # every output lives in ONE device arena (typed views at 256-byte aligned offsets): `download_outputs()` brings all of a
         # step's results to the host with a single copy -- what the N = 1 look-alike classes (hope_amd/env.py) need per step
@@ -74,44 +75,51 @@ class ParkingBatch:
                               self.reward.data_ptr(), self.reward_info.data_ptr(), self.status.data_ptr(),
                               self.done.data_ptr(), self.pose.data_ptr(), self.rs_word.data_ptr(),
                               self.rs_lengths.data_ptr(), self.img.data_ptr() if image else None)
+        # what the enable_* methods allocate on first use (None: that part is off, and its calls say so) and what the pool setters record
+        self.planned = self._plan_exec = self.plan_executing = None
+        self.chosen_action = self.chosen_action_f32 = self.chosen_idx = self.chosen_log_prob = self.chosen_probs = None
+        self.norm_lidar = self.norm_target = self.gae_sums = self._gae_out = None
+        self.eval_alive = self.eval_word = self.eval_done = self._eval_rec = None
+        self.pool_size = self.n_dlp_cases = None
+        self._refresher_filling = False
 
     # -- scenes ------------------------------------------------------------------------------------
     def set_scenes(self, ids, scenes):
         """map.reset + vehicle.reset for the listed scene slots (host -> device; synchronous)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
         start, dest, bbox, verts, nob, _nv = pack_scenes(scenes, self.max_obst)
         self.set_scene_arrays(ids, start, dest, bbox, verts, nob)
 
     def set_draw_class(self, ids, cls):
         """size class of scene slots (0: lots of <= 32 obstacles, 1: larger lots / Dragon-Lake cases): which launch chain steps a
         slot and which pool entries it draws at turnover; set_scenes derives it from the obstacle count of the uploaded map"""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        c = np.ascontiguousarray(np.broadcast_to(np.asarray(cls, dtype=np.uint8), ids.shape))
+        ids = L.array_arg('hope_env_set_draw_class', 'ids', ids, np.int32, (None,))
+        c = L.array_arg('hope_env_set_draw_class', 'cls', np.broadcast_to(np.asarray(cls, dtype=np.uint8), ids.shape), np.uint8, ids.shape)
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_set_draw_class(self.h, ids.ctypes.data, len(ids), c.ctypes.data), 'hope_env_set_draw_class')
+        L.check(self.lib.hope_env_set_draw_class(self.h, ids.ctypes, len(ids), c.ctypes), 'hope_env_set_draw_class')
         return self
 
     def set_scene_arrays(self, ids, start, dest, bbox, verts, n_obst):
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (start, dest, bbox, verts)]
-        nob = np.ascontiguousarray(n_obst, dtype=np.int32)
-        assert a[3].shape == (len(ids), self.max_obst, 4, 2)
+        ids = L.array_arg('hope_env_set_scenes', 'ids', ids, np.int32, (None,))
+        a = self._scene_arrays('hope_env_set_scenes', len(ids), start, dest, bbox, verts, n_obst)
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_set_scenes(self.h, ids.ctypes.data, len(ids), a[0].ctypes.data, a[1].ctypes.data,
-                                             a[2].ctypes.data, a[3].ctypes.data, nob.ctypes.data),
-                'hope_env_set_scenes')
+        L.check(self.lib.hope_env_set_scenes(self.h, ids.ctypes, len(ids), *[x.ctypes for x in a]), 'hope_env_set_scenes')
+
+    def _scene_arrays(self, call, n, start, dest, bbox, verts, n_obst):
+        """n maps in the library's layout: start [n, 3], dest [n, 3], bbox [n, 4], verts [n, max_obst, 4, 2] float64, n_obst [n] int32"""
+        return [L.array_arg(call, 'start', start, np.float64, (n, 3)), L.array_arg(call, 'dest', dest, np.float64, (n, 3)),
+                L.array_arg(call, 'bbox', bbox, np.float64, (n, 4)), L.array_arg(call, 'verts', verts, np.float64, (n, self.max_obst, 4, 2)),
+                L.array_arg(call, 'n_obst', n_obst, np.int32, (n,))]
 
     def set_pool(self, scenes):
         """upload a pool of complete scenes (list[Scene] or the tuple pack_scenes returns) that redraw() draws from"""
         start, dest, bbox, verts, nob, _nv = pack_scenes(scenes, self.max_obst) if isinstance(scenes, list) else scenes
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (start, dest, bbox, verts)]
-        nob = np.ascontiguousarray(nob, dtype=np.int32)
-        if getattr(self, '_refresher_filling', False):
+        nob = L.array_arg('hope_env_set_pool', 'n_obst', nob, np.int32, (None,))
+        a = self._scene_arrays('hope_env_set_pool', len(nob), start, dest, bbox, verts, nob)
+        if self._refresher_filling:
             raise L.HopeError('set_pool while a PoolRefresher fill is running: the pinned staging arrays are being written by its '
                               'thread (close() / poll(wait=True) the refresher first)')
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_set_pool(self.h, len(nob), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data,
-                                           a[3].ctypes.data, nob.ctypes.data), 'hope_env_set_pool')
+        L.check(self.lib.hope_env_set_pool(self.h, len(nob), *[x.ctypes for x in a]), 'hope_env_set_pool')
         self.pool_size = len(nob)
 
     def pool_staging(self, n_pool):
@@ -156,7 +164,7 @@ class ParkingBatch:
         No host thread, staging or upload; asynchronous."""
         from .scene_gen import pool_level_counts
         counts = (C.c_int32 * 3)(*pool_level_counts(n_pool, levels))
-        L.check(self.lib.hope_env_generate_pool(self.h, int(n_pool), counts, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+        L.check(self.lib.hope_env_generate_pool(self.h, int(n_pool), counts, L.seed64(seed),
                                                 C.c_int64(int(batch) * int(n_pool)), 1 if relaxed else 0), 'hope_env_generate_pool')
         self.pool_size = int(n_pool)
         return self
@@ -178,15 +186,14 @@ class ParkingBatch:
 
     def set_pool_buckets(self, buckets):
         """level (0 Normal, 1 Complex, 2 Extrem; 255 unlabelled) of every entry of the resident pool (generate_pool labels its own)"""
-        b = np.ascontiguousarray(buckets, dtype=np.uint8)
+        b = L.array_arg('hope_env_set_pool_buckets', 'buckets', buckets, np.uint8, (None,))
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_set_pool_buckets(self.h, len(b), b.ctypes.data), 'hope_env_set_pool_buckets')
+        L.check(self.lib.hope_env_set_pool_buckets(self.h, len(b), b.ctypes), 'hope_env_set_pool_buckets')
         return self
 
     def curriculum_tally(self):
         """count the episodes the last step finished (its own status / done buffers), asynchronously on the current stream"""
-        L.check(self.lib.hope_env_curriculum_tally(self.h, C.c_void_p(self.status.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                                   self._stream()), 'hope_env_curriculum_tally')
+        L.check(self.lib.hope_env_curriculum_tally(self.h, self._out.status, self._out.done, self._stream()), 'hope_env_curriculum_tally')
         return self
 
     def curriculum_update(self):
@@ -199,25 +206,26 @@ class ParkingBatch:
         'updates', 'unlabelled_episodes', 'unlabelled_successes', 'on'} -- host-synchronous"""
         nb = C.c_int32(0)
         misc = np.zeros(4, np.uint64)
-        L.check(self.lib.hope_env_curriculum_state(self.h, C.byref(nb), None, None, None, None, None, None, misc.ctypes.data), 'hope_env_curriculum_state')
+        L.check(self.lib.hope_env_curriculum_state(self.h, C.byref(nb), None, None, None, None, None, None, misc.ctypes), 'hope_env_curriculum_state')
         out = {'on': bool(misc[3]), 'updates': int(misc[0]), 'n_buckets': int(nb.value)}
         if not out['on']:
             return out
         n = nb.value
         e, s = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         wn, ws, prob, pw = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(4)
-        L.check(self.lib.hope_env_curriculum_state(self.h, None, e.ctypes.data, s.ctypes.data, wn.ctypes.data, ws.ctypes.data, prob.ctypes.data,
-                                                   pw.ctypes.data, misc.ctypes.data), 'hope_env_curriculum_state')
+        L.check(self.lib.hope_env_curriculum_state(self.h, None, e.ctypes, s.ctypes, wn.ctypes, ws.ctypes, prob.ctypes, pw.ctypes, misc.ctypes),
+                'hope_env_curriculum_state')
         out.update(episodes=e, successes=s, win_n=wn, win_s=ws, prob=prob, q=prob[:4].copy(), pw=pw, updates=int(misc[0]),
                    unlabelled_episodes=int(misc[1]), unlabelled_successes=int(misc[2]))
         return out
 
     def curriculum_set_windows(self, win_n, win_s, episodes, successes):
         """set the windows and cumulative counters by hand (checkpoint restore, tests) and rebuild the lists from them"""
-        a = [np.ascontiguousarray(win_n, dtype=np.float64), np.ascontiguousarray(win_s, dtype=np.float64),
-             np.ascontiguousarray(episodes, dtype=np.uint64), np.ascontiguousarray(successes, dtype=np.uint64)]
+        arg = partial(L.array_arg, 'hope_env_curriculum_set_windows')
+        wn = arg('win_n', win_n, np.float64, (None,))                   # (the library compares the count with its number of buckets)
+        a = [wn, arg('win_s', win_s, np.float64, wn.shape), arg('episodes', episodes, np.uint64, wn.shape), arg('successes', successes, np.uint64, wn.shape)]
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_curriculum_set_windows(self.h, len(a[0]), *[x.ctypes.data for x in a]), 'hope_env_curriculum_set_windows')
+        L.check(self.lib.hope_env_curriculum_set_windows(self.h, len(wn), *[x.ctypes for x in a]), 'hope_env_curriculum_set_windows')
         return self
 
     def curriculum_lists(self):
@@ -226,7 +234,7 @@ class ParkingBatch:
         L.check(self.lib.hope_env_curriculum_state(self.h, C.byref(nb), None, None, None, None, None, None, None), 'hope_env_curriculum_state')
         l0, l1 = np.full(L.CURRICULUM_LIST_LEN, -1, np.int32), np.full(L.CURRICULUM_LIST_LEN, -1, np.int32)
         pos = np.zeros((2, nb.value), np.int32)
-        L.check(self.lib.hope_env_curriculum_download_lists(self.h, l0.ctypes.data, l1.ctypes.data, pos.ctypes.data), 'hope_env_curriculum_download_lists')
+        L.check(self.lib.hope_env_curriculum_download_lists(self.h, l0.ctypes, l1.ctypes, pos.ctypes), 'hope_env_curriculum_download_lists')
         return l0, l1, pos
 
     def set_dlp_cases(self, pool=None):
@@ -238,59 +246,58 @@ class ParkingBatch:
             return self
         from .scenes import DlpScenePool
         pool = pool or DlpScenePool()
-        dest = np.ascontiguousarray(pool.dest, dtype=np.float64)
-        cand_off = np.ascontiguousarray(pool.start_off, dtype=np.int32)
-        cand = np.ascontiguousarray(pool.starts, dtype=np.float64)
-        case_set = np.ascontiguousarray(pool.case_set, dtype=np.int32)
-        set_off = np.ascontiguousarray(pool.set_off, dtype=np.int32)
+        arg = partial(L.array_arg, 'hope_env_set_dlp_cases')
+        dest = arg('dest', pool.dest, np.float64, (None, 3))
+        cand_off = arg('start_off', pool.start_off, np.int32, (len(dest) + 1,))
+        cand = arg('starts', pool.starts, np.float64, (None, 3))
+        case_set = arg('case_set', pool.case_set, np.int32, (len(dest),))
+        set_off = arg('set_off', pool.set_off, np.int32, (None,))
         sv = np.array(pool.set_verts, dtype=np.float64)          # [total][4][2]; triangles repeat their last vertex
         tri = np.asarray(pool.set_nvert) == 3
         sv[tri, 3] = sv[tri, 2]
-        sv = np.ascontiguousarray(sv)
+        sv = arg('set_verts', sv, np.float64, (None, 4, 2))
         torch.cuda.synchronize(self.device)
-        L.check(self.lib.hope_env_set_dlp_cases(self.h, len(dest), dest.ctypes.data, cand_off.ctypes.data, cand.ctypes.data,
-                                                case_set.ctypes.data, len(set_off) - 1, set_off.ctypes.data, sv.ctypes.data),
-                'hope_env_set_dlp_cases')
+        L.check(self.lib.hope_env_set_dlp_cases(self.h, len(dest), dest.ctypes, cand_off.ctypes, cand.ctypes, case_set.ctypes,
+                                                len(set_off) - 1, set_off.ctypes, sv.ctypes), 'hope_env_set_dlp_cases')
         self.n_dlp_cases = len(dest)
         return self
 
     def pool_overflow(self):
         out = np.zeros(1, np.int32)
-        L.check(self.lib.hope_env_pool_overflow(self.h, out.ctypes.data), 'hope_env_pool_overflow')
+        L.check(self.lib.hope_env_pool_overflow(self.h, out.ctypes), 'hope_env_pool_overflow')
         return int(out[0])
 
     def download_scenes(self, ids):
         """the maps the listed scene slots hold now -> (start, dest, bbox, verts, n_obst) (host arrays)"""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        ids = L.array_arg('hope_env_download_scenes', 'ids', ids, np.int32, (None,))
         n = len(ids)
         start, dest, bbox = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
         verts, nob = np.zeros((n, self.max_obst, 4, 2)), np.zeros(n, np.int32)
-        L.check(self.lib.hope_env_download_scenes(self.h, ids.ctypes.data, n, start.ctypes.data, dest.ctypes.data, bbox.ctypes.data,
-                                                  verts.ctypes.data, nob.ctypes.data), 'hope_env_download_scenes')
+        L.check(self.lib.hope_env_download_scenes(self.h, ids.ctypes, n, start.ctypes, dest.ctypes, bbox.ctypes, verts.ctypes, nob.ctypes),
+                'hope_env_download_scenes')
         return start, dest, bbox, verts, nob
 
     def pool_state(self):
         """(pool index, episode counter) of every scene: with download_state() and pool_generation() the whole snapshot of a
         run that draws maps from a pool that is NOT replaced in the meantime (refreshed runs: download_scenes / set_scene_arrays)"""
         idx, ep = np.zeros(self.n, np.int32), np.zeros(self.n, np.uint32)
-        L.check(self.lib.hope_env_download_pool_state(self.h, idx.ctypes.data, ep.ctypes.data), 'hope_env_download_pool_state')
+        L.check(self.lib.hope_env_download_pool_state(self.h, idx.ctypes, ep.ctypes), 'hope_env_download_pool_state')
         return idx, ep
 
     def restore_maps(self, pool_index, episode, seed, generation=0):
         """repeat the draws of a snapshot (the seed in use then); `generation` = pool_generation() saved with the snapshot: the
         call fails (HOPE_ESTATE) if the pool has been replaced since -- the draws would return other maps; 0 skips the check.
         Follow with upload_state()"""
-        drawn = np.ascontiguousarray(np.asarray(pool_index) != -1, dtype=np.uint8)
-        ep = np.ascontiguousarray(episode, dtype=np.uint32)
-        L.check(self.lib.hope_env_restore_maps(self.h, drawn.ctypes.data, ep.ctypes.data, C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                               C.c_uint64(int(generation))), 'hope_env_restore_maps')
+        drawn = L.array_arg('hope_env_restore_maps', 'pool_index', np.asarray(pool_index) != -1, np.uint8, (self.n,))
+        ep = L.array_arg('hope_env_restore_maps', 'episode', episode, np.uint32, (self.n,))
+        L.check(self.lib.hope_env_restore_maps(self.h, drawn.ctypes, ep.ctypes, L.seed64(seed), C.c_uint64(int(generation))),
+                'hope_env_restore_maps')
         return self
 
     def redraw(self, mask, seed=0):
         """map.reset for the flagged scenes: each takes a pool scene of its tile class and restarts (asynchronous)"""
-        assert mask.dtype == torch.uint8 and mask.shape == (self.n,) and mask.device == self.device
-        L.check(self.lib.hope_env_redraw(self.h, C.c_void_p(mask.data_ptr()), C.c_uint64(int(seed) & (2 ** 64 - 1)), self._stream()),
-                'hope_env_redraw')
+        mp = L.tensor_arg('hope_env_redraw', 'mask', mask, torch.uint8, (self.n,), self.device)
+        L.check(self.lib.hope_env_redraw(self.h, mp, L.seed64(seed), self._stream()), 'hope_env_redraw')
         return self
 
     def turnover(self, seed=0):
@@ -300,13 +307,13 @@ class ParkingBatch:
         self._done_mask.copy_(self.done)
         self.redraw(self._done_mask, seed)
         stages = L.STAGE_ALL | (L.STAGE_IMG if self.image else 0)
-        L.check(self.lib.hope_env_reset_obs(self.h, C.c_void_p(self._done_mask.data_ptr()), stages, C.byref(self._out_obs),
-                                            self._stream()), 'hope_env_reset_obs')
+        mp = L.tensor_arg('hope_env_reset_obs', 'done mask', self._done_mask, torch.uint8, (self.n,), self.device)
+        L.check(self.lib.hope_env_reset_obs(self.h, mp, stages, C.byref(self._out_obs), self._stream()), 'hope_env_reset_obs')
         return self
 
     def pool_index(self):
         out = np.zeros(self.n, np.int32)
-        L.check(self.lib.hope_env_download_pool_index(self.h, out.ctypes.data), 'hope_env_download_pool_index')
+        L.check(self.lib.hope_env_download_pool_index(self.h, out.ctypes), 'hope_env_download_pool_index')
         return out
 
     # -- the hot path ------------------------------------------------------------------------------
@@ -317,14 +324,13 @@ class ParkingBatch:
         """the action-less step of CarParking.reset (car_parking_base.py:138)."""
         if self.image and (stages & L.STAGE_ALL) == L.STAGE_ALL:
             stages |= L.STAGE_IMG
-        ap = C.c_void_p(active.data_ptr()) if active is not None else None
-        L.check(self.lib.hope_env_reset_obs(self.h, ap, stages, C.byref(self._out), self._stream()),
-                'hope_env_reset_obs')
+        ap = L.tensor_arg('hope_env_reset_obs', 'active', active, (torch.uint8, torch.bool), (self.n,), self.device, optional=True)
+        L.check(self.lib.hope_env_reset_obs(self.h, ap, stages, C.byref(self._out), self._stream()), 'hope_env_reset_obs')
         return self
 
     def set_redraw_seed(self, seed):
         """seed of the draws of step(..., auto_reset=True, fresh=True)"""
-        L.check(self.lib.hope_env_set_redraw_seed(self.h, C.c_uint64(int(seed) & (2 ** 64 - 1))), 'hope_env_set_redraw_seed')
+        L.check(self.lib.hope_env_set_redraw_seed(self.h, L.seed64(seed)), 'hope_env_set_redraw_seed')
         return self
 
     def step(self, actions, active=None, stages=L.STAGE_ALL, auto_reset=False, fresh=False, defer_rs=False):
@@ -341,11 +347,9 @@ class ParkingBatch:
         if auto_reset:
             stages |= L.AUTO_RESET | (L.AUTO_REDRAW if fresh else 0)
         stages |= self._action_bits
-        assert actions.shape == (self.n, 2) and actions.dtype == self.action_dtype and actions.is_contiguous()
-        assert actions.device == self.device
-        ap = C.c_void_p(active.data_ptr()) if active is not None else None
-        L.check(self.lib.hope_env_step(self.h, C.c_void_p(actions.data_ptr()), ap, stages, C.byref(self._out),
-                                       self._stream()), 'hope_env_step')
+        xp = L.tensor_arg('hope_env_step', 'actions', actions, self.action_dtype, (self.n, 2), self.device)
+        ap = L.tensor_arg('hope_env_step', 'active', active, (torch.uint8, torch.bool), (self.n,), self.device, optional=True)
+        L.check(self.lib.hope_env_step(self.h, xp, ap, stages, C.byref(self._out), self._stream()), 'hope_env_step')
         return self
 
     def last_step(self):
@@ -369,7 +373,7 @@ class ParkingBatch:
         """RsPlanner / ParkingAgent's path replay as device state of the handle (48 B per scene, every scene idle).  Off by default."""
         torch.cuda.synchronize(self.device)
         L.check(self.lib.hope_env_planner_enable(self.h, float(step_ratio)), 'hope_env_planner_enable')
-        if getattr(self, 'planned', None) is None:
+        if self.planned is None:
             self.planned = torch.zeros((self.n, 2), dtype=torch.float64, device=self.device)
             self._plan_exec = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
             self.plan_executing = self._plan_exec.view(torch.bool)
@@ -382,10 +386,8 @@ class ParkingBatch:
 
     def planner_reset(self, mask=None):
         """clear the path of the scenes flagged in mask (u8 [N]), or of all (asynchronous on the current stream)"""
-        if mask is not None:
-            assert mask.dtype == torch.uint8 and mask.shape == (self.n,) and mask.device == self.device and mask.is_contiguous()
-        L.check(self.lib.hope_env_planner_reset(self.h, C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()),
-                'hope_env_planner_reset')
+        mp = L.tensor_arg('hope_env_planner_reset', 'mask', mask, torch.uint8, (self.n,), self.device, optional=True)
+        L.check(self.lib.hope_env_planner_reset(self.h, mp, self._stream()), 'hope_env_planner_reset')
         return self
 
     def planner_step(self, forced=False, step=None, actions=None, rs_word=None, rs_lengths=None, done=True, pop=True):
@@ -398,34 +400,24 @@ class ParkingBatch:
         pop=False: bookkeeping only."""
         if step is None:
             L.check(self.lib.hope_env_wait_rs(self.h, self._stream()), 'hope_env_wait_rs')
-        word = self.rs_word if rs_word is None else rs_word
-        lens = self.rs_lengths if rs_lengths is None else rs_lengths
-        dn = self.done if done is True else done
-        assert word.dtype == torch.int8 and word.shape == (self.n, 8) and word.device == self.device and word.is_contiguous()
-        assert lens.dtype == self.obs_dtype and lens.shape == (self.n, 5) and lens.device == self.device and lens.is_contiguous()
-        if dn is not None:
-            assert dn.dtype == torch.uint8 and dn.shape == (self.n,) and dn.device == self.device and dn.is_contiguous()
-        af64 = 0
-        if actions is not None:
-            assert actions.shape == (self.n, 2) and actions.dtype in (torch.float32, torch.float64) and actions.is_contiguous()
-            assert actions.device == self.device
-            af64 = int(actions.dtype == torch.float64)
+        n, arg = self.n, partial(L.tensor_arg, 'hope_env_planner_step', device=self.device)
+        wp = arg('rs_word', self.rs_word if rs_word is None else rs_word, torch.int8, (n, 8))
+        lp = arg('rs_lengths', self.rs_lengths if rs_lengths is None else rs_lengths, self.obs_dtype, (n, 5))
+        dp = arg('done', self.done if done is True else done, torch.uint8, (n,), optional=True)
+        ap = arg('actions', actions, (torch.float32, torch.float64), (n, 2), optional=True)
+        af64 = int(actions is not None and actions.dtype == torch.float64)
         flags = (L.PLAN_FORCED if forced else 0) | (0 if pop else L.PLAN_NO_POP)
-        if getattr(self, 'planned', None) is None:       # (the library then reports that the planner is off)
-            pp = ep = None
-        else:
-            pp, ep = C.c_void_p(self.planned.data_ptr()), C.c_void_p(self._plan_exec.data_ptr())
-        L.check(self.lib.hope_env_planner_step(self.h, C.c_void_p(word.data_ptr()), C.c_void_p(lens.data_ptr()),
-                                               C.c_void_p(dn.data_ptr()) if dn is not None else None, flags, C.c_uint64(int(step or 0)),
-                                               pp, ep, C.c_void_p(actions.data_ptr()) if actions is not None else None, af64,
-                                               self._stream()), 'hope_env_planner_step')
+        pp = arg('planned', self.planned, torch.float64, (n, 2), optional=True)    # (None: the library reports that the planner is off)
+        ep = arg('executing', self._plan_exec, torch.uint8, (n,), optional=True)
+        L.check(self.lib.hope_env_planner_step(self.h, wp, lp, dp, flags, C.c_uint64(int(step or 0)), pp, ep, ap, af64, self._stream()),
+                'hope_env_planner_step')
         return self.planned, self.plan_executing
 
     def planner_state(self):
         """the planner's state block (numpy uint64 [6, N]: the five segment lengths in steps as float64 bits, the packed cursor
         word) -- host-synchronous; tests"""
         out = np.zeros((L.PLAN_STATE_WORDS, self.n), np.uint64)
-        L.check(self.lib.hope_env_planner_download_state(self.h, out.ctypes.data), 'hope_env_planner_download_state')
+        L.check(self.lib.hope_env_planner_download_state(self.h, out.ctypes), 'hope_env_planner_download_state')
         return out
 
     # -- masked choice of the discrete action on the device (hope_env.h; rule: csrc/hope_chooser_core.h) -----------------
@@ -433,16 +425,16 @@ class ParkingBatch:
         """ActionMask.choose_action + the agent's cast / clamp / planner override / log-probability as one kernel (k_choose).
         Uploads the 42 x 2 action table in the policy's scaling (numpy's own bits).  Off by default."""
         torch.cuda.synchronize(self.device)
-        acts = np.ascontiguousarray(T.discrete_actions() / [T.VALID_STEER[1], 1.0], dtype=np.float64)
-        L.check(self.lib.hope_env_chooser_enable(self.h, acts.ctypes.data), 'hope_env_chooser_enable')
-        if getattr(self, 'chosen_action', None) is None:
+        acts = L.array_arg('hope_env_chooser_enable', 'actions', T.discrete_actions() / [T.VALID_STEER[1], 1.0], np.float64, (L.N_ACTION, 2))
+        L.check(self.lib.hope_env_chooser_enable(self.h, acts.ctypes), 'hope_env_chooser_enable')
+        if self.chosen_action is None:
             dev = self.device
             self.chosen_action_f32 = torch.zeros((self.n, 2), dtype=torch.float32, device=dev)
             # a float32 env steps with the very tensor the transition ring stores
             self.chosen_action = self.chosen_action_f32 if self.action_dtype == torch.float32 else torch.zeros((self.n, 2), dtype=torch.float64, device=dev)
             self.chosen_idx = torch.zeros(self.n, dtype=torch.int32, device=dev)
             self.chosen_log_prob = torch.zeros((self.n, 2), dtype=torch.float32, device=dev)
-            self.chosen_probs = None                      # [N, 42] float64, allocated by the first call that asks for it
+            # (chosen_probs, [N, 42] float64, is allocated by the first call that asks for it)
         return self
 
     def disable_chooser(self):
@@ -459,32 +451,25 @@ class ParkingBatch:
         CHOOSE_NOMASK / CHOOSE_FIXED on a degenerate row; log_prob f32 [N, 2][; probs f64 [N, 42]]): persistent tensors of this
         object, overwritten by the next call."""
         n, dev = self.n, self.device
-        mask = self.action_mask if mask is None else mask
-        assert mean.dtype in (torch.float32, torch.float64) and log_std.dtype == mean.dtype
-        assert mean.shape == (n, 2) and mean.device == dev and mean.is_contiguous()
-        assert log_std.shape in ((n, 2), (1, 2)) and log_std.device == dev and log_std.is_contiguous()
-        assert mask.dtype == self.obs_dtype and mask.shape == (n, 42) and mask.device == dev and mask.is_contiguous()
-        assert (planned is None) == (executing is None), 'planned and executing go together'
-        pp = ep = up = None
-        if planned is not None:
-            assert planned.dtype == torch.float64 and planned.shape == (n, 2) and planned.device == dev and planned.is_contiguous()
-            assert executing.dtype in (torch.bool, torch.uint8) and executing.shape == (n,) and executing.device == dev and executing.is_contiguous()
-            pp, ep = C.c_void_p(planned.data_ptr()), C.c_void_p(executing.data_ptr())
-        if u is not None:
-            assert u.dtype == torch.float64 and u.shape == (n,) and u.device == dev and u.is_contiguous()
-            up = C.c_void_p(u.data_ptr())
-        if getattr(self, 'chosen_action', None) is None:  # (the library then reports that the chooser is off)
-            ap = fp = ip = lp = qp = None
-        else:
-            if probs and self.chosen_probs is None:
-                self.chosen_probs = torch.zeros((n, 42), dtype=torch.float64, device=dev)
-            ap, fp = C.c_void_p(self.chosen_action.data_ptr()), C.c_void_p(self.chosen_action_f32.data_ptr())
-            ip, lp = C.c_void_p(self.chosen_idx.data_ptr()), C.c_void_p(self.chosen_log_prob.data_ptr())
-            qp = C.c_void_p(self.chosen_probs.data_ptr()) if probs else None
-        L.check(self.lib.hope_env_choose(self.h, C.c_void_p(mean.data_ptr()), C.c_void_p(log_std.data_ptr()), 2 if log_std.shape[0] == n and n > 1 else 0,
-                                         int(mean.dtype == torch.float64), C.c_void_p(mask.data_ptr()), pp, ep, up,
-                                         C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), ap, fp, ip, lp, qp,
-                                         self._stream()), 'hope_env_choose')
+        arg = partial(L.tensor_arg, 'hope_env_choose', device=dev)
+        mp = arg('mean', mean, (torch.float32, torch.float64), (n, 2))
+        one_row = n > 1 and tuple(getattr(log_std, 'shape', ())) == (1, 2)
+        sp = arg('log_std', log_std, mean.dtype, (1, 2) if one_row else (n, 2))
+        kp = arg('mask', self.action_mask if mask is None else mask, self.obs_dtype, (n, L.N_ACTION))
+        if (planned is None) != (executing is None):
+            raise L.HopeError('hope_env_choose: planned and executing go together')
+        pp = arg('planned', planned, torch.float64, (n, 2), optional=True)
+        ep = arg('executing', executing, (torch.bool, torch.uint8), (n,), optional=True)
+        up = arg('u', u, torch.float64, (n,), optional=True)
+        if probs and self.chosen_probs is None and self.chosen_action is not None:
+            self.chosen_probs = torch.zeros((n, L.N_ACTION), dtype=torch.float64, device=dev)
+        ap = arg('chosen_action', self.chosen_action, self.action_dtype, (n, 2), optional=True)    # (None: the library reports that the chooser is off)
+        fp = arg('chosen_action_f32', self.chosen_action_f32, torch.float32, (n, 2), optional=True)
+        ip = arg('chosen_idx', self.chosen_idx, torch.int32, (n,), optional=True)
+        lp = arg('chosen_log_prob', self.chosen_log_prob, torch.float32, (n, 2), optional=True)
+        qp = arg('chosen_probs', self.chosen_probs, torch.float64, (n, L.N_ACTION), optional=True) if probs else None
+        L.check(self.lib.hope_env_choose(self.h, mp, sp, 0 if one_row or n == 1 else 2, int(mean.dtype == torch.float64), kp, pp, ep, up,
+                                         L.seed64(seed), L.seed64(counter), ap, fp, ip, lp, qp, self._stream()), 'hope_env_choose')
         out = (self.chosen_action, self.chosen_action_f32, self.chosen_idx, self.chosen_log_prob)
         return out + (self.chosen_probs,) if probs else out
 
@@ -495,7 +480,7 @@ class ParkingBatch:
         them.  Off by default."""
         torch.cuda.synchronize(self.device)
         L.check(self.lib.hope_env_obsnorm_enable(self.h), 'hope_env_obsnorm_enable')
-        if getattr(self, 'norm_lidar', None) is None:
+        if self.norm_lidar is None:
             self.norm_lidar = torch.zeros((self.n, L.OBSNORM_LIDAR), dtype=torch.float32, device=self.device)
             self.norm_target = torch.zeros((self.n, L.OBSNORM_TARGET), dtype=torch.float32, device=self.device)
         return self
@@ -511,20 +496,17 @@ class ParkingBatch:
         three launches on the current stream, no host synchronisation, no wait for a deferred search.
         -> (lidar f32 [rows, 120], target f32 [rows, 5]): (views of) persistent tensors of this object, overwritten by the next
         normalising call; (None, None) without normalize."""
-        dev = self.device
+        arg = partial(L.tensor_arg, 'hope_env_obsnorm', device=self.device)
         lidar = self.lidar if lidar is None else lidar
-        target = self.target if target is None else target
-        assert lidar.dtype in (torch.float32, torch.float64) and target.dtype == lidar.dtype
-        assert lidar.dim() == 2 and target.dim() == 2 and lidar.shape[1] == L.OBSNORM_LIDAR and target.shape[1] == L.OBSNORM_TARGET
-        assert lidar.shape[0] == target.shape[0]
-        assert lidar.device == dev and target.device == dev and lidar.is_contiguous() and target.is_contiguous()
-        rows = lidar.shape[0]
+        lp = arg('lidar', lidar, (torch.float32, torch.float64), (None, L.OBSNORM_LIDAR))
+        rows = lidar.shape[0]                                                   # (the library checks 1 <= rows <= N)
+        tp = arg('target', self.target if target is None else target, lidar.dtype, (rows, L.OBSNORM_TARGET))
         flags = (L.OBSNORM_UPDATE if update else 0) | (L.OBSNORM_NORMALIZE if normalize else 0)
         ol = ot = None
-        if normalize and getattr(self, 'norm_lidar', None) is not None:         # (without them the library reports that it is off)
-            ol, ot = C.c_void_p(self.norm_lidar.data_ptr()), C.c_void_p(self.norm_target.data_ptr())
-        L.check(self.lib.hope_env_obsnorm(self.h, C.c_void_p(lidar.data_ptr()), C.c_void_p(target.data_ptr()), rows,
-                                          int(lidar.dtype == torch.float64), flags, ol, ot, self._stream()), 'hope_env_obsnorm')
+        if normalize:                                                           # (None: the library reports that it is off)
+            ol = arg('norm_lidar', self.norm_lidar, torch.float32, (self.n, L.OBSNORM_LIDAR), optional=True)
+            ot = arg('norm_target', self.norm_target, torch.float32, (self.n, L.OBSNORM_TARGET), optional=True)
+        L.check(self.lib.hope_env_obsnorm(self.h, lp, tp, rows, int(lidar.dtype == torch.float64), flags, ol, ot, self._stream()), 'hope_env_obsnorm')
         if not normalize:
             return None, None
         return (self.norm_lidar, self.norm_target) if rows == self.n else (self.norm_lidar[:rows], self.norm_target[:rows])
@@ -539,14 +521,13 @@ class ParkingBatch:
         """-> (n_state, mean, S, std): numpy float64 [125] each (columns 0..119 lidar, 120..124 target); host-synchronous"""
         n = C.c_int64(0)
         mean, S, std = (np.zeros(L.OBSNORM_COLS, np.float64) for _ in range(3))
-        L.check(self.lib.hope_env_obsnorm_get(self.h, C.byref(n), mean.ctypes.data, S.ctypes.data, std.ctypes.data), 'hope_env_obsnorm_get')
+        L.check(self.lib.hope_env_obsnorm_get(self.h, C.byref(n), mean.ctypes, S.ctypes, std.ctypes), 'hope_env_obsnorm_get')
         return int(n.value), mean, S, std
 
     def obsnorm_load(self, n_state, mean, S, std):
         """replace the statistics (e.g. a checkpoint's); host-synchronous"""
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (mean, S, std)]
-        assert all(x.shape == (L.OBSNORM_COLS,) for x in a)
-        L.check(self.lib.hope_env_obsnorm_set(self.h, int(n_state), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data), 'hope_env_obsnorm_set')
+        a = [L.array_arg('hope_env_obsnorm_set', k, x, np.float64, (L.OBSNORM_COLS,)) for k, x in (('mean', mean), ('S', S), ('std', std))]
+        L.check(self.lib.hope_env_obsnorm_set(self.h, int(n_state), *[x.ctypes for x in a]), 'hope_env_obsnorm_set')
         return self
 
     # -- PPO's advantage block on the device (hope_env.h; rule: csrc/hope_gae_core.h) -----------------------------------
@@ -555,9 +536,8 @@ class ParkingBatch:
         k_adv_apply) over [rows, T] float32 tensors.  Off by default."""
         torch.cuda.synchronize(self.device)
         L.check(self.lib.hope_env_gae_enable(self.h), 'hope_env_gae_enable')
-        if getattr(self, 'gae_sums', None) is None:
+        if self.gae_sums is None:                                  # (_gae_out, (adv, v_target) [N, T], is allocated at the first call for its T)
             self.gae_sums = torch.zeros(3, dtype=torch.float64, device=self.device)
-            self._gae_out = None                                   # (adv, v_target): [N, T], allocated at the first call for its T
         return self
 
     def disable_gae(self):
@@ -573,34 +553,29 @@ class ParkingBatch:
         sums: a float64 [3] device tensor that takes {sum adv, sum adv^2, rows T}; None: this object's `gae_sums`.
         -> (adv [rows, T], v_target [rows, T], sums): (views of) persistent tensors of this object, overwritten by the next call."""
         dev = self.device
-        assert reward.dim() == 2 and v_last.dim() == 1
+        arg = partial(L.tensor_arg, 'hope_env_gae', device=dev)
+        rp = arg('reward', reward, torch.float32, (None, None))    # (the library checks 1 <= rows <= N and 1 <= T <= 4096)
         rows, t = reward.shape
-        for x in (reward, done, value, value_target):
-            assert x.shape == (rows, t)
-        assert v_last.shape == (rows,)
-        for x in (reward, done, value, v_last, value_target):
-            assert x.dtype == torch.float32 and x.device == dev and x.is_contiguous()
-        sums = getattr(self, 'gae_sums', None) if sums is None else sums
-        if sums is not None:
-            assert sums.dtype == torch.float64 and sums.shape == (3,) and sums.device == dev and sums.is_contiguous()
-        out = getattr(self, '_gae_out', None)
+        dp, vp = arg('done', done, torch.float32, (rows, t)), arg('value', value, torch.float32, (rows, t))
+        lp, tp = arg('v_last', v_last, torch.float32, (rows,)), arg('value_target', value_target, torch.float32, (rows, t))
+        sums = self.gae_sums if sums is None else sums
+        sp = arg('sums', sums, torch.float64, (3,), optional=True)
+        out = self._gae_out
         if out is None or out[0].shape[1] != t:                    # (before enable_gae the library reports that it is off)
             out = self._gae_out = tuple(torch.zeros((max(self.n, rows), t), dtype=torch.float32, device=dev) for _ in range(2))
-        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        ap, op = (arg(k, x, torch.float32, (out[0].shape[0], t)) for k, x in zip(('adv', 'v_target'), out))
         flags = 0 if normalize is None else (L.GAE_SUMS | (L.GAE_NORMALIZE if normalize else 0))
-        L.check(self.lib.hope_env_gae(self.h, P(reward), P(done), P(value), P(v_last), P(value_target), rows, t, float(gamma), float(lam), flags,
-                                      P(out[0]), P(out[1]), P(sums), self._stream()), 'hope_env_gae')
+        L.check(self.lib.hope_env_gae(self.h, rp, dp, vp, lp, tp, rows, t, float(gamma), float(lam), flags, ap, op, sp, self._stream()), 'hope_env_gae')
         return out[0][:rows], out[1][:rows], sums
 
     def adv_normalize(self, adv, sums, out=None):
         """out = (adv - mean) / (std + 1e-5) from sums = {sum, sum of squares, count} (float64 [3] on the device, e.g. all-reduced);
         out=None: in place.  One launch on the current stream."""
         out = adv if out is None else out
-        assert adv.dtype == torch.float32 and adv.is_contiguous() and adv.device == self.device
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device and out.shape == adv.shape
-        assert sums.dtype == torch.float64 and sums.shape == (3,) and sums.device == self.device and sums.is_contiguous()
-        L.check(self.lib.hope_env_adv_normalize(self.h, C.c_void_p(adv.data_ptr()), adv.numel(), C.c_void_p(sums.data_ptr()),
-                                                C.c_void_p(out.data_ptr()), self._stream()), 'hope_env_adv_normalize')
+        arg = partial(L.tensor_arg, 'hope_env_adv_normalize', device=self.device)
+        ap = arg('adv', adv, torch.float32, (None,) * getattr(adv, 'ndim', 1))
+        op, sp = arg('out', out, torch.float32, tuple(adv.shape)), arg('sums', sums, torch.float64, (3,))
+        L.check(self.lib.hope_env_adv_normalize(self.h, ap, adv.numel(), sp, op, self._stream()), 'hope_env_adv_normalize')
         return out
 
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
@@ -609,9 +584,9 @@ class ParkingBatch:
         k_eval_begin, k_eval_override, k_eval_track.  The stuck detector draws from the physical action box (tables.VALID_STEER /
         VALID_SPEED).  Enabling again keeps the state.  Off by default."""
         torch.cuda.synchronize(self.device)
-        box = np.array([T.VALID_STEER[0], T.VALID_STEER[1], T.VALID_SPEED[0], T.VALID_SPEED[1]], dtype=np.float64)
-        L.check(self.lib.hope_env_eval_enable(self.h, box.ctypes.data), 'hope_env_eval_enable')
-        if getattr(self, 'eval_alive', None) is None:
+        box = L.array_arg('hope_env_eval_enable', 'box', T.VALID_STEER + T.VALID_SPEED, np.float64, (4,))
+        L.check(self.lib.hope_env_eval_enable(self.h, box.ctypes), 'hope_env_eval_enable')
+        if self.eval_alive is None:
             dev = self.device
             self.eval_alive = torch.zeros(self.n, dtype=torch.uint8, device=dev)
             self.eval_word = torch.zeros((self.n, 8), dtype=torch.int8, device=dev)
@@ -624,16 +599,11 @@ class ParkingBatch:
         L.check(self.lib.hope_env_eval_disable(self.h), 'hope_env_eval_disable')
         return self
 
-    def _eval_obs(self, t, shape, dtype):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.device == self.device and t.is_contiguous()
-        return C.c_void_p(t.data_ptr())
-
     def eval_begin(self, target=None, pose=None):
         """a new episode in every scene, from the first observation (None: the env's own target / pose); one k_eval_begin launch on
         the current stream, no host synchronisation"""
-        n = self.n
-        tp = self._eval_obs(self.target if target is None else target, (n, 5), self.obs_dtype)
-        pp = self._eval_obs(self.pose if pose is None else pose, (n, 3), torch.float64)
+        tp = L.tensor_arg('hope_env_eval_begin', 'target', self.target if target is None else target, self.obs_dtype, (self.n, 5), self.device)
+        pp = L.tensor_arg('hope_env_eval_begin', 'pose', self.pose if pose is None else pose, torch.float64, (self.n, 3), self.device)
         L.check(self.lib.hope_env_eval_begin(self.h, tp, pp, self._stream()), 'hope_env_eval_begin')
         return self
 
@@ -642,49 +612,42 @@ class ParkingBatch:
         whose target did not change in the last step are replaced by the clipped draw from the physical action box.  u f64 [N, 2] in
         [0, 1) or None: counter-based draws keyed by (seed, counter, scene, dimension).  One k_eval_override launch, no host
         synchronisation.  -> eval_alive (uint8 [N], persistent): the scenes whose episode is still running -- step()'s `active`."""
-        n, dev = self.n, self.device
-        assert actions.shape == (n, 2) and actions.dtype in (torch.float32, torch.float64) and actions.is_contiguous() and actions.device == dev
-        up = None
-        if u is not None:
-            assert u.dtype == torch.float64 and u.shape == (n, 2) and u.device == dev and u.is_contiguous()
-            up = C.c_void_p(u.data_ptr())
-        al = getattr(self, 'eval_alive', None)               # (without it the library reports that the tracker is off)
-        L.check(self.lib.hope_env_eval_override(self.h, C.c_void_p(actions.data_ptr()), int(actions.dtype == torch.float64), up,
-                                                C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)),
-                                                C.c_void_p(al.data_ptr()) if al is not None else None, self._stream()), 'hope_env_eval_override')
-        return al
+        n, arg = self.n, partial(L.tensor_arg, 'hope_env_eval_override', device=self.device)
+        ap = arg('actions', actions, (torch.float32, torch.float64), (n, 2))
+        up = arg('u', u, torch.float64, (n, 2), optional=True)
+        lp = arg('eval_alive', self.eval_alive, torch.uint8, (n,), optional=True)    # (None: the library reports that the tracker is off)
+        L.check(self.lib.hope_env_eval_override(self.h, ap, int(actions.dtype == torch.float64), up, L.seed64(seed), L.seed64(counter), lp,
+                                                self._stream()), 'hope_env_eval_override')
+        return self.eval_alive
 
     def eval_track(self, target=None, pose=None, reward=None, status=None, done=None, rs_word=None):
         """the tally of the step just taken (None: the env's own outputs); one k_eval_track launch on the current stream, no host
         synchronisation, no wait for a deferred search.  -> (eval_word int8 [N, 8]: rs_word with the found flag cleared for frozen
         scenes, eval_done uint8 [N]: episodes that ended in this step): persistent tensors, overwritten by the next call."""
-        n = self.n
-        ptrs = [self._eval_obs(self.target if target is None else target, (n, 5), self.obs_dtype),
-                self._eval_obs(self.pose if pose is None else pose, (n, 3), torch.float64),
-                self._eval_obs(self.reward if reward is None else reward, (n,), self.obs_dtype),
-                self._eval_obs(self.status if status is None else status, (n,), torch.int32),
-                self._eval_obs(self.done if done is None else done, (n,), torch.uint8),
-                self._eval_obs(self.rs_word if rs_word is None else rs_word, (n, 8), torch.int8)]
-        if getattr(self, 'eval_word', None) is None:         # (the library then reports that the tracker is off)
-            wp = dp = None
-        else:
-            wp, dp = C.c_void_p(self.eval_word.data_ptr()), C.c_void_p(self.eval_done.data_ptr())
-        L.check(self.lib.hope_env_eval_track(self.h, *ptrs, wp, dp, self._stream()), 'hope_env_eval_track')
-        return getattr(self, 'eval_word', None), getattr(self, 'eval_done', None)
+        n, arg = self.n, partial(L.tensor_arg, 'hope_env_eval_track', device=self.device)
+        ptrs = [arg('target', self.target if target is None else target, self.obs_dtype, (n, 5)),
+                arg('pose', self.pose if pose is None else pose, torch.float64, (n, 3)),
+                arg('reward', self.reward if reward is None else reward, self.obs_dtype, (n,)),
+                arg('status', self.status if status is None else status, torch.int32, (n,)),
+                arg('done', self.done if done is None else done, torch.uint8, (n,)),
+                arg('rs_word', self.rs_word if rs_word is None else rs_word, torch.int8, (n, 8)),
+                arg('eval_word', self.eval_word, torch.int8, (n, 8), optional=True),    # (None: the library reports that the tracker is off)
+                arg('eval_done', self.eval_done, torch.uint8, (n,), optional=True)]
+        L.check(self.lib.hope_env_eval_track(self.h, *ptrs, self._stream()), 'hope_env_eval_track')
+        return self.eval_word, self.eval_done
 
     def eval_records(self):
         """-> float32 [N, 4]: status, steps, summed reward, path length of every scene's episode so far (a persistent tensor,
         overwritten by the next call); one launch, no host synchronisation"""
-        rec = getattr(self, '_eval_rec', None)
-        L.check(self.lib.hope_env_eval_records(self.h, C.c_void_p(rec.data_ptr()) if rec is not None else None, self._stream()),
-                'hope_env_eval_records')
-        return rec
+        rp = L.tensor_arg('hope_env_eval_records', 'records', self._eval_rec, torch.float32, (self.n, 4), self.device, optional=True)
+        L.check(self.lib.hope_env_eval_records(self.h, rp, self._stream()), 'hope_env_eval_records')
+        return self._eval_rec
 
     def eval_state(self):
         """the tracker's state block (numpy uint64 [10, N]: previous target, previous position, summed reward, path length as
         float64 bits, the packed steps / status / alive / stuck word) -- host-synchronous; tests"""
         out = np.zeros((L.EVAL_STATE_WORDS, self.n), np.uint64)
-        L.check(self.lib.hope_env_eval_download_state(self.h, out.ctypes.data), 'hope_env_eval_download_state')
+        L.check(self.lib.hope_env_eval_download_state(self.h, out.ctypes), 'hope_env_eval_download_state')
         return out
 
     def queue_check(self):
@@ -706,7 +669,7 @@ class ParkingBatch:
     def n_obst_now(self):
         """obstacle count of every scene as it is on the device now (device-side draws change it): numpy int32 [N]"""
         out = np.zeros(self.n, np.int32)
-        L.check(self.lib.hope_env_download_n_obst(self.h, out.ctypes.data), 'hope_env_download_n_obst')
+        L.check(self.lib.hope_env_download_n_obst(self.h, out.ctypes), 'hope_env_download_n_obst')
         return out
 
     def map_levels(self, active=None, out=None, detail=False):
@@ -716,30 +679,26 @@ class ParkingBatch:
         last step's `done` and the previous labels as `out` to relabel only the scenes that drew a new map)."""
         if out is None:
             out = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        assert out.dtype == torch.uint8 and out.shape == (self.n,) and out.device == self.device and out.is_contiguous()
-        ap = None
-        if active is not None:
-            assert active.dtype == torch.uint8 and active.shape == (self.n,) and active.device == self.device and active.is_contiguous()
-            ap = C.c_void_p(active.data_ptr())
+        arg = partial(L.tensor_arg, 'hope_env_map_level', device=self.device)
         det = None
         if detail is not False and detail is not None:
             det = detail if torch.is_tensor(detail) else torch.zeros((self.n, 8), dtype=torch.int32, device=self.device)
-            assert det.dtype == torch.int32 and det.shape == (self.n, 8) and det.device == self.device and det.is_contiguous()
-        L.check(self.lib.hope_env_map_level(self.h, ap, C.c_void_p(out.data_ptr()), C.c_void_p(det.data_ptr()) if det is not None else None,
-                                            self._stream()), 'hope_env_map_level')
+        ap, op = arg('active', active, torch.uint8, (self.n,), optional=True), arg('out', out, torch.uint8, (self.n,))
+        dp = arg('detail', det, torch.int32, (self.n, 8), optional=True)
+        L.check(self.lib.hope_env_map_level(self.h, ap, op, dp, self._stream()), 'hope_env_map_level')
         return (out, det) if det is not None else out
 
     def restart(self, mask):
         """episodes flagged in mask (u8 [N]) go back to their start pose, t = 0 (same map)."""
-        assert mask.dtype == torch.uint8 and mask.shape == (self.n,) and mask.device == self.device
-        L.check(self.lib.hope_env_restart(self.h, C.c_void_p(mask.data_ptr()), self._stream()), 'hope_env_restart')
+        mp = L.tensor_arg('hope_env_restart', 'mask', mask, torch.uint8, (self.n,), self.device)
+        L.check(self.lib.hope_env_restart(self.h, mp, self._stream()), 'hope_env_restart')
         return self
 
     def kernel_ms(self, reset=True):
         """{kernel name: (accumulated ms, launches)} from the library's per-launch HIP events (profile=True)."""
         ms = np.zeros(len(L.KERNELS))
         cnt = np.zeros(len(L.KERNELS), np.int64)
-        L.check(self.lib.hope_env_kernel_ms(self.h, ms.ctypes.data, cnt.ctypes.data, int(reset)), 'hope_env_kernel_ms')
+        L.check(self.lib.hope_env_kernel_ms(self.h, ms.ctypes, cnt.ctypes, int(reset)), 'hope_env_kernel_ms')
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(L.KERNELS)}
 
     def kernel_union_ms(self, reset=True):
@@ -747,7 +706,7 @@ class ParkingBatch:
         kernel's launch intervals (the two tile classes overlap on two streams).  Read it before kernel_ms(reset=True)."""
         ms = np.zeros(len(L.KERNELS))
         cnt = np.zeros(len(L.KERNELS), np.int64)
-        L.check(self.lib.hope_env_kernel_union_ms(self.h, ms.ctypes.data, cnt.ctypes.data, int(reset)), 'hope_env_kernel_union_ms')
+        L.check(self.lib.hope_env_kernel_union_ms(self.h, ms.ctypes, cnt.ctypes, int(reset)), 'hope_env_kernel_union_ms')
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(L.KERNELS)}
 
     def profile_kernels(self, names=None):
@@ -777,17 +736,14 @@ class ParkingBatch:
     # -- state -------------------------------------------------------------------------------------
     def download_state(self):
         pose, t, acc = np.zeros((self.n, 3)), np.zeros(self.n, np.int32), np.zeros(self.n)
-        L.check(self.lib.hope_env_download_state(self.h, pose.ctypes.data, t.ctypes.data, acc.ctypes.data),
-                'hope_env_download_state')
+        L.check(self.lib.hope_env_download_state(self.h, pose.ctypes, t.ctypes, acc.ctypes), 'hope_env_download_state')
         return pose, t, acc
 
     def upload_state(self, pose=None, t=None, accum=None):
-        p = np.ascontiguousarray(pose, dtype=np.float64) if pose is not None else None
-        tt = np.ascontiguousarray(t, dtype=np.int32) if t is not None else None
-        a = np.ascontiguousarray(accum, dtype=np.float64) if accum is not None else None
-        L.check(self.lib.hope_env_upload_state(self.h, p.ctypes.data if p is not None else None,
-                                               tt.ctypes.data if tt is not None else None,
-                                               a.ctypes.data if a is not None else None), 'hope_env_upload_state')
+        a = [L.array_arg('hope_env_upload_state', 'pose', pose, np.float64, (self.n, 3), optional=True),
+             L.array_arg('hope_env_upload_state', 't', t, np.int32, (self.n,), optional=True),
+             L.array_arg('hope_env_upload_state', 'accum', accum, np.float64, (self.n,), optional=True)]
+        L.check(self.lib.hope_env_upload_state(self.h, *[None if x is None else x.ctypes for x in a]), 'hope_env_upload_state')
 
     def close(self):
         if getattr(self, 'h', None):

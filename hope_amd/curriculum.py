@@ -11,6 +11,7 @@ restatement the device runs (include/hope_env.h, DESIGN.md "Curriculum"):
            p = 0.2 / n_cases + 0.8 * fail / sum(fail)                     (DlpCaseChoose.choose_case); uniform before 500
 """
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
@@ -83,20 +84,19 @@ def lists_host(n_obst, buckets, n_cases, max_obstacles, episodes, win_n, win_s, 
     """hope_curriculum_lists_host: the weighted draw lists the device builds from these windows, computed on the host (no GPU).
     -> dict(list0, list1 [2^20] int32 (None without want_lists), prob [4 + n_cases], pw [4], positions [2, 4 + n_cases])"""
     lib = L.load_library()
-    nob = np.ascontiguousarray(n_obst, dtype=np.int32)
-    bk = None if buckets is None else np.ascontiguousarray(buckets, dtype=np.uint8)
+    arg = partial(L.array_arg, 'hope_curriculum_lists_host')
+    nob = arg('n_obst', n_obst, np.int32, (None,))
+    bk = arg('buckets', buckets, np.uint8, nob.shape, optional=True)
     nb = 4 + int(n_cases)
-    e = np.ascontiguousarray(episodes, dtype=np.uint64)
-    wn, ws = np.ascontiguousarray(win_n, dtype=np.float64), np.ascontiguousarray(win_s, dtype=np.float64)
-    assert len(e) == nb and len(wn) == nb and len(ws) == nb and (bk is None or len(bk) == len(nob))
+    e = arg('episodes', episodes, np.uint64, (nb,))
+    wn, ws = arg('win_n', win_n, np.float64, (nb,)), arg('win_s', win_s, np.float64, (nb,))
     l0 = np.full(L.CURRICULUM_LIST_LEN, -1, np.int32) if want_lists else None
     l1 = np.full(L.CURRICULUM_LIST_LEN, -1, np.int32) if want_lists else None
     prob, pw, pos = np.zeros(nb), np.zeros(4), np.zeros((2, nb), np.int32)
     p = L.CurriculumParams(**dict(DEFAULTS, **params))
-    L.check(lib.hope_curriculum_lists_host(C.byref(p), len(nob), nob.ctypes.data, None if bk is None else bk.ctypes.data, int(n_cases),
-                                           int(max_obstacles), e.ctypes.data, wn.ctypes.data, ws.ctypes.data,
-                                           None if l0 is None else l0.ctypes.data, None if l1 is None else l1.ctypes.data,
-                                           prob.ctypes.data, pw.ctypes.data, pos.ctypes.data), 'hope_curriculum_lists_host')
+    L.check(lib.hope_curriculum_lists_host(C.byref(p), len(nob), nob.ctypes, None if bk is None else bk.ctypes, int(n_cases), int(max_obstacles),
+                                           e.ctypes, wn.ctypes, ws.ctypes, None if l0 is None else l0.ctypes, None if l1 is None else l1.ctypes,
+                                           prob.ctypes, pw.ctypes, pos.ctypes), 'hope_curriculum_lists_host')
     return {'list0': l0, 'list1': l1, 'prob': prob, 'pw': pw, 'positions': pos}
 
 

@@ -18,6 +18,7 @@ pure-Python twin of the detail record those entries return.
 """
 import ctypes as C
 import math
+from functools import partial
 
 import numpy as np
 
@@ -308,15 +309,15 @@ def get_map_levels_host(start, dest, verts, n_obst, detail=False, n_threads=0):
     -> uint8 [n] (index into LEVEL_NAMES) [, int32 [n, 8] detail]"""
     from . import _lib as L
     lib = L.load_library()
-    start, dest = np.ascontiguousarray(start, dtype=np.float64), np.ascontiguousarray(dest, dtype=np.float64)
-    verts, n_obst = np.ascontiguousarray(verts, dtype=np.float64), np.ascontiguousarray(n_obst, dtype=np.int32)
+    arg = partial(L.array_arg, 'hope_map_level_host')
+    n_obst = arg('n_obst', n_obst, np.int32, (None,))
     n = len(n_obst)
-    if verts.ndim != 4 or verts.shape[0] != n or verts.shape[2:] != (4, 2) or start.shape != (n, 3) or dest.shape != (n, 3):
-        raise ValueError('get_map_levels_host: start / dest [n, 3], verts [n, max_obstacles, 4, 2], n_obst [n] expected')
+    start, dest = arg('start', start, np.float64, (n, 3)), arg('dest', dest, np.float64, (n, 3))
+    verts = arg('verts', verts, np.float64, (n, None, 4, 2))
     level = np.zeros(n, np.uint8)
     det = np.zeros((n, DETAIL_WORDS), np.int32) if detail else None
-    L.check(lib.hope_map_level_host(n, verts.shape[1], start.ctypes.data, dest.ctypes.data, verts.ctypes.data, n_obst.ctypes.data,
-                                    level.ctypes.data, det.ctypes.data if detail else None, int(n_threads)), 'hope_map_level_host')
+    L.check(lib.hope_map_level_host(n, verts.shape[1], start.ctypes, dest.ctypes, verts.ctypes, n_obst.ctypes, level.ctypes,
+                                    det.ctypes if detail else None, int(n_threads)), 'hope_map_level_host')
     return (level, det) if detail else level
 
 
@@ -326,18 +327,16 @@ def get_map_levels_device(start, dest, verts, n_obst, detail=False):
     import torch
     from . import _lib as L
     lib = L.load_library()
-    n = n_obst.shape[0]
-    for t, dt, shape in ((start, torch.float64, (n, 3)), (dest, torch.float64, (n, 3)), (n_obst, torch.int32, (n,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
-            raise ValueError('get_map_levels_device: contiguous device tensors start / dest float64 [n, 3], n_obst int32 [n] expected')
-    if verts.dtype != torch.float64 or verts.dim() != 4 or verts.shape[0] != n or tuple(verts.shape[2:]) != (4, 2) or not verts.is_cuda \
-            or not verts.is_contiguous():
-        raise ValueError('get_map_levels_device: verts must be a contiguous float64 device tensor [n, max_obstacles, 4, 2]')
     dev = verts.device
+    if dev.type != 'cuda':
+        raise L.HopeError(f'hope_map_level_device: verts must be on a HIP device, got {dev}')
+    arg = partial(L.tensor_arg, 'hope_map_level_device', device=dev)
+    vp = arg('verts', verts, torch.float64, (None, None, 4, 2))
+    n = verts.shape[0]
+    sp, dp, np_ = arg('start', start, torch.float64, (n, 3)), arg('dest', dest, torch.float64, (n, 3)), arg('n_obst', n_obst, torch.int32, (n,))
     level = torch.zeros(n, dtype=torch.uint8, device=dev)
     det = torch.zeros((n, DETAIL_WORDS), dtype=torch.int32, device=dev) if detail else None
+    lp, tp = arg('level', level, torch.uint8, (n,)), arg('detail', det, torch.int32, (n, DETAIL_WORDS), optional=True)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    L.check(lib.hope_map_level_device(dev.index or 0, n, verts.shape[1], C.c_void_p(start.data_ptr()), C.c_void_p(dest.data_ptr()),
-                                      C.c_void_p(verts.data_ptr()), C.c_void_p(n_obst.data_ptr()), C.c_void_p(level.data_ptr()),
-                                      C.c_void_p(det.data_ptr()) if detail else None, stream), 'hope_map_level_device')
+    L.check(lib.hope_map_level_device(dev.index or 0, n, verts.shape[1], sp, dp, vp, np_, lp, tp, stream), 'hope_map_level_device')
     return (level, det) if detail else level

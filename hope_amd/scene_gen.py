@@ -22,9 +22,8 @@ def generate_arrays(level, n, seed=0, max_obst=128, first_index=0, bay_mode=-1, 
     start, dest, bbox = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
     verts = np.zeros((n, max_obst, 4, 2))
     nob, cid = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    rc = lib.hope_scenegen_generate(LEVEL_ID[level], int(bay_mode), int(n), int(seed) & (2 ** 64 - 1), int(first_index), int(max_obst),
-                                    start.ctypes.data, dest.ctypes.data, bbox.ctypes.data, verts.ctypes.data, nob.ctypes.data,
-                                    cid.ctypes.data, int(threads))
+    rc = lib.hope_scenegen_generate(LEVEL_ID[level], int(bay_mode), int(n), L.seed64(seed), int(first_index), int(max_obst),
+                                    start.ctypes, dest.ctypes, bbox.ctypes, verts.ctypes, nob.ctypes, cid.ctypes, int(threads))
     if rc != 0:
         raise L.HopeError(f'hope_scenegen_generate failed (code {rc})')
     return start, dest, bbox, verts, nob, np.full((n, max_obst), 4, np.int32), cid
@@ -38,9 +37,9 @@ def generate_arrays_det(level, n, seed=0, max_obst=128, first_index=0, bay_mode=
     start, dest, bbox = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
     verts = np.zeros((n, max_obst, 4, 2))
     nob, cid = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    L.check(lib.hope_scenegen_generate_det(LEVEL_ID[level], int(bay_mode), int(n), int(seed) & (2 ** 64 - 1), int(first_index), int(max_obst),
-                                           start.ctypes.data, dest.ctypes.data, bbox.ctypes.data, verts.ctypes.data, nob.ctypes.data,
-                                           cid.ctypes.data, int(threads)), 'hope_scenegen_generate_det')
+    L.check(lib.hope_scenegen_generate_det(LEVEL_ID[level], int(bay_mode), int(n), L.seed64(seed), int(first_index), int(max_obst),
+                                           start.ctypes, dest.ctypes, bbox.ctypes, verts.ctypes, nob.ctypes, cid.ctypes, int(threads)),
+            'hope_scenegen_generate_det')
     return start, dest, bbox, verts, nob, np.full((n, max_obst), 4, np.int32), cid
 
 
@@ -55,14 +54,13 @@ def generate_arrays_device(level, n, seed=0, max_obst=128, first_index=0, bay_mo
         f64 = dict(dtype=torch.float64, device=device)
         out = (torch.zeros((n, 3), **f64), torch.zeros((n, 3), **f64), torch.zeros((n, 4), **f64), torch.zeros((n, max_obst, 4, 2), **f64),
                torch.zeros(n, dtype=torch.int32, device=device), torch.zeros(n, dtype=torch.int32, device=device))
-    start, dest, bbox, verts, nob, cid = out
-    for t, shp, dt in zip(out, ((n, 3), (n, 3), (n, 4), (n, max_obst, 4, 2), (n,), (n,)), (torch.float64,) * 4 + (torch.int32,) * 2):
-        assert tuple(t.shape) == shp and t.dtype == dt and t.is_contiguous() and t.device == device, 'generate_arrays_device: bad output tensor'
+    spec = (('start', torch.float64, (n, 3)), ('dest', torch.float64, (n, 3)), ('bbox', torch.float64, (n, 4)),
+            ('verts', torch.float64, (n, max_obst, 4, 2)), ('n_obst', torch.int32, (n,)), ('case_id', torch.int32, (n,)))
+    ptrs = [L.tensor_arg('hope_scenegen_generate_device', k, t, dt, shp, device) for t, (k, dt, shp) in zip(out, spec)]
     stream = torch.cuda.current_stream(device).cuda_stream
-    L.check(lib.hope_scenegen_generate_device(device.index or 0, LEVEL_ID[level], int(bay_mode), int(n), int(seed) & (2 ** 64 - 1),
-                                              int(first_index), int(max_obst), start.data_ptr(), dest.data_ptr(), bbox.data_ptr(),
-                                              verts.data_ptr(), nob.data_ptr(), cid.data_ptr(), stream), 'hope_scenegen_generate_device')
-    return start, dest, bbox, verts, nob, cid
+    L.check(lib.hope_scenegen_generate_device(device.index or 0, LEVEL_ID[level], int(bay_mode), int(n), L.seed64(seed), int(first_index),
+                                              int(max_obst), *ptrs, stream), 'hope_scenegen_generate_device')
+    return tuple(out)
 
 
 def pool_level_counts(n_pool, levels):
@@ -127,9 +125,9 @@ class PoolRefresher:
             for j, lv in enumerate(self.levels):
                 a = j * per
                 b = self.n if j == len(self.levels) - 1 else a + per
-                rc = lib.hope_scenegen_generate(LEVEL_ID[lv], -1, b - a, (self.seed * 1000003 + j) & (2 ** 64 - 1), batch * self.n,
-                                                self.env.max_obst, start[a:].ctypes.data, dest[a:].ctypes.data, bbox[a:].ctypes.data,
-                                                verts[a:].ctypes.data, nob[a:].ctypes.data, None, self.threads)
+                rc = lib.hope_scenegen_generate(LEVEL_ID[lv], -1, b - a, L.seed64(self.seed * 1000003 + j), batch * self.n, self.env.max_obst,
+                                                start[a:].ctypes, dest[a:].ctypes, bbox[a:].ctypes, verts[a:].ctypes, nob[a:].ctypes, None,
+                                                self.threads)
                 if rc != 0:
                     raise L.HopeError(f'hope_scenegen_generate failed (code {rc})')
             self.gen_seconds += time.perf_counter() - t0

@@ -349,3 +349,100 @@ def test_enable_disable_enable_starts_from_the_initial_state(feature):
     fresh(2)
     assert disable() == OK and disable() == OK                       # (idempotent)
     assert lib.hope_env_destroy(h) == OK
+
+
+def test_binding_refuses_bad_arguments_by_name():
+    """ParkingBatch in front of the ABI: a tensor or array of the wrong dtype, shape or layout is refused by _lib.tensor_arg /
+    _lib.array_arg with a HopeError that names the call and the argument, before the library is called -- the step counter and the
+    output arena are what they were.  Every bad argument here occupies at least as much memory as the right one (a larger element, one
+    element more, one dimension more, a strided view over a larger buffer); too short and wrong device: tests/test_binding_args.py."""
+    from hope_amd import ParkingBatch
+    from hope_amd.scene_gen import mixed_arrays
+    n, mo, t, dev = 64, 16, 5, 'cuda:0'
+    start, dest, bbox, verts, nob, _ = mixed_arrays(4 * n, levels=('Normal',), seed=5, max_obst=32)
+    keep = np.nonzero(nob <= mo)[0][:n]
+    assert len(keep) == n
+    arrs = [start[keep], dest[keep], bbox[keep], np.ascontiguousarray(verts[keep][:, :mo]), nob[keep]]
+    g = torch.Generator(device=dev).manual_seed(7)
+    acts = [torch.rand((n, 2), device=dev, generator=g) * 2 - 1 for _ in range(2)]
+    envs = []
+    for _ in range(2):
+        e = ParkingBatch(n, mo)
+        e.set_scene_arrays(np.arange(n), *arrs)
+        e.set_pool(tuple(arrs) + (None,))
+        e.enable_planner().enable_chooser().enable_obsnorm().enable_gae().enable_eval_tracker()
+        e.reset_obs().step(acts[0])
+        envs.append(e)
+    env, twin = envs
+
+    z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+    u8, i32, i64, f64 = torch.uint8, torch.int32, torch.int64, torch.float64
+    mask, strided = z(n, dtype=u8), z(2 * n, dtype=u8)[::2]
+    mean, log_std = z(n, 2), z(1, 2)
+    rew = dict(reward=z(n, t), done=z(n, t), value=z(n, t), v_last=z(n), value_target=z(n, t), gamma=0.98, lam=0.95)
+    wn = np.ones(4)
+    cases = [
+        ('hope_env_step', 'actions', lambda: env.step(z(n, 2, dtype=f64))),
+        ('hope_env_step', 'actions', lambda: env.step(z(n, 3))),
+        ('hope_env_step', 'actions', lambda: env.step(z(2, n).t())),
+        ('hope_env_step', 'active', lambda: env.step(acts[1], active=z(n, dtype=i32))),
+        ('hope_env_step', 'active', lambda: env.step(acts[1], active=z(n + 1, dtype=u8))),
+        ('hope_env_step', 'active', lambda: env.step(acts[1], active=strided)),
+        ('hope_env_reset_obs', 'active', lambda: env.reset_obs(active=z(n))),
+        ('hope_env_reset_obs', 'active', lambda: env.reset_obs(active=z(n, 1, dtype=u8))),
+        ('hope_env_redraw', 'mask', lambda: env.redraw(z(n + 1, dtype=u8))),
+        ('hope_env_redraw', 'mask', lambda: env.redraw(strided)),
+        ('hope_env_restart', 'mask', lambda: env.restart(strided)),
+        ('hope_env_restart', 'mask', lambda: env.restart(z(n, dtype=i64))),
+        ('hope_env_map_level', 'out', lambda: env.map_levels(out=z(n, dtype=i32))),
+        ('hope_env_map_level', 'active', lambda: env.map_levels(active=z(n + 1, dtype=u8))),
+        ('hope_env_map_level', 'detail', lambda: env.map_levels(detail=z(n, 9, dtype=i32))),
+        ('hope_env_planner_step', 'rs_word', lambda: env.planner_step(rs_word=z(n, 9, dtype=torch.int8))),
+        ('hope_env_planner_step', 'rs_lengths', lambda: env.planner_step(rs_lengths=z(n, 5, dtype=f64))),
+        ('hope_env_planner_step', 'done', lambda: env.planner_step(done=z(n + 1, dtype=u8))),
+        ('hope_env_planner_step', 'actions', lambda: env.planner_step(actions=z(n, 3))),
+        ('hope_env_choose', 'mean', lambda: env.choose_actions(z(n + 1, 2), log_std)),
+        ('hope_env_choose', 'log_std', lambda: env.choose_actions(mean, z(n, 2, dtype=f64))),
+        ('hope_env_choose', 'mask', lambda: env.choose_actions(mean, log_std, mask=z(n, 43))),
+        ('hope_env_choose', 'planned', lambda: env.choose_actions(mean, log_std, planned=z(n, 3, dtype=f64), executing=mask)),
+        ('hope_env_choose', 'executing', lambda: env.choose_actions(mean, log_std, planned=z(n, 2, dtype=f64), executing=z(n, dtype=i32))),
+        ('hope_env_choose', 'u', lambda: env.choose_actions(mean, log_std, u=z(n + 1, dtype=f64))),
+        ('hope_env_obsnorm', 'lidar', lambda: env.obsnorm(lidar=z(n, 121))),
+        ('hope_env_obsnorm', 'target', lambda: env.obsnorm(target=z(n, 5, dtype=f64))),
+        ('hope_env_obsnorm', 'target', lambda: env.obsnorm(target=z(n + 1, 5))),
+        ('hope_env_gae', 'done', lambda: env.gae(**dict(rew, done=z(n, t + 1)))),
+        ('hope_env_gae', 'value', lambda: env.gae(**dict(rew, value=z(n, t, dtype=f64)))),
+        ('hope_env_gae', 'v_last', lambda: env.gae(**dict(rew, v_last=z(n + 1)))),
+        ('hope_env_gae', 'sums', lambda: env.gae(**rew, sums=z(4, dtype=f64))),
+        ('hope_env_eval_track', 'target', lambda: env.eval_track(target=z(n, 5, dtype=f64))),
+        ('hope_env_eval_track', 'status', lambda: env.eval_track(status=z(n, dtype=i64))),
+        ('hope_env_eval_track', 'done', lambda: env.eval_track(done=z(n + 1, dtype=u8))),
+        ('hope_env_eval_track', 'rs_word', lambda: env.eval_track(rs_word=z(n, 9, dtype=torch.int8))),
+        ('hope_env_set_scenes', 'start', lambda: env.set_scene_arrays(np.arange(n), np.zeros((n, 4)), *arrs[1:])),
+        ('hope_env_set_scenes', 'bbox', lambda: env.set_scene_arrays(np.arange(n), arrs[0], arrs[1], np.zeros((n, 5)), arrs[3], arrs[4])),
+        ('hope_env_set_scenes', 'verts', lambda: env.set_scene_arrays(np.arange(n), *arrs[:3], np.zeros((n, mo + 1, 4, 2)), arrs[4])),
+        ('hope_env_set_scenes', 'n_obst', lambda: env.set_scene_arrays(np.arange(n), *arrs[:4], np.zeros(n + 1, np.int32))),
+        ('hope_env_set_pool', 'verts', lambda: env.set_pool((*arrs[:3], np.zeros((n, mo + 1, 4, 2)), arrs[4], None))),
+        ('hope_env_set_pool', 'start', lambda: env.set_pool((np.zeros((n + 1, 3)), *arrs[1:], None))),
+        ('hope_env_upload_state', 'pose', lambda: env.upload_state(pose=np.zeros((n, 4)))),
+        ('hope_env_upload_state', 't', lambda: env.upload_state(t=np.zeros(n + 1, np.int32))),
+        ('hope_env_upload_state', 'accum', lambda: env.upload_state(accum=np.zeros((n, 2)))),
+        ('hope_env_restore_maps', 'pool_index', lambda: env.restore_maps(np.zeros(n + 1, np.int32), np.zeros(n, np.uint32), seed=1)),
+        ('hope_env_restore_maps', 'episode', lambda: env.restore_maps(np.zeros(n, np.int32), np.zeros(n + 1, np.uint32), seed=1)),
+        ('hope_env_curriculum_set_windows', 'win_s', lambda: env.curriculum_set_windows(wn, np.ones(5), wn, wn)),
+        ('hope_env_curriculum_set_windows', 'successes', lambda: env.curriculum_set_windows(wn, wn, wn, np.ones((4, 2)))),
+    ]
+    for call, arg, bad in cases:
+        torch.cuda.synchronize()
+        before = (env.last_step(), env._arena.clone())
+        with pytest.raises(L.HopeError, match=f'^{call}: {arg} must be '):
+            bad()
+        torch.cuda.synchronize()
+        assert env.last_step() == before[0] and torch.equal(env._arena, before[1]), (call, arg)
+    env.step(acts[1])
+    twin.step(acts[1])
+    torch.cuda.synchronize()
+    assert env.last_step() == twin.last_step() and torch.equal(env._arena, twin._arena)
+    assert int(env.status.min()) >= 1 and bool(torch.isfinite(env.lidar).all())
+    env.close()
+    twin.close()

@@ -162,7 +162,7 @@ def test_misuse_returns_the_documented_codes():
     assert lib.hope_env_destroy(h) == OK
     assert lib.hope_env_map_level(h, None, p(lv), None, None) == EINVAL         # a destroyed handle
     env = make_env(n, mo=mo, unique=16)
-    with pytest.raises(AssertionError):
+    with pytest.raises(L.HopeError):
         env.map_levels(out=torch.zeros(n, dtype=torch.int32, device='cuda'))
     assert env.map_levels().shape == (n,)
     env.close()

@@ -55,6 +55,86 @@ def test_library_exports_every_declared_symbol():
     assert L.hope_abi_version() == _lib.ABI_VERSION == 8
 
 
+def _header(name=os.path.join('include', 'hope_env.h'), keep_comments=False):
+    text = open(os.path.join(ROOT, name)).read()
+    return text if keep_comments else re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+
+
+def _c_number(text):
+    """the value of a numeric macro / constexpr body: literals, parentheses, shifts, a minus sign, an unsigned suffix"""
+    text = re.sub(r'\b(0[xX][0-9a-fA-F]+|\d+)[uU]\b', r'\1', text.strip())
+    assert re.fullmatch(r'[0-9a-fA-FxX.()<\- ]+', text), text
+    return eval(text, {'__builtins__': {}})
+
+
+def test_prototype_table_mirrors_the_header():
+    """_lib.PROTOTYPES against include/hope_env.h: every prototype's return type, parameter count and the kind of every parameter
+    (pointer, int / int32_t, uint32_t, int64_t, uint64_t, double, size_t -- compared by size and signedness, not by ctypes identity)."""
+    from hope_amd import _lib
+    hdr = re.sub(r'^\s*#.*$', '', _header(), flags=re.M)
+    protos = re.findall(r'([\w \t\*]+?)\b(hope_\w+)\s*\(([^;{]*?)\)\s*;', hdr)
+    assert len(protos) >= 98 and len({p[1] for p in protos}) == len(protos), len(protos)
+    assert {p[1] for p in protos} == set(_lib.EXPORTS)
+    ints = {'int': (4, True), 'int32_t': (4, True), 'uint32_t': (4, False), 'int64_t': (8, True), 'uint64_t': (8, False),
+            'size_t': (ctypes.sizeof(ctypes.c_size_t), False)}
+
+    def agrees(param, ct):
+        words = param.replace('*', ' * ').split()
+        if '*' in words:
+            return ct in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ct, ctypes._Pointer)
+        base = [w for w in words[:-1] if w != 'const']
+        assert len(base) == 1 and (base[0] in ints or base[0] == 'double'), f'unknown parameter kind: {param!r}'
+        if base[0] == 'double':
+            return ct is ctypes.c_double
+        size, signed = ints[base[0]]
+        return issubclass(ct, ctypes._SimpleCData) and ct._type_ in 'iIlLqQ' and ctypes.sizeof(ct) == size and (ct(-1).value < 0) == signed
+
+    for ret, name, params in protos:
+        restype, argtypes = _lib.PROTOTYPES[name]
+        ret = ' '.join(ret.replace('*', ' * ').split())
+        assert (ret, restype) in (('int', ctypes.c_int), ('const char *', ctypes.c_char_p)), (name, ret, restype)
+        params = [] if params.strip() == 'void' else [p.strip() for p in params.split(',')]
+        assert len(params) == len(argtypes), (name, params, argtypes)
+        for i, (p, ct) in enumerate(zip(params, argtypes)):
+            assert agrees(p, ct), (name, i, p, ct)
+    L = _lib.load_library()                                 # and the table is what the loaded functions carry
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == list(argtypes), name
+
+
+def test_constants_mirror_the_header():
+    """every upper-case number of _lib equals its HOPE_ define; KERNELS is the HOPE_K_ order; the constants without a public define are
+    listed here, each with the internal definition it restates"""
+    from hope_amd import _lib
+    defines = {m.group(1): _c_number(m.group(2)) for m in re.finditer(r'^[ \t]*#define[ \t]+HOPE_(\w+)[ \t]+([^\n]+?)[ \t]*$', _header(), flags=re.M)}
+    numbers = {k: v for k, v in vars(_lib).items() if k.isupper() and isinstance(v, (int, float)) and not isinstance(v, bool)}
+    assert 'ABI_VERSION' in numbers and 'CURRICULUM_LIST_LEN' in numbers and len(numbers) >= 45
+    private = {k for k in numbers if k not in defines}
+    assert private == {'STAGE_NO_CULL', 'STAGE_ONE_SCENE', 'CHOOSE_FALLBACK', 'BUCKET_UNLABELLED'}, private
+    for k in numbers.keys() - private:
+        assert numbers[k] == defines[k] and type(numbers[k]) is type(defines[k]), (k, numbers[k], defines[k])
+    internal = _header(os.path.join('hope_amd', 'csrc', 'hope_internal.h'))
+    for k in ('STAGE_NO_CULL', 'STAGE_ONE_SCENE'):
+        assert numbers[k] == _c_number(re.search(r'constexpr\s+uint32_t\s+%s\s*=\s*([^;]+);' % k, internal).group(1)), k
+    for k, macro, name in (('CHOOSE_FALLBACK', 'CH_FALLBACK', 'hope_chooser_core.h'), ('BUCKET_UNLABELLED', 'CW_UNLABELLED', 'hope_curriculum_core.h')):
+        text = _header(os.path.join('hope_amd', 'csrc', name))
+        assert numbers[k] == _c_number(re.search(r'^[ \t]*#define[ \t]+%s[ \t]+([^\n]+?)[ \t]*$' % macro, text, flags=re.M).group(1)), k
+    # the comment behind each HOPE_K_ define names the kernel
+    kernels = {int(i): k for i, k in re.findall(r'#define[ \t]+HOPE_K_\w+[ \t]+(\d+)[ \t]*/\*[ \t]*(k_\w+)', _header(keep_comments=True))}
+    assert len(_lib.KERNELS) == defines['N_KERNELS'] == len(kernels)
+    assert list(_lib.KERNELS) == [kernels[i] for i in range(len(kernels))]
+
+
+def test_structures_mirror_the_header():
+    """field names, in order, of the three ctypes.Structure mirrors"""
+    from hope_amd import _lib
+    hdr = _header()
+    for cls, struct in ((_lib.StepOut, 'hope_step_out'), (_lib.CurriculumParams, 'hope_curriculum_params'), (_lib.ObsNormState, 'hope_obsnorm_state')):
+        body = re.search(r'typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;' % (struct, struct), hdr, flags=re.S).group(1)
+        fields = [re.search(r'(\w+)\s*(\[[^\]]*\]\s*)*$', d.strip()).group(1) for d in re.split(r'[;,]', body) if d.strip()]      # (`double a[N], b[N];`)
+        assert fields == [f[0] for f in cls._fields_], (struct, fields)
+
+
 def test_environment_variables_are_the_documented_ones():
     """the library reads exactly the environment variables that include/hope_env.h documents, each by a literal name."""
     csrc = os.path.join(ROOT, 'hope_amd', 'csrc')

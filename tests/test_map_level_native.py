@@ -130,7 +130,7 @@ def test_host_entry_rejects_misuse(fresh):
     assert call() == 0
     for kw in (dict(n=0), dict(n=-3), dict(mo=0), dict(mo=256), dict(level_p=None), dict(start_p=None)):
         assert call(**kw) == -1, kw                                            # HOPE_EINVAL
-    with pytest.raises(ValueError):
+    with pytest.raises(L.HopeError):
         M.get_map_levels_host(start, dest, verts[:, :, :3], nob)
 
 
