@@ -26,6 +26,7 @@ PLAN_STATE_WORDS, PLAN_STEP_RATIO, PLAN_FORCED, PLAN_NO_POP = 6, 1.25, 0x1, 0x2
 CHOOSE_NOMASK, CHOOSE_FIXED, CHOOSE_FALLBACK = 64, 128, 10     # flag bits of the chooser's index output; the fixed index
 OBSNORM_LIDAR, OBSNORM_TARGET, OBSNORM_COLS, OBSNORM_UPDATE, OBSNORM_NORMALIZE = 120, 5, 125, 0x1, 0x2
 GAE_SUMS, GAE_NORMALIZE, GAE_MAX_T = 0x1, 0x2, 4096
+RING_MAX_T, RING_MAX_BATCH = 4096, 1 << 20
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
 
@@ -55,6 +56,19 @@ class CurriculumParams(C.Structure):
 class ObsNormState(C.Structure):
     """hope_obsnorm_state: the statistics as the host twin hope_obsnorm_host holds them (zero to start)"""
     _fields_ = [('n_state', C.c_int64), ('mean', C.c_double * OBSNORM_COLS), ('S', C.c_double * OBSNORM_COLS), ('std', C.c_double * OBSNORM_COLS)]
+
+
+class Ring(C.Structure):
+    """hope_ring_t: the transition ring's tensors (float32, contiguous) and extents; `ring_desc` builds one from torch tensors"""
+    _fields_ = [('lidar', C.c_void_p), ('target', C.c_void_p), ('action_mask', C.c_void_p), ('action', C.c_void_p), ('log_prob', C.c_void_p),
+                ('reward', C.c_void_p), ('done', C.c_void_p), ('n', C.c_int32), ('T', C.c_int32)]
+
+
+class RingBatch(C.Structure):
+    """hope_ring_batch_t: the tensors a sampled batch goes to; `ring_batch_desc` builds one"""
+    _fields_ = [('obs_lidar', C.c_void_p), ('obs_target', C.c_void_p), ('obs_mask', C.c_void_p), ('next_lidar', C.c_void_p),
+                ('next_target', C.c_void_p), ('next_mask', C.c_void_p), ('action', C.c_void_p), ('reward', C.c_void_p), ('done', C.c_void_p),
+                ('idx', C.c_void_p)]
 
 
 # the prototypes of include/hope_env.h, one entry per exported call: name -> (return type, parameter types).  The parameter kinds:
@@ -158,6 +172,14 @@ PROTOTYPES = {
     'hope_env_adv_normalize': (I, [P, P, I64, P, P, P]),
     'hope_gae_host': (I, [P] * 5 + [I64, I64, D, D, U32] + [P] * 4),
     'hope_adv_normalize_host': (I, [P, I64, P, P, P]),
+    'hope_env_ring_enable': (I, [P]),
+    'hope_env_ring_disable': (I, [P]),
+    'hope_env_ring_before': (I, [P, C.POINTER(Ring), I] + [P] * 6),
+    'hope_env_ring_after': (I, [P, C.POINTER(Ring), I, P, I] + [P] * 5),
+    'hope_env_ring_sample': (I, [P, C.POINTER(Ring), I, I, I, P, P, U64, U64, P, P, P, C.POINTER(RingBatch), P]),
+    'hope_ring_before_host': (I, [C.POINTER(Ring), I] + [P] * 5),
+    'hope_ring_after_host': (I, [C.POINTER(Ring), I, P, I] + [P] * 4),
+    'hope_ring_sample_host': (I, [C.POINTER(Ring), I, I, I64, P, P, U64, U64, P, P, P, C.POINTER(RingBatch)]),
     'hope_env_num_scenes': (I, [P]),
     'hope_env_max_obstacles': (I, [P]),
     'hope_env_device_arch': (S, [P]),
@@ -241,3 +263,29 @@ def array_arg(call, name, x, dtype, shape, optional=False):
         return a
     got = f'{a.dtype.name} {list(a.shape)}' if a is not None else 'None' if x is None else type(x).__name__
     raise HopeError(f"{call}: {name} must be {np.dtype(dtype).name} {str(list(shape)).replace('None', '?')}, got {got}")
+
+
+_RING_FIELDS = (('lidar', LIDAR_NUM), ('target', TARGET_DIM), ('action_mask', N_ACTION), ('action', 2), ('log_prob', 2), ('reward', None), ('done', None))
+_BATCH_FIELDS = (('obs_lidar', LIDAR_NUM), ('obs_target', TARGET_DIM), ('obs_mask', N_ACTION), ('next_lidar', LIDAR_NUM), ('next_target', TARGET_DIM),
+                 ('next_mask', N_ACTION), ('action', 2), ('reward', None), ('done', None))
+
+
+def ring_desc(call, device, n, horizon, **tensors):
+    """the hope_ring_t over the float32 tensors lidar, target, action_mask, action, log_prob [n, T, width], reward, done [n, T], each
+    checked by tensor_arg.  The struct holds addresses only: keep the tensors alive as long as it is used."""
+    import torch
+    r = Ring(n=n, T=horizon)
+    for name, width in _RING_FIELDS:
+        shape = (n, horizon) if width is None else (n, horizon, width)
+        setattr(r, name, tensor_arg(call, name, tensors.get(name), torch.float32, shape, device).value)
+    return r
+
+
+def ring_batch_desc(call, device, batch, **tensors):
+    """the hope_ring_batch_t over float32 tensors [batch, width] / [batch] and idx int32 [batch, 3], each checked by tensor_arg"""
+    import torch
+    o = RingBatch()
+    for name, width in _BATCH_FIELDS:
+        setattr(o, name, tensor_arg(call, name, tensors.get(name), torch.float32, (batch,) if width is None else (batch, width), device).value)
+    o.idx = tensor_arg(call, 'idx', tensors.get('idx'), torch.int32, (batch, 3), device).value
+    return o

@@ -578,6 +578,60 @@ class ParkingBatch:
         L.check(self.lib.hope_env_adv_normalize(self.h, ap, adv.numel(), sp, op, self._stream()), 'hope_env_adv_normalize')
         return out
 
+    # -- the transition ring on the device (hope_env.h; rule: csrc/hope_ring_core.h) ------------------------------------
+    def enable_ring(self):
+        """TransitionRing's push, the episode / success / reward tally of the step and the SAC batch as four kernels (k_ring_before,
+        k_ring_after, k_ring_tally, k_ring_sample) over the caller's ring tensors (rollout.DeviceTransitionRing owns a set).  Off by
+        default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_ring_enable(self.h), 'hope_env_ring_enable')
+        return self
+
+    def disable_ring(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_ring_disable(self.h), 'hope_env_ring_disable')
+        return self
+
+    @staticmethod
+    def _ring_arg(call, ring):
+        if not isinstance(ring, L.Ring):
+            raise L.HopeError(f'{call}: ring must be a hope_amd._lib.Ring (ring_desc), got {type(ring).__name__}')
+        return ring
+
+    def ring_before(self, ring, t, lidar, target, mask, action, log_prob):
+        """the before half of column t: lidar [n, 120], target [n, 5], mask [n, 42], action [n, 2], log_prob [n, 2], float32, contiguous,
+        n = the ring's; `ring` is a `_lib.Ring` (ring_desc).  One launch on the current stream, no host synchronisation."""
+        r, n = self._ring_arg('hope_env_ring_before', ring), ring.n
+        arg = partial(L.tensor_arg, 'hope_env_ring_before', dtype=torch.float32, device=self.device)
+        L.check(self.lib.hope_env_ring_before(self.h, r, int(t), arg('lidar', lidar, shape=(n, L.LIDAR_NUM)), arg('target', target, shape=(n, L.TARGET_DIM)),
+                                              arg('mask', mask, shape=(n, L.N_ACTION)), arg('action', action, shape=(n, 2)),
+                                              arg('log_prob', log_prob, shape=(n, 2)), self._stream()), 'hope_env_ring_before')
+
+    def ring_after(self, ring, t, reward, done, status=None, counts=None, reward_sum=None):
+        """the after half of column t: reward [n] float32 / float64, done [n] uint8 / bool.  status int32 [n], counts int64 [2] and
+        reward_sum float64 [1] go together: then the step is tallied into them (two launches), otherwise one launch."""
+        r, n = self._ring_arg('hope_env_ring_after', ring), ring.n
+        arg = partial(L.tensor_arg, 'hope_env_ring_after', device=self.device)
+        rp = arg('reward', reward, (torch.float32, torch.float64), (n,))
+        dp = arg('done', done, (torch.uint8, torch.bool), (n,))
+        sp, cp = arg('status', status, torch.int32, (n,), optional=True), arg('counts', counts, torch.int64, (2,), optional=True)
+        tp = arg('reward_sum', reward_sum, torch.float64, (1,), optional=True)
+        L.check(self.lib.hope_env_ring_after(self.h, r, int(t), rp, int(reward.dtype == torch.float64), dp, sp, cp, tp, self._stream()), 'hope_env_ring_after')
+
+    def ring_sample(self, ring, head, size, batch, out, last_lidar, last_target, last_mask, s=None, j=None, seed=0, counter=0):
+        """`batch` transitions into `out` (a `_lib.RingBatch`, ring_batch_desc) from the ring's `size` newest columns; s, j int32
+        [batch] (scene, age; 0 = the oldest column), or both None: counter-based draws keyed by (seed, counter, item).  last_*: the
+        float32 observation after the newest column.  One launch on the current stream, no host synchronisation."""
+        r, n = self._ring_arg('hope_env_ring_sample', ring), ring.n
+        if not isinstance(out, L.RingBatch):
+            raise L.HopeError(f'hope_env_ring_sample: out must be a hope_amd._lib.RingBatch (ring_batch_desc), got {type(out).__name__}')
+        arg = partial(L.tensor_arg, 'hope_env_ring_sample', device=self.device)
+        sp, jp = arg('s', s, torch.int32, (batch,), optional=True), arg('j', j, torch.int32, (batch,), optional=True)
+        lp, tp = arg('last_lidar', last_lidar, torch.float32, (n, L.LIDAR_NUM)), arg('last_target', last_target, torch.float32, (n, L.TARGET_DIM))
+        mp = arg('last_mask', last_mask, torch.float32, (n, L.N_ACTION))
+        L.check(self.lib.hope_env_ring_sample(self.h, r, int(head), int(size), int(batch), sp, jp, L.seed64(seed), L.seed64(counter), lp, tp, mp, out,
+                                              self._stream()), 'hope_env_ring_sample')
+
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
     def enable_eval_tracker(self):
         """eval()'s per-episode tally (eval_utils.py:35-57) as device state of the handle (80 B per scene) and three kernels:

@@ -1,5 +1,5 @@
 // hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
-// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block -- and their host twins.  They share nothing with the
+// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring -- and their host twins.  They share nothing with the
 // step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include "hope_obsnorm_kernel.h"
 #include "hope_evaltrack_kernel.h"
 #include "hope_gae_kernel.h"
+#include "hope_ring_kernel.h"
 
 using namespace hope;
 
@@ -19,6 +20,7 @@ using namespace hope;
 #define OBSNORM_ON(h, name) HOPE_NEED((h)->onorm.on, name, "the normalisation is off (hope_env_obsnorm_enable first)")
 #define EVAL_ON(h, name) HOPE_NEED((h)->evalt.on, name, "the evaluation tracker is off (hope_env_eval_enable first)")
 #define GAE_ON(h, name) HOPE_NEED((h)->gae.on, name, "the advantage block is off (hope_env_gae_enable first)")
+#define RING_ON(h, name) HOPE_NEED((h)->ring.on, name, "the transition ring is off (hope_env_ring_enable first)")
 
 // What every hope_env_*_enable does with a feature's device buffer: allocate it if absent, fill it (from `src`, or with zeros) and
 // wait.  On any failure the buffer is freed and *buf is null; the caller then puts the feature's struct back to "off" (*_free).
@@ -75,6 +77,27 @@ void hope::gae_free(hope_env_t* h) {
     if (h->gae.part) hipFree(h->gae.part);
     if (h->gae.sums) hipFree(h->gae.sums);
     h->gae = hope_env::Gae{};
+}
+
+void hope::ring_free(hope_env_t* h) {
+    if (h->ring.part) hipFree(h->ring.part);
+    if (h->ring.cnt) hipFree(h->ring.cnt);
+    h->ring = hope_env::Ring{};
+}
+
+// the ring descriptor of a hope_env_ring_* call `name`: every tensor there and aligned to its element, n and T in range
+#define RING_ARG(h, R, name)                                                                                                                  \
+    do {                                                                                                                                      \
+        if (!(R)) return fail(HOPE_EINVAL, name ": null ring");                                                                               \
+        if (!rg_ring_ok_ptrs(R)) return fail(HOPE_EINVAL, name ": null tensor in the ring");                                                  \
+        if (ring_bits(R) & 3) return fail(HOPE_EINVAL, name ": misaligned buffer (the ring's float32 tensors 4 bytes)");                      \
+        if ((R)->n < 1 || (R)->n > (h)->n) return fail(HOPE_EINVAL, name ": the ring's n must be 1 .. the handle's scenes");                  \
+        if ((R)->T < 1 || (R)->T > HOPE_RING_MAX_T) return fail(HOPE_EINVAL, name ": the ring's T must be 1 .. " + std::to_string(HOPE_RING_MAX_T)); \
+    } while (0)
+static bool rg_ring_ok_ptrs(const hope_ring_t* R) { return R->lidar && R->target && R->action_mask && R->action && R->log_prob && R->reward && R->done; }
+static uintptr_t ring_bits(const hope_ring_t* R) {
+    return (uintptr_t)R->lidar | (uintptr_t)R->target | (uintptr_t)R->action_mask | (uintptr_t)R->action | (uintptr_t)R->log_prob | (uintptr_t)R->reward |
+           (uintptr_t)R->done;
 }
 
 template <class T>
@@ -489,6 +512,112 @@ int hope_gae_host(const float* reward, const float* done, const float* value, co
 int hope_adv_normalize_host(const float* adv, int64_t count, const double* sums, float* out, float* mean_std) {
     const int rc = ga_normalize_host(adv, count, sums, out, mean_std);
     if (rc != HOPE_OK) return fail(rc, "hope_adv_normalize_host: bad argument (null sums, a negative count, or a null adv / out with count > 0)");
+    return HOPE_OK;
+}
+
+// ---- the transition ring (include/hope_env.h; kernels: hope_ring_kernel.h, rule: hope_ring_core.h) ----
+int hope_env_ring_enable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_ring_enable");
+    if (h->ring.on) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    const size_t nk = (size_t)ga_chunks(h->n);
+    int rc = device_buffer("hope_env_ring_enable", &h->ring.part, nk * sizeof(double));
+    if (rc == HOPE_OK) rc = device_buffer("hope_env_ring_enable", &h->ring.cnt, nk * 2 * sizeof(int32_t));
+    if (rc != HOPE_OK) { ring_free(h); return rc; }
+    h->ring.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_ring_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_ring_disable");
+    return feature_disable(h, ring_free);
+}
+
+int hope_env_ring_before(hope_env_t* h, const hope_ring_t* ring, int t, const float* lidar, const float* target, const float* mask, const float* action,
+                         const float* log_prob, void* stream) {
+    HOPE_ENTER(h, "hope_env_ring_before");
+    RING_ON(h, "hope_env_ring_before");
+    RING_ARG(h, ring, "hope_env_ring_before");
+    if (t < 0 || t >= ring->T) return fail(HOPE_EINVAL, "hope_env_ring_before: t must be 0 .. T - 1");
+    if (!lidar || !target || !mask || !action || !log_prob) return fail(HOPE_EINVAL, "hope_env_ring_before: null lidar / target / mask / action / log_prob");
+    const uintptr_t in = (uintptr_t)lidar | (uintptr_t)target | (uintptr_t)mask | (uintptr_t)action | (uintptr_t)log_prob;
+    if (in & 3) return fail(HOPE_EINVAL, "hope_env_ring_before: misaligned buffer (float32 tensors 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const uintptr_t a16 = (uintptr_t)lidar | (uintptr_t)ring->lidar;
+    const uintptr_t a8 = (uintptr_t)mask | (uintptr_t)action | (uintptr_t)log_prob | (uintptr_t)ring->action_mask | (uintptr_t)ring->action | (uintptr_t)ring->log_prob;
+    const dim3 grid((unsigned)((ring->n + RB_SCENES - 1) / RB_SCENES)), block(64);
+    if (!(a16 & 15) && !(a8 & 7)) hipLaunchKernelGGL(k_ring_before<4>, grid, block, 0, (hipStream_t)stream, *ring, t, lidar, target, mask, action, log_prob);
+    else hipLaunchKernelGGL(k_ring_before<1>, grid, block, 0, (hipStream_t)stream, *ring, t, lidar, target, mask, action, log_prob);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_ring_after(hope_env_t* h, const hope_ring_t* ring, int t, const void* reward, int reward_f64, const uint8_t* done, const int32_t* status,
+                        int64_t* counts, double* reward_sum, void* stream) {
+    HOPE_ENTER(h, "hope_env_ring_after");
+    RING_ON(h, "hope_env_ring_after");
+    RING_ARG(h, ring, "hope_env_ring_after");
+    if (t < 0 || t >= ring->T) return fail(HOPE_EINVAL, "hope_env_ring_after: t must be 0 .. T - 1");
+    if (!reward || !done) return fail(HOPE_EINVAL, "hope_env_ring_after: null reward / done");
+    const bool tally = status || counts || reward_sum;
+    if (tally && (!status || !counts || !reward_sum)) return fail(HOPE_EINVAL, "hope_env_ring_after: status, counts and reward_sum go together");
+    if (((uintptr_t)reward & (reward_f64 ? 7 : 3)) || ((uintptr_t)status & 3) || ((uintptr_t)counts & 7) || ((uintptr_t)reward_sum & 7))
+        return fail(HOPE_EINVAL, "hope_env_ring_after: misaligned buffer (reward and status their element, counts and reward_sum 8 bytes)");
+    HOPE_ON_DEVICE(h);
+    const long long nk = ga_chunks(ring->n);                      // <= the partials' room: n <= N
+    hipLaunchKernelGGL(k_ring_after, dim3((unsigned)nk), dim3(64), 0, (hipStream_t)stream, *ring, t, reward, reward_f64 ? 1 : 0, done, status, nk,
+                       tally ? h->ring.part : nullptr, tally ? h->ring.cnt : nullptr);
+    if (tally)
+        hipLaunchKernelGGL(k_ring_tally, dim3(1), dim3(64), 0, (hipStream_t)stream, nk, h->ring.part, (const int32_t*)h->ring.cnt, (long long*)counts, reward_sum);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_ring_sample(hope_env_t* h, const hope_ring_t* ring, int head, int size, int batch, const int32_t* s, const int32_t* j, uint64_t seed,
+                         uint64_t counter, const float* last_lidar, const float* last_target, const float* last_mask, const hope_ring_batch_t* out, void* stream) {
+    HOPE_ENTER(h, "hope_env_ring_sample");
+    RING_ON(h, "hope_env_ring_sample");
+    RING_ARG(h, ring, "hope_env_ring_sample");
+    if (head < 0 || head >= ring->T) return fail(HOPE_EINVAL, "hope_env_ring_sample: head must be 0 .. T - 1");
+    if (size < 1 || size > ring->T) return fail(HOPE_EINVAL, "hope_env_ring_sample: size must be 1 .. T");
+    if (batch < 1 || batch > HOPE_RING_MAX_BATCH) return fail(HOPE_EINVAL, "hope_env_ring_sample: batch must be 1 .. " + std::to_string(HOPE_RING_MAX_BATCH));
+    if ((s != nullptr) != (j != nullptr)) return fail(HOPE_EINVAL, "hope_env_ring_sample: s and j go together");
+    if (!last_lidar || !last_target || !last_mask) return fail(HOPE_EINVAL, "hope_env_ring_sample: null last_lidar / last_target / last_mask");
+    if (!out) return fail(HOPE_EINVAL, "hope_env_ring_sample: null out");
+    if (!rg_batch_ok(out)) return fail(HOPE_EINVAL, "hope_env_ring_sample: null tensor in out");
+    const uintptr_t all = (uintptr_t)s | (uintptr_t)j | (uintptr_t)last_lidar | (uintptr_t)last_target | (uintptr_t)last_mask | (uintptr_t)out->obs_lidar |
+                          (uintptr_t)out->obs_target | (uintptr_t)out->obs_mask | (uintptr_t)out->next_lidar | (uintptr_t)out->next_target |
+                          (uintptr_t)out->next_mask | (uintptr_t)out->action | (uintptr_t)out->reward | (uintptr_t)out->done | (uintptr_t)out->idx;
+    if (all & 3) return fail(HOPE_EINVAL, "hope_env_ring_sample: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_ring_sample, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, *ring, head, size, s, j, (unsigned long long)seed,
+                       (unsigned long long)counter, last_lidar, last_target, last_mask, *out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_ring_before_host(const hope_ring_t* ring, int t, const float* lidar, const float* target, const float* mask, const float* action,
+                          const float* log_prob) {
+    const int rc = rg_before_host(ring, t, lidar, target, mask, action, log_prob);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_ring_before_host: bad argument (a null ring, tensor or input, n or T < 1, or t outside 0 .. T - 1)");
+    return HOPE_OK;
+}
+
+int hope_ring_after_host(const hope_ring_t* ring, int t, const void* reward, int reward_f64, const uint8_t* done, const int32_t* status, int64_t* counts,
+                         double* reward_sum) {
+    const int rc = rg_after_host(ring, t, reward, reward_f64, done, status, counts, reward_sum);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_ring_after_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_ring_after_host: bad argument (a null ring, tensor, reward or done, n or T < 1, t outside 0 .. T - 1, or status / counts / reward_sum not together)");
+    return HOPE_OK;
+}
+
+int hope_ring_sample_host(const hope_ring_t* ring, int head, int size, int64_t batch, const int32_t* s, const int32_t* j, uint64_t seed, uint64_t counter,
+                          const float* last_lidar, const float* last_target, const float* last_mask, const hope_ring_batch_t* out) {
+    const int rc = rg_sample_host(ring, head, size, batch, s, j, seed, counter, last_lidar, last_target, last_mask, out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_ring_sample_host: bad argument (a null ring, tensor, last_* or out, n or T < 1, head outside 0 .. T - 1, size outside 1 .. T, batch < 1, or s without j or the reverse)");
     return HOPE_OK;
 }
 

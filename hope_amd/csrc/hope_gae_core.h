@@ -64,6 +64,18 @@ HM_FN GaMeanStd ga_mean_std(double s0, double s1, double n) {
 }
 HM_FN float ga_apply(float a, GaMeanStd ms) { return (a - ms.m) / (ms.s + GA_EPS); }
 
+/* The two trees of step 2 on the host, in place (hope_ring_core.h sums a step's rewards in the same order):
+ * ga_chunk_tree: the aligned binary tree over one chunk's GA_CHUNK values, the sum ends in c[0];
+ * ga_merge_tree: the aligned binary tree with pass-through over nk chunk partials, the sum ends in p[0]. */
+static inline void ga_chunk_tree(double* c) {
+    for (int h = 1; h < GA_CHUNK; h *= 2)
+        for (int l = 0; l + h < GA_CHUNK; l += 2 * h) c[l] += c[l + h];
+}
+static inline void ga_merge_tree(double* p, int64_t nk) {
+    for (int64_t h = 1; h < nk; h *= 2)                /* level: h = 2^l */
+        for (int64_t i = 0; i + h < nk; i += 2 * h) p[i] += p[i + h];
+}
+
 /* The host twins (layouts as hope_env_gae / hope_env_adv_normalize; no alignment requirements, no upper bound on rows or T).
  * ga_host: delta_out [rows][T] (may be NULL) takes batched_gae's float32 delta; sums_out (may be NULL) the three doubles.  Returns
  * HOPE_OK, HOPE_EINVAL or HOPE_ENOMEM; hope_gae_host forwards to it. */
@@ -102,13 +114,13 @@ static inline int ga_host(const float* reward, const float* done, const float* v
             c0[l] = s0; c1[l] = s1;
         }
         if (!want_sums) continue;
-        for (int h = 1; h < GA_CHUNK; h *= 2)
-            for (int l = 0; l + h < GA_CHUNK; l += 2 * h) { c0[l] += c0[l + h]; c1[l] += c1[l + h]; }
+        ga_chunk_tree(c0);
+        ga_chunk_tree(c1);
         part[k] = c0[0]; part[nk + k] = c1[0];
     }
     if (!want_sums) return HOPE_OK;
-    for (int64_t h = 1; h < nk; h *= 2)                /* level: h = 2^l */
-        for (int64_t i = 0; i + h < nk; i += 2 * h) { part[i] += part[i + h]; part[nk + i] += part[nk + i + h]; }
+    ga_merge_tree(part, nk);
+    ga_merge_tree(part + nk, nk);
     const double sums[3] = {part[0], part[nk], (double)(rows * T)};
     free(part);
     if (sums_out) { sums_out[0] = sums[0]; sums_out[1] = sums[1]; sums_out[2] = sums[2]; }

@@ -20,6 +20,25 @@ namespace hope {
 // x of lane + h (the own value past the wave's end: those lanes' results are never used)
 __device__ __forceinline__ double ga_down(double x, int h) { return __shfl_down(x, (unsigned)h, 64); }
 
+// the chunk's aligned tree over the wave's 64 values: lane 0 ends with the chunk's sum (ga_chunk_tree's order)
+__device__ __forceinline__ double ga_wave_tree(double x) {
+#pragma unroll
+    for (int h = 1; h < GA_CHUNK; h *= 2) x += ga_down(x, h);
+    return x;
+}
+// the aligned tree with pass-through over K planes of nk chunk partials (plane k at part + k nk), level by level and in place, by one
+// wave with a block barrier behind every level (ga_merge_tree's order); plane k's sum ends in part[k nk]
+template <int K>
+__device__ __forceinline__ void ga_merge_wave(double* part, long long nk, int lane) {
+    for (long long h = 1; h < nk; h *= 2) {                       // level: h = 2^l
+        for (long long i = (long long)lane * 2 * h; i + h < nk; i += 128 * h) {
+#pragma unroll
+            for (int k = 0; k < K; k++) part[k * nk + i] += part[k * nk + i + h];
+        }
+        __syncthreads();
+    }
+}
+
 template <int V>
 __global__ __launch_bounds__(64) void k_gae_scan(const float* __restrict__ reward, const float* __restrict__ done, const float* __restrict__ value,
                                                  const float* __restrict__ v_last, const float* __restrict__ value_target, int rows, int T, double gamma,
@@ -60,11 +79,8 @@ __global__ __launch_bounds__(64) void k_gae_scan(const float* __restrict__ rewar
         }
     }
     if (!part) return;                                            // (uniform: a kernel argument)
-#pragma unroll
-    for (int h = 1; h < GA_CHUNK; h *= 2) {
-        s0 += ga_down(s0, h);
-        s1 += ga_down(s1, h);
-    }
+    s0 = ga_wave_tree(s0);
+    s1 = ga_wave_tree(s1);
     if (threadIdx.x == 0 && (long long)blockIdx.x < chunks) {
         part[blockIdx.x] = s0;
         part[chunks + blockIdx.x] = s1;
@@ -73,18 +89,10 @@ __global__ __launch_bounds__(64) void k_gae_scan(const float* __restrict__ rewar
 
 __global__ __launch_bounds__(64) void k_gae_merge(long long nk, double count, double* part, double* __restrict__ sums) {
     const int lane = threadIdx.x;
-    double* p0 = part;
-    double* p1 = part + nk;
-    for (long long h = 1; h < nk; h *= 2) {                       // level: h = 2^l
-        for (long long i = (long long)lane * 2 * h; i + h < nk; i += 128 * h) {
-            p0[i] += p0[i + h];
-            p1[i] += p1[i + h];
-        }
-        __syncthreads();
-    }
+    ga_merge_wave<2>(part, nk, lane);
     if (lane == 0) {
-        sums[0] = p0[0];
-        sums[1] = p1[0];
+        sums[0] = part[0];
+        sums[1] = part[nk];
         sums[2] = count;
     }
 }

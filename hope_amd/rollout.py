@@ -13,8 +13,10 @@ the hybrid controller of src/model/agent/parking_agent.py (replay a found Reeds-
 ParkingBatch's observation tensors are persistent buffers that the next step overwrites in place, so every loop
 copies what it keeps BEFORE stepping.
 """
+import numpy as np
 import torch
 
+from . import _lib as L
 from . import agent_glue as G
 
 
@@ -112,12 +114,16 @@ class TransitionRing:
         return ({k: v[:, idx] for k, v in self.obs.items()}, self.action[:, idx], self.reward[:, idx], self.done[:, idx],
                 self.log_prob[:, idx])
 
-    def sample(self, batch_size, last_obs, generator=None):
+    def sample(self, batch_size, last_obs, generator=None, index=None):
         """uniform (scene, time) transitions like ReplayMemory.sample (:33-35); the observation after the newest column
-        is `last_obs` (the one the agent is about to act on)."""
+        is `last_obs` (the one the agent is about to act on).  index=(s, j): the scene and the age (0: the oldest column) of every
+        item instead of the two draws -- tests feed this ring and DeviceTransitionRing the same choices."""
         idx = self.columns()
-        s = torch.randint(self.n, (batch_size,), device=self.device, generator=generator)
-        j = torch.randint(self.size, (batch_size,), device=self.device, generator=generator)
+        if index is None:
+            s = torch.randint(self.n, (batch_size,), device=self.device, generator=generator)
+            j = torch.randint(self.size, (batch_size,), device=self.device, generator=generator)
+        else:
+            s, j = (torch.as_tensor(x, device=self.device).long() for x in index)
         t = idx[j]
         newest = j == self.size - 1
         tn = idx[torch.clamp(j + 1, max=self.size - 1)]
@@ -133,9 +139,173 @@ class TransitionRing:
         self.head, self.size = 0, 0
 
 
+def _mix64(z):
+    """splitmix64's finaliser over uint64 arrays (hope_chooser_core.h's ch_mix64)"""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def ring_draws(seed, counter, batch, n, size):
+    """the counter-based draws of hope_ring_core.h restated in numpy: -> (s, j) int32 [batch], the scene (0 .. n-1) and the age
+    (0 .. size-1) of every batch item for (seed, counter)"""
+    with np.errstate(over='ignore'):
+        key = _mix64(_mix64(np.array([int(seed) & (2 ** 64 - 1)], dtype=np.uint64)) ^ np.uint64(int(counter) & (2 ** 64 - 1)))
+        b = np.arange(batch, dtype=np.uint64)
+        out = []
+        for d, rng in ((0, n), (1, size)):
+            x = _mix64(key ^ (np.uint64(2) * b + np.uint64(d)))
+            out.append((((x >> np.uint64(32)) * np.uint64(rng)) >> np.uint64(32)).astype(np.int32))
+    return out[0], out[1]
+
+
+class DeviceTransitionRing:
+    """TransitionRing's surface over the library's transition ring (include/hope_env.h "the transition ring"; rule:
+    csrc/hope_ring_core.h): write_before is ONE k_ring_before launch, write_after one k_ring_after launch -- with `status` two, and
+    the step's episodes, successes and reward sum are tallied into `counts` (int64 [2]) and `reward_sum` (float64 [1]) on the
+    device -- and sample one k_ring_sample launch.  The tensors are this object's, in TransitionRing's layout, and hold the same
+    words.  The image key stays torch code (one large copy_ per push, a gather from `idx` per batch).  On an env without the library
+    (CPU tensors; tests/fake_env.OracleEnv) the same runs on the host through hope_ring_*_host: the rule is one source for both.
+    sample's draws are counter-based, keyed by `seed` and the number of draws so far (`counter`), not torch.randint's stream; the
+    tensors it returns for a batch size are persistent and overwritten by the next call with that size."""
+    CORE = ('lidar', 'target', 'action_mask')
+
+    def __init__(self, env, horizon, keys, seed=0, img_shape=(3, 64, 64)):
+        self.env, self.n, self.T, self.device = env, env.n, horizon, torch.device(env.device)
+        missing = [k for k in self.CORE if k not in keys]
+        if missing:
+            raise ValueError(f'DeviceTransitionRing needs the observation keys {self.CORE}, missing {missing}')
+        n, dev = self.n, self.device
+        shp = {'lidar': (120,), 'target': (5,), 'action_mask': (42,), 'img': tuple(img_shape)}
+        self.obs = {k: torch.zeros((n, horizon) + shp[k], dtype=torch.uint8 if k == 'img' else torch.float32, device=dev) for k in keys}
+        self.action = torch.zeros((n, horizon, 2), dtype=torch.float32, device=dev)
+        self.log_prob = torch.zeros((n, horizon, 2), dtype=torch.float32, device=dev)
+        self.reward = torch.zeros((n, horizon), dtype=torch.float32, device=dev)
+        self.done = torch.zeros((n, horizon), dtype=torch.float32, device=dev)
+        self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.reward_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.head, self.size = 0, 0
+        self.seed, self.counter = seed, 0
+        self.on_device = hasattr(env, 'ring_before')
+        if self.on_device:
+            env.enable_ring()
+        else:
+            self._lib = G._host_library(dev, 'ring_before')
+        self._desc = L.ring_desc('DeviceTransitionRing', dev, n, horizon, lidar=self.obs['lidar'], target=self.obs['target'],
+                                 action_mask=self.obs['action_mask'], action=self.action, log_prob=self.log_prob, reward=self.reward, done=self.done)
+        self._out = {}                                # batch size -> (tensors, descriptor)
+
+    @staticmethod
+    def _f32(x):
+        return x.detach().to(torch.float32).contiguous()
+
+    def write_before(self, nobs, action, log_prob):
+        t = self.head
+        x = [self._f32(nobs[k]) for k in self.CORE] + [self._f32(action), self._f32(log_prob)]
+        if self.on_device:
+            self.env.ring_before(self._desc, t, *x)
+        else:
+            arg = partial_arg('hope_ring_before_host', self.device)
+            ptrs = [arg(k, v, torch.float32, (self.n, w)) for k, v, w in zip(('lidar', 'target', 'mask', 'action', 'log_prob'), x, (120, 5, 42, 2, 2))]
+            L.check(self._lib.hope_ring_before_host(self._desc, t, *ptrs), 'hope_ring_before_host')
+        if 'img' in self.obs:
+            self.obs['img'][:, t].copy_(nobs['img'])
+
+    def write_after(self, reward, done, status=None):
+        """status (int32 [n], the env's): the step is also tallied into `counts` and `reward_sum`"""
+        t = self.head
+        reward = reward.detach().contiguous()
+        if reward.dtype not in (torch.float32, torch.float64):
+            reward = reward.to(torch.float32)
+        done = done.detach().contiguous()
+        if done.dtype not in (torch.uint8, torch.bool):
+            done = (done != 0).to(torch.uint8)
+        tally = (None, None, None) if status is None else (status.detach().to(torch.int32).contiguous(), self.counts, self.reward_sum)
+        if self.on_device:
+            self.env.ring_after(self._desc, t, reward, done, *tally)
+        else:
+            arg = partial_arg('hope_ring_after_host', self.device)
+            ptrs = [arg('status', tally[0], torch.int32, (self.n,), optional=True), arg('counts', tally[1], torch.int64, (2,), optional=True),
+                    arg('reward_sum', tally[2], torch.float64, (1,), optional=True)]
+            L.check(self._lib.hope_ring_after_host(self._desc, t, arg('reward', reward, (torch.float32, torch.float64), (self.n,)),
+                                                   int(reward.dtype == torch.float64), arg('done', done, (torch.uint8, torch.bool), (self.n,)), *ptrs),
+                    'hope_ring_after_host')
+        self.head = (t + 1) % self.T
+        self.size = min(self.size + 1, self.T)
+
+    columns = TransitionRing.columns
+    ordered = TransitionRing.ordered
+
+    def _outputs(self, batch):
+        if batch not in self._out:
+            dev, f = self.device, torch.float32
+            t = {'obs_lidar': torch.zeros((batch, 120), dtype=f, device=dev), 'obs_target': torch.zeros((batch, 5), dtype=f, device=dev),
+                 'obs_mask': torch.zeros((batch, 42), dtype=f, device=dev), 'next_lidar': torch.zeros((batch, 120), dtype=f, device=dev),
+                 'next_target': torch.zeros((batch, 5), dtype=f, device=dev), 'next_mask': torch.zeros((batch, 42), dtype=f, device=dev),
+                 'action': torch.zeros((batch, 2), dtype=f, device=dev), 'reward': torch.zeros(batch, dtype=f, device=dev),
+                 'done': torch.zeros(batch, dtype=f, device=dev), 'idx': torch.zeros((batch, 3), dtype=torch.int32, device=dev)}
+            self._out[batch] = (t, L.ring_batch_desc('DeviceTransitionRing.sample', dev, batch, **t))
+        return self._out[batch]
+
+    def sample(self, batch_size, last_obs, generator=None, index=None):
+        """TransitionRing.sample's dict plus 'idx' (int32 [batch, 3]: scene, column, next column or -1 where next_obs is last_obs).
+        index=(s, j): the scene and the age of every item (a pair out of range gives a zero row with idx -1); None: the counter-based
+        draws of `ring_draws(seed, counter, ...)`, and the counter moves on.  `generator` is not used."""
+        if self.size < 1:
+            raise ValueError('sample from an empty ring')
+        t, desc = self._outputs(batch_size)
+        last = [self._f32(last_obs[k]) for k in self.CORE]
+        if index is None:
+            s = j = None
+            counter = self.counter
+            self.counter += 1
+        else:
+            s, j = (torch.as_tensor(x, device=self.device).to(torch.int32).contiguous() for x in index)
+            counter = 0
+        if self.on_device:
+            self.env.ring_sample(self._desc, self.head, self.size, batch_size, desc, *last, s=s, j=j, seed=self.seed, counter=counter)
+        else:
+            arg = partial_arg('hope_ring_sample_host', self.device)
+            ptrs = [arg(k, v, torch.float32, (self.n, w)) for k, v, w in zip(('last_lidar', 'last_target', 'last_mask'), last, (120, 5, 42))]
+            L.check(self._lib.hope_ring_sample_host(self._desc, self.head, self.size, batch_size, arg('s', s, torch.int32, (batch_size,), optional=True),
+                                                    arg('j', j, torch.int32, (batch_size,), optional=True), L.seed64(self.seed), L.seed64(counter), *ptrs, desc),
+                    'hope_ring_sample_host')
+        obs = {'lidar': t['obs_lidar'], 'target': t['obs_target'], 'action_mask': t['obs_mask']}
+        nxt = {'lidar': t['next_lidar'], 'target': t['next_target'], 'action_mask': t['next_mask']}
+        if 'img' in self.obs:                         # the image key: gathered in torch from the kernel's indices
+            ix = t['idx'].long()
+            sc, tc, tn = ix[:, 0].clamp(min=0), ix[:, 1].clamp(min=0), ix[:, 2]
+            img = self.obs['img']
+            obs['img'] = img[sc, tc]
+            newest = ((tn < 0) & (ix[:, 0] >= 0)).view(-1, 1, 1, 1)
+            nxt['img'] = torch.where(newest, last_obs['img'][sc].to(img.dtype), img[sc, tn.clamp(min=0)])
+        return {'obs': {k: obs[k] for k in self.obs}, 'next_obs': {k: nxt[k] for k in self.obs}, 'action': t['action'], 'reward': t['reward'],
+                'done': t['done'], 'idx': t['idx']}
+
+    def clear(self):
+        self.head, self.size = 0, 0
+
+
+def partial_arg(call, device):
+    """_lib.tensor_arg for one call and device: arg(name, x, dtype, shape, optional=False)"""
+    def arg(name, x, dtype, shape, optional=False):
+        return L.tensor_arg(call, name, x, dtype, shape, device, optional)
+    return arg
+
+
+def make_ring(ring, env, horizon, keys, seed):
+    """the trainers' `ring` argument: None -- today's TransitionRing (torch copies and gathers); 'device' -- a DeviceTransitionRing"""
+    if ring is None:
+        return TransitionRing(env.n, horizon, keys, env.device)
+    if ring != 'device':
+        raise ValueError(f"ring must be None or 'device', not {ring!r}")
+    return DeviceTransitionRing(env, horizon, keys, seed=seed)
+
+
 class HopeRollout:
     def __init__(self, env, agent, horizon, use_mask=True, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None,
-                 defer_rs=True, curriculum=None, chooser=None, obs_norm=None):
+                 defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None):
         """defer_rs: step the env with two completion points (HOPE_DEFER_RS): the next policy forward is enqueued as soon as the
         observation is written, the planner reads rs_word / rs_lengths (after ParkingBatch.wait_rs) just before its override --
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
@@ -159,7 +329,11 @@ class HopeRollout:
         obs_norm: None -- the agent's BatchedStateNorm (torch code: `agent.observe` after the step, `_norm_obs` in the next `act`);
         'device' -- the agent's state_norm is swapped for an agent_glue.DeviceStateNorm that takes over its statistics, and the two
         become ONE update_and_normalize call after the step (three launches), whose float32 result is handed to the next `act`.  The
-        fold's arithmetic order is fixed there, so the statistics differ from the torch path's in the last bits."""
+        fold's arithmetic order is fixed there, so the statistics differ from the torch path's in the last bits.
+        ring: None -- TransitionRing: the push is seven strided copy_ launches, the tally of episodes, successes and rewards about
+        eight more, a SAC batch about thirty; 'device' -- DeviceTransitionRing: one launch for the before half, two for the after half
+        with the tally in it (the totals live in the ring: `ring.counts`, `ring.reward_sum`), one for a batch (counter-based draws
+        keyed by `seed`, not torch.randint's stream).  The ring's tensors hold the same words either way."""
         self.chooser = G.make_chooser(chooser, env, seed)
         self.obs_norm = G.make_obs_norm(obs_norm, env, agent)
         self._nobs = None                             # device norm: the normalised observation the next act takes
@@ -177,7 +351,8 @@ class HopeRollout:
         self._plan_pending = False                    # the planner has not yet seen the last step's done / RS outputs
         self._rs_step = None                          # hope_env_last_step() of the deferred step whose search the planner waits for
         dev = env.device
-        self.ring = TransitionRing(env.n, horizon, agent.keys, dev)
+        self.ring = make_ring(ring, env, horizon, agent.keys, seed)
+        self._device_ring = isinstance(self.ring, DeviceTransitionRing)
         if use_planner == 'device':
             self.planner = G.DeviceRsPlanner(env)
         elif use_planner is True or use_planner == 1:
@@ -268,15 +443,19 @@ class HopeRollout:
             env.step(step_action, auto_reset=True, **kw)
         if self.curriculum is not None:               # update_success_record (:215-225), and every K steps the new draw weights
             self.curriculum.after_step()
-        self.ring.write_after(env.reward, env.done)
+        if self._device_ring:                         # the after half and the three tallies: two launches
+            self.ring.write_after(env.reward, env.done, env.status)
+        else:
+            self.ring.write_after(env.reward, env.done)
         if self.obs_norm is not None:
             self._nobs = self._fold(self._raw_obs())
         else:
             agent.observe(self._raw_obs())                          # push_memory: state_norm(next_obs, update=True)
-        done = env.done.bool()
-        self.episodes += done.sum()
-        self.successes += (env.status == 2).sum()
-        self.reward_sum += env.reward.sum(dtype=torch.float64)
+        if not self._device_ring:
+            done = env.done.bool()
+            self.episodes += done.sum()
+            self.successes += (env.status == 2).sum()
+            self.reward_sum += env.reward.sum(dtype=torch.float64)
         self._plan_pending = self.planner is not None               # (its bookkeeping runs in _plan, before the next override)
         self._rs_step = env.last_step() if (self.defer_rs and hasattr(env, 'last_step')) else None
         self.steps += 1
@@ -289,9 +468,12 @@ class HopeRollout:
         return self.agent._norm_obs(self._raw_obs())
 
     def stats(self):
-        ep = int(self.episodes.item())
-        out = {'steps': self.steps, 'episodes': ep, 'success_rate': float(self.successes.item()) / max(ep, 1),
-               'mean_reward': float(self.reward_sum.item()) / max(self.steps * self.env.n, 1)}
+        if self._device_ring:
+            (ep, ok), total = self.ring.counts.tolist(), float(self.ring.reward_sum.item())
+        else:
+            ep, ok, total = int(self.episodes.item()), self.successes.item(), float(self.reward_sum.item())
+        out = {'steps': self.steps, 'episodes': ep, 'success_rate': float(ok) / max(ep, 1),
+               'mean_reward': total / max(self.steps * self.env.n, 1)}
         if self.curriculum is not None:               # success_rate_<type>, as the reference logs them (:233-235)
             out.update(self.curriculum.stats())
         return out
@@ -302,15 +484,16 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None, obs_norm=None, gae=None):
-        """curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update
+                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None):
+        """ring: as HopeRollout.
+        curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update
         gae: None -- the agent's advantage block is torch code (a Python loop along the horizon); 'device' -- the agent's `gae` becomes
         an agent_glue.DeviceGae over `env`: GAE, the critic's target and the advantages' normalisation in three launches."""
         self._curriculum_per_update = curriculum is not None and 'update_every' not in curriculum
         if self._curriculum_per_update:
             curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring)
         self.gae = G.make_gae(gae, env, agent)
         self.updates = 0
 
@@ -334,10 +517,11 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None):
-        """chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used"""
+                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None):
+        """chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used
+        ring: as HopeRollout; with 'device' the batch is one k_ring_sample launch"""
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
-                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm)
+                         pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

@@ -790,6 +790,80 @@ int hope_gae_host(const float *reward, const float *done, const float *value, co
                   float *delta);
 int hope_adv_normalize_host(const float *adv, int64_t count, const double *sums, float *out, float *mean_std);
 
+/* ---- the transition ring (additive to ABI 8) ------------------------------------------------------------------------------------
+ * What rollout.TransitionRing and the three running statistics behind it do between the env step and the policy (the batched
+ * ReplayMemory of the reference, src/model/replay_memory.py:6-49): the push of a column in two halves, the tally of episodes,
+ * successes and rewards of the same step, and the uniform draw of a SAC batch with its next observations.  Four kernels:
+ * k_ring_before (a wave per scene row), k_ring_after (a lane per scene: the two column stores and the chunk's share of the tally),
+ * k_ring_tally (one wave: the partials into the running totals), k_ring_sample (a wave per batch item).  The ring's tensors and the
+ * totals are the caller's; the handle holds the chunk partials only.  Off until enabled; with it off no launch, pointer or output of
+ * any other entry point differs.  The rule and the bit-equal host twins: hope_amd/csrc/hope_ring_core.h, DESIGN.md 5j. */
+#define HOPE_RING_MAX_T 4096
+#define HOPE_RING_MAX_BATCH 1048576
+/* the ring: float32, contiguous; n scenes x T columns */
+typedef struct hope_ring_t {
+    float *lidar;          /* [n][T][120] */
+    float *target;         /* [n][T][5] */
+    float *action_mask;    /* [n][T][42] */
+    float *action;         /* [n][T][2] */
+    float *log_prob;       /* [n][T][2] */
+    float *reward;         /* [n][T] */
+    float *done;           /* [n][T]: 0 / 1 */
+    int32_t n, T;
+} hope_ring_t;
+/* a batch drawn from it: float32, contiguous */
+typedef struct hope_ring_batch_t {
+    float *obs_lidar;      /* [batch][120] */
+    float *obs_target;     /* [batch][5] */
+    float *obs_mask;       /* [batch][42] */
+    float *next_lidar;     /* [batch][120] */
+    float *next_target;    /* [batch][5] */
+    float *next_mask;      /* [batch][42] */
+    float *action;         /* [batch][2] */
+    float *reward;         /* [batch] */
+    float *done;           /* [batch] */
+    int32_t *idx;          /* [batch][3]: scene, column, next column (-1: the newest column, next_* is last_*); all -1: a refused row */
+} hope_ring_batch_t;
+/* allocate the chunk partials of the tally (ceil(N / 64) doubles and 2 x ceil(N / 64) int32).  Enabling an enabled handle changes
+ * nothing.  Host-synchronous. */
+int hope_env_ring_enable(hope_env_t *h);
+/* free them.  Host-synchronous (calls in flight use them). */
+int hope_env_ring_disable(hope_env_t *h);
+/* The three calls below are asynchronous on `stream`; they wait for nothing, never synchronise the host and do not join a deferred
+ * search.  The structs are HOST memory, read during the call; everything they and the other arguments point to is DEVICE memory,
+ * aligned to its element (float32 4, int64 / float64 8 bytes).  1 <= ring->n <= N, 1 <= ring->T <= HOPE_RING_MAX_T.
+ * HOPE_ESTATE before hope_env_ring_enable; HOPE_EINVAL for a NULL or misaligned pointer or a number out of range; on any error
+ * nothing is launched and the handle stays usable.
+ *
+ * before half of column t (0 <= t < T): lidar [n][120], target [n][5], mask [n][42], action [n][2], log_prob [n][2], float32, go
+ * into [i][t] word for word.  One launch; with the lidar bases (input and ring) 16-byte and the mask / action / log_prob bases
+ * 8-byte aligned a lane moves 16 / 8 bytes, otherwise 4; the results do not depend on that. */
+int hope_env_ring_before(hope_env_t *h, const hope_ring_t *ring, int t, const float *lidar, const float *target, const float *mask,
+                         const float *action, const float *log_prob, void *stream);
+/* after half of column t: reward [n] (float32, or float64 with reward_f64 != 0: rounded to nearest), done u8 [n] -> 0 / 1.
+ * status i32 [n], counts int64[2] and reward_sum double[1] go together: all three, and the step is tallied (counts[0] += the
+ * scenes with done != 0, counts[1] += those with status == 2, reward_sum += the sum of (double)reward in the one order of
+ * hope_ring_core.h; two launches, the partials are the handle's, so calls belong on one stream), or all NULL: one launch. */
+int hope_env_ring_after(hope_env_t *h, const hope_ring_t *ring, int t, const void *reward, int reward_f64, const uint8_t *done,
+                        const int32_t *status, int64_t *counts, double *reward_sum, void *stream);
+/* a batch of 1 <= batch <= HOPE_RING_MAX_BATCH transitions from the ring's `size` newest columns (1 <= size <= T), the next write
+ * going to column `head` (0 <= head < T).  s, j i32 [batch]: the scene and the age (0: the oldest column) of every item -- an item
+ * whose s or j is out of range gets zeros and idx = {-1, -1, -1}; both NULL: counter-based draws keyed by (seed, counter, item).
+ * last_lidar [n][120], last_target [n][5], last_mask [n][42] float32: the observation after the newest column.  One launch. */
+int hope_env_ring_sample(hope_env_t *h, const hope_ring_t *ring, int head, int size, int batch, const int32_t *s, const int32_t *j,
+                         uint64_t seed, uint64_t counter, const float *last_lidar, const float *last_target, const float *last_mask,
+                         const hope_ring_batch_t *out, void *stream);
+/* The same over HOST arrays: pure host code from the same source, no handle, no device; bit-equal to the kernels.  No alignment
+ * requirements, no upper bound on n, T or batch.  HOPE_EINVAL for a NULL required pointer, n or T < 1, t / head / size out of
+ * range, batch < 1, or a status / counts / reward_sum (s / j) given without the others. */
+int hope_ring_before_host(const hope_ring_t *ring, int t, const float *lidar, const float *target, const float *mask,
+                          const float *action, const float *log_prob);
+int hope_ring_after_host(const hope_ring_t *ring, int t, const void *reward, int reward_f64, const uint8_t *done,
+                         const int32_t *status, int64_t *counts, double *reward_sum);
+int hope_ring_sample_host(const hope_ring_t *ring, int head, int size, int64_t batch, const int32_t *s, const int32_t *j,
+                          uint64_t seed, uint64_t counter, const float *last_lidar, const float *last_target, const float *last_mask,
+                          const hope_ring_batch_t *out);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
