@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -845,8 +846,31 @@ const char* hope_env_device_arch(const hope_env_t* h) { return is_live(h) ? h->a
 // whose computed bin is b -- the bin's edges are widened by 1e-6 of a bin (the device evaluates b in float64: its rounding is ~1e-13 of
 // a bin) and by 2e-9 m (the tie band of the coarse decision is 1e-9 m).  cnt_lo == cnt_hi: the count is known and no table entry lies
 // within 1e-9 of x; otherwise the kernel looks at the float64 entries cnt_lo .. cnt_hi - 1 themselves.  tab: [NL][NITER][NACT] prefix-maxed.
-static void build_mask_lut(const std::vector<double>& tab, const std::vector<double>& pmax, const double* hull_base,
-                           std::vector<uint16_t>& lut, std::vector<double>& bsc) {
+//
+// The kernels index the table with (int)((x - lo_i) scale_i) once that is below MASK_LUT_NB, so a table whose scale is not a finite positive
+// number would send them out of bounds: tables with a value that is not finite, or with a coarse beam whose maximum does not lie above
+// lo_i, are refused (HOPE_EINVAL, `err` names the beam) before anything is built from them.  dist_star: the caller's [NL][NACT][NITER].
+static int build_mask_lut(const double* dist_star, const std::vector<double>& tab, const std::vector<double>& pmax, const double* hull_base,
+                          std::vector<uint16_t>& lut, std::vector<double>& bsc, std::string& err) {
+    // a count takes four bits of a table word (0 .. NITER), and the pair kernel keeps a table row next to its beam in 16 bits
+    static_assert(NITER <= 15 && NBEAM * MASK_LUT_NB < 65536, "the mask table's packing: 4-bit counts, 16-bit row numbers");
+    for (int i = 0; i < NBEAM; i++)
+        if (!std::isfinite(hull_base[i])) { err = "hull_base is not finite at beam " + std::to_string(i); return HOPE_EINVAL; }
+    for (int l = 0; l < NL; l++)
+        for (int e = 0; e < NACT * NITER; e++)
+            if (!std::isfinite(dist_star[(size_t)l * NACT * NITER + e])) {
+                err = "dist_star is not finite at beam " + std::to_string(l / UPS) + " (row " + std::to_string(l) + ", action " +
+                      std::to_string(e / NITER) + ")";
+                return HOPE_EINVAL;
+            }
+    for (int i = 0; i < NBEAM; i++) {
+        const double lo = hull_base[i] - 1e-6;
+        const double scale = (double)MASK_LUT_NB / (pmax[UPS * i] + 4e-9 - lo);
+        if (!(pmax[UPS * i] > lo) || !std::isfinite(scale) || !(scale > 0.0)) {
+            err = "dist_star's maximum at beam " + std::to_string(i) + " does not lie above hull_base - 1e-6: the beam's bins have no extent";
+            return HOPE_EINVAL;
+        }
+    }
     lut.assign((size_t)MASK_LUT_ROWS * MASK_LUT_ROW, (uint16_t)0xAAAA);       // padding lanes and the neutral last row: [10, 10]
     bsc.assign(NBEAM, 0.0);
     for (int i = 0; i < NBEAM; i++) {
@@ -872,6 +896,7 @@ static void build_mask_lut(const std::vector<double>& tab, const std::vector<dou
             }
         }
     }
+    return HOPE_OK;
 }
 
 // device layout of the mask table: prefix-max over k (first exceedance of a sequence == first exceedance of its running max: exact),
@@ -898,8 +923,9 @@ int hope_debug_mask_lut(const double* dist_star, const double* hull_base, uint16
     if (!dist_star || !hull_base || !lut_out || !scale_out) return fail(HOPE_EINVAL, "hope_debug_mask_lut: null argument");
     std::vector<double> tab, pmax, bsc;
     std::vector<uint16_t> lut;
+    std::string err;
     build_mask_tab(dist_star, tab, pmax);
-    build_mask_lut(tab, pmax, hull_base, lut, bsc);
+    if (build_mask_lut(dist_star, tab, pmax, hull_base, lut, bsc, err) != HOPE_OK) return fail(HOPE_EINVAL, "hope_debug_mask_lut: " + err);
     memcpy(lut_out, lut.data(), MASK_LUT_BYTES);
     memcpy(scale_out, bsc.data(), NBEAM * sizeof(double));
     return HOPE_OK;
@@ -909,17 +935,16 @@ int hope_env_upload_tables(hope_env_t* h, const double* dist_star, const double*
     HOPE_ENTER_AS(h, "hope_env_upload_tables", "null argument");
     if (!dist_star || !hull_base || !beam_ab) return fail(HOPE_EINVAL, "hope_env_upload_tables: null argument");
     HOPE_ON_DEVICE(h);
-    std::vector<double> tab, pmax;
+    // everything is derived, and the tables are validated, before the first copy: a refused call leaves the handle's tables as they were
+    std::vector<double> tab, pmax, bsc;
+    std::vector<uint16_t> lut;
+    std::string err;
     build_mask_tab(dist_star, tab, pmax);
+    if (build_mask_lut(dist_star, tab, pmax, hull_base, lut, bsc, err) != HOPE_OK) return fail(HOPE_EINVAL, "hope_env_upload_tables: " + err);
     HIPCHK(hipMemcpy(h->tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->pmax, pmax.data(), pmax.size() * sizeof(double), hipMemcpyHostToDevice));
-    {
-        std::vector<uint16_t> lut;
-        std::vector<double> bsc;
-        build_mask_lut(tab, pmax, hull_base, lut, bsc);
-        HIPCHK(hipMemcpy(h->mask_lut, lut.data(), MASK_LUT_BYTES, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->mask_bsc, bsc.data(), NBEAM * sizeof(double), hipMemcpyHostToDevice));
-    }
+    HIPCHK(hipMemcpy(h->mask_lut, lut.data(), MASK_LUT_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->mask_bsc, bsc.data(), NBEAM * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->hull_base, hull_base, NBEAM * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->beam_ab, beam_ab, 2 * NBEAM * sizeof(double), hipMemcpyHostToDevice));
     h->have_tables = true;

@@ -179,7 +179,12 @@ int hope_abi_version(void);
  * beam_ab    [120][2]  (sin theta_i, -cos theta_i) of lidar_simulator.py:86-88.
  * The library derives its device tables from them on the host: dist_star prefix-maxed over k and transposed, its per-beam maximum,
  * and (round 6) the count-interval table of the mask stage -- per coarse beam 128 scan-value bins, per bin and action the interval that
- * brackets ActionMask.get_steps' first-exceed count (action_mask.py:166-177) for every scan value of the bin (hope_debug_mask_lut). */
+ * brackets ActionMask.get_steps' first-exceed count (action_mask.py:166-177) for every scan value of the bin (hope_debug_mask_lut).
+ * The mask stage finds a beam's bin as (int)((scan - (hull_base - 1e-6)) * 128 / (max of dist_star at the beam + 4e-9 - (hull_base - 1e-6))),
+ * so tables it could not index are refused: HOPE_EINVAL if a dist_star or hull_base value is not finite, or if at one of the 120 coarse
+ * beams (rows 0, 10, 20, ...) the maximum of dist_star over actions and increments does not lie above hull_base - 1e-6;
+ * hope_last_error() names the beam.  The tables are validated before the first copy: a refused call leaves the handle's tables, and
+ * whether it has any, as they were. */
 int hope_env_upload_tables(hope_env_t *h, const double *dist_star, const double *hull_base,
                            const double *beam_ab);
 
@@ -377,7 +382,8 @@ int hope_debug_geom(int fn, int n, int n_obst, const double *in, void *out, void
 
 /* Test hook (pure host code, no device needed): the count-interval table hope_env_upload_tables derives from dist_star / hull_base for
  * the action-mask stage (hope_amd/csrc/hope_step_kernel.h MASK_LUT_*): lut_out [(120 * 128 + 1)][32] uint16, scale_out [120] bins per
- * metre.  tests/test_mask_lut.py checks its bracketing property against the float64 table (action_mask.py:166-177). */
+ * metre.  tests/test_mask_lut.py checks its bracketing property against the float64 table (action_mask.py:166-177).  HOPE_EINVAL, with
+ * the beam named, on the tables hope_env_upload_tables refuses; the outputs are then left untouched. */
 int hope_debug_mask_lut(const double *dist_star, const double *hull_base, uint16_t *lut_out, double *scale_out);
 
 /* Profiling hook: one sweep over `bytes` of the DEVICE buffer `buf` with a known byte count in one of the library's access widths --

@@ -238,6 +238,57 @@ def test_misuse_returns_its_code_and_leaves_the_handle_usable(case):
     assert lib.hope_env_destroy(h) == OK
 
 
+def test_tables_the_mask_stage_cannot_index_are_refused_and_the_handle_keeps_its_tables():
+    """hope_env_upload_tables validates before its first copy: a dist_star whose maximum at beam 0 lies below the hull range (the mask
+    stage's bin scale would be negative), a NaN and an inf are HOPE_EINVAL with the beam named, nothing is launched on them, and the
+    handle's next observation and step equal the oracle's on the tables it had"""
+    from hope_amd import tables as T
+    from hope_amd.scene_gen import mixed_arrays
+    from oracle import oracle as O
+    lib = _lib()
+    t = T.all_tables()
+    start, dest, bbox, verts, nob, nvert = mixed_arrays(N, seed=3, max_obst=MO, levels=('Normal', 'Complex', 'Extrem'))
+    arrays = [np.ascontiguousarray(a) for a in (start, dest, bbox, verts, nob.astype(np.int32))]
+    h = _create()
+    outs = Outs()
+    assert _tables(h) == OK and _set_scenes(h, arrays) == OK
+    hb = np.ascontiguousarray(t['hull_base'], np.float64)
+    ab = np.ascontiguousarray(t['beam_ab'], np.float64)
+
+    def upload(ds, hull=hb):
+        ds, hull = np.ascontiguousarray(ds, np.float64), np.ascontiguousarray(hull, np.float64)
+        return lib.hope_env_upload_tables(h, ds.ctypes.data, hull.ctypes.data, ab.ctypes.data)
+
+    bad = t['dist_star'].copy()
+    bad[:10] = 0.0
+    bad[-10:] = 0.0                                            # beam 0's table maximum is 0: below its hull range
+    assert upload(bad) == EINVAL and 'beam 0' in _err()
+    for v, where in ((np.nan, (770, 5, 3)), (np.inf, (1199, 41, 9))):
+        bad = t['dist_star'].copy()
+        bad[where] = v
+        assert upload(bad) == EINVAL and f'beam {where[0] // 10}' in _err()
+    hull = hb.copy()
+    hull[64] = np.nan
+    assert upload(t['dist_star'], hull) == EINVAL and 'beam 64' in _err()
+
+    O.set_tables(hull_base=t['hull_base'], beam_a=t['beam_ab'][:, 0], beam_b=t['beam_ab'][:, 1], dist_star=t['dist_star'], omp=True)
+    orc = O.BatchOracle(N, MO, omp=True, track_traj=False)
+    orc.set_scenes(np.arange(N), start, dest, bbox, verts, nvert, nob)
+    stages = L.STAGE_MOTION | L.STAGE_OBS | L.STAGE_REWARD
+    act = np.random.default_rng(12).integers(-8, 9, (N, 2)) / 8.0                # (float32 holds these exactly)
+    want = [{k: v.copy() for k, v in orc.reset_obs(with_rs=False).items()}, {k: v.copy() for k, v in orc.step(act, with_rs=False).items()}]
+    assert lib.hope_env_reset_obs(h, None, stages, C.byref(outs.s), None) == OK
+    for k, w in enumerate(want):
+        if k:
+            assert _step(h, outs, torch.from_numpy(act.astype(np.float32)).to('cuda:0'), stages=stages) == OK
+        torch.cuda.synchronize()
+        assert np.array_equal(outs.t['lidar'].cpu().numpy(), w['lidar'].astype(np.float32)), k
+        assert np.array_equal(outs.t['action_mask'].cpu().numpy(), w['mask'].astype(np.float32)), k
+        assert np.array_equal(outs.t['status'].cpu().numpy(), w['status']), k
+    assert np.array_equal(outs.t['pose'].cpu().numpy(), orc.pose)
+    assert lib.hope_env_destroy(h) == OK
+
+
 def test_destroy_is_idempotent_for_null_and_refuses_a_dead_handle():
     lib = _lib()
     assert lib.hope_env_destroy(None) == OK

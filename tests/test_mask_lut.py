@@ -9,13 +9,11 @@ import pytest
 
 from hope_amd import load_library
 from hope_amd import tables as T
+from mask_program import NB, ROW, NBEAM, NACT, NITER, UPS, exact_counts, kernel_mask_counts, unpack      # the mirror shared with test_mask_program.py
+import mask_program as M
 
-NB, ROW, NBEAM, NACT, NITER, UPS = 128, 32, 120, 42, 10, 10
 
-
-@pytest.fixture(scope='module')
-def lut():
-    t = T.all_tables()
+def _lut_of(t):
     ds = np.ascontiguousarray(t['dist_star'], np.float64)           # [1200][42][10]
     hb = np.ascontiguousarray(t['hull_base'], np.float64)
     out = np.zeros((NBEAM * NB + 1, ROW), np.uint16)
@@ -26,12 +24,15 @@ def lut():
     return dict(lut=out, scale=sc, tab=tab, hb=hb, pmax=tab.max(axis=(1, 2)))
 
 
-def unpack(v):
-    """-> cnt_lo[.., 42], cnt_hi[.., 42] from rows of 32 uint16 (word hl: forward action hl | backward action 21 + hl)"""
-    w = v[..., :NACT // 2].astype(np.int64)
-    lo = np.concatenate([w & 15, (w >> 8) & 15], axis=-1)
-    hi = np.concatenate([(w >> 4) & 15, w >> 12], axis=-1)
-    return lo, hi
+@pytest.fixture(scope='module')
+def lut():
+    return _lut_of(T.all_tables())
+
+
+@pytest.fixture(scope='module')
+def lut_quantised():
+    """the coarse rows on a 0.05 m grid: the library accepts the table; bins hold up to ten (equal) entries"""
+    return _lut_of(M.quantised_tables())
 
 
 def test_padding_and_neutral_row(lut):
@@ -42,14 +43,12 @@ def test_padding_and_neutral_row(lut):
     assert (lo == hi).mean() > 0.93
 
 
-def bins_of(L, i, x):
-    q = (x - (L['hb'][i] - 1e-6)) * L['scale'][i]                   # the kernel's expression, float64
-    return q
-
-
 def test_brackets_the_float64_counts(lut):
     """every scan value, also those on bin edges, table entries and their 1e-9 neighbourhoods"""
-    L = lut
+    _brackets(lut)
+
+
+def _brackets(L):
     rng = np.random.default_rng(0)
     for i in range(NBEAM):
         lo_i = L['hb'][i] - 1e-6
@@ -60,7 +59,7 @@ def test_brackets_the_float64_counts(lut):
             xs.append(L['tab'][i].ravel() + d)
         x = np.concatenate(xs)
         x = x[x >= L['hb'][i]]
-        q = bins_of(L, i, x)
+        q = M.bin_value_at(L, i, x)
         act = q < NB
         # beyond the last bin every entry is <= x - 1e-9 (the beam cannot lower any count)
         assert (L['tab'][i].max() <= x[~act] - 1e-9).all()
@@ -72,38 +71,11 @@ def test_brackets_the_float64_counts(lut):
         assert (lo <= cnt_m).all() and (cnt <= hi).all()
 
 
-def kernel_mask_counts(L, x):
-    """numpy mirror of the mask stage of k_obs_pair (HOPE_MASK_LUT): -> (ms[42], tie)"""
-    q = (x - (L['hb'] - 1e-6)) * L['scale']
-    act = np.nonzero(q < NB)[0]
-    if len(act) == 0:
-        return np.full(NACT, NITER), False
-    rows = act * NB + q[act].astype(np.int64)
-    lo, hi = unpack(L['lut'][rows])                                 # [n_act, 42]
-    mhi = hi.min(0).copy()
-    tie = False
-    if (lo.min(0) < mhi).any():
-        for j, i in enumerate(act):
-            for a in range(NACT):
-                if lo[j, a] < hi[j, a] and lo[j, a] < mhi[a]:
-                    c, lim = lo[j, a], min(hi[j, a], mhi[a])
-                    while c < lim:
-                        t = L['tab'][i, a, c]
-                        if t > x[i]:
-                            break
-                        if t > x[i] - 1e-9:
-                            tie = True
-                        c += 1
-                    mhi[a] = min(mhi[a], c)
-    return mhi, tie
-
-
-def exact_counts(L, x, shift=0.0):
-    return (L['tab'] <= (x - shift)[:, None, None]).sum(-1).min(0)
-
-
 def test_two_visit_evaluation_is_exact_or_ties(lut):
-    L = lut
+    _two_visit(lut)
+
+
+def _two_visit(L):
     rng = np.random.default_rng(1)
     n_tie = 0
     for trial in range(3000):
@@ -125,3 +97,57 @@ def test_two_visit_evaluation_is_exact_or_ties(lut):
             assert (ms == m).all()
         n_tie += tie
     assert 0 < n_tie < 3000
+
+
+def test_quantised_table_is_accepted_and_keeps_both_properties(lut_quantised):
+    L = lut_quantised
+    lo, hi = unpack(L['lut'][:-1])
+    assert (lo <= hi).all() and hi.max() <= NITER and (hi - lo).max() == NITER       # a bin that holds all ten entries of an action
+    _brackets(L)
+    _two_visit(L)
+
+
+def _status(ds, hb):
+    out = np.full((NBEAM * NB + 1, ROW), 0x1234, np.uint16)
+    sc = np.full(NBEAM, -7.0)
+    lib = load_library()
+    ds, hb = np.ascontiguousarray(ds, np.float64), np.ascontiguousarray(hb, np.float64)
+    rc = lib.hope_debug_mask_lut(ds.ctypes.data, hb.ctypes.data, out.ctypes.data, sc.ctypes.data)
+    if rc != 0:
+        assert (out == 0x1234).all() and (sc == -7.0).all()         # a refused table writes nothing
+    return rc, lib.hope_last_error().decode(errors='replace')
+
+
+@pytest.mark.parametrize('beam', [0, 37, 64, 119])
+def test_a_beam_whose_table_maximum_is_not_above_its_hull_range_is_refused(beam):
+    """the bin scale 128 / (max + 4e-9 - (hull_base - 1e-6)) would be negative (below) or span no scan value at all (equal): the
+    kernels would index the table with (int) of a negative or unbounded number.  HOPE_EINVAL, the beam named"""
+    t = T.all_tables()
+    hb = t['hull_base']
+    assert _status(t['dist_star'], hb)[0] == 0
+    below = t['dist_star'].copy()
+    below[(np.arange(10 * beam - 9, 10 * beam + 10)) % 1200] = 0.0       # the rows whose interpolation the coarse row 10 * beam enters
+    rc, err = _status(below, hb)
+    assert rc == -1 and f'beam {beam} ' in err, err
+    equal = t['dist_star'].copy()
+    equal[10 * beam] = np.minimum(equal[10 * beam], hb[beam] - 1e-6)
+    assert equal[10 * beam].max() == hb[beam] - 1e-6
+    rc, err = _status(equal, hb)
+    assert rc == -1 and f'beam {beam} ' in err, err
+    just_above = equal.copy()
+    just_above[10 * beam, 3, 9] = np.nextafter(hb[beam] - 1e-6, np.inf)
+    assert _status(just_above, hb)[0] == 0                          # (a positive finite scale: nothing to refuse)
+
+
+@pytest.mark.parametrize('value', [np.nan, np.inf, -np.inf])
+def test_a_value_that_is_not_finite_is_refused(value):
+    t = T.all_tables()
+    for where in ((0, 0, 0), (775, 20, 4), (1199, 41, 9)):
+        ds = t['dist_star'].copy()
+        ds[where] = value
+        rc, err = _status(ds, t['hull_base'])
+        assert rc == -1 and f'beam {where[0] // 10} ' in err and 'dist_star' in err, err
+    hb = t['hull_base'].copy()
+    hb[91] = value
+    rc, err = _status(t['dist_star'], hb)
+    assert rc == -1 and 'beam 91' in err and 'hull_base' in err, err
