@@ -43,6 +43,9 @@ def main():
     ap.add_argument('--device-ring', action='store_true',
                     help="also run a short PPO loop with the transition ring on the device (ring='device': k_ring_before / k_ring_after / "
                          'k_ring_tally per step instead of seven strided copy_ launches and the three torch tallies)')
+    ap.add_argument('--device-ppo-batch', action='store_true',
+                    help="also run a short PPO loop with the minibatch on the device (minibatch='device': k_ppo_gather, then k_ppo_loss / "
+                         'k_ppo_merge per minibatch instead of seven index launches, the elementwise loss and autograd through it)')
     ap.add_argument('--device-eval', action='store_true',
                     help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
                          'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
@@ -142,6 +145,22 @@ def main():
             st = tr.stats()
             print(f'  device ring: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f"{st['episodes']} episodes tallied on the device, success rate {st['success_rate']:.3f}, mean reward {st['mean_reward']:.4f}")
+    if args.device_ppo_batch:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 4096), mini_epoch=2), horizon=4,
+                        seed=rank, use_planner='device' if args.device_planner else True,
+                        chooser='device' if args.device_chooser else None, obs_norm='device' if args.device_norm else None,
+                        gae='device' if args.device_gae else None, ring='device' if args.device_ring else None, minibatch='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(16):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            al, cl = tr.agent.last_losses
+            print(f'  device ppo batch: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f'last minibatch: actor loss {al:.5f}, critic loss {cl:.5f}')
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

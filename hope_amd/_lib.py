@@ -27,6 +27,7 @@ CHOOSE_NOMASK, CHOOSE_FIXED, CHOOSE_FALLBACK = 64, 128, 10     # flag bits of th
 OBSNORM_LIDAR, OBSNORM_TARGET, OBSNORM_COLS, OBSNORM_UPDATE, OBSNORM_NORMALIZE = 120, 5, 125, 0x1, 0x2
 GAE_SUMS, GAE_NORMALIZE, GAE_MAX_T = 0x1, 0x2, 4096
 RING_MAX_T, RING_MAX_BATCH = 4096, 1 << 20
+PPO_MAX_BATCH = 1 << 20
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
 
@@ -69,6 +70,12 @@ class RingBatch(C.Structure):
     _fields_ = [('obs_lidar', C.c_void_p), ('obs_target', C.c_void_p), ('obs_mask', C.c_void_p), ('next_lidar', C.c_void_p),
                 ('next_target', C.c_void_p), ('next_mask', C.c_void_p), ('action', C.c_void_p), ('reward', C.c_void_p), ('done', C.c_void_p),
                 ('idx', C.c_void_p)]
+
+
+class PpoBatch(C.Structure):
+    """hope_ppo_batch_t: the tensors a gathered PPO minibatch goes to; `ppo_batch_desc` builds one (and notes its `batch`)"""
+    _fields_ = [('lidar', C.c_void_p), ('target', C.c_void_p), ('mask', C.c_void_p), ('action', C.c_void_p), ('old_lp', C.c_void_p),
+                ('adv', C.c_void_p), ('v_target', C.c_void_p), ('idx', C.c_void_p)]
 
 
 # the prototypes of include/hope_env.h, one entry per exported call: name -> (return type, parameter types).  The parameter kinds:
@@ -180,6 +187,12 @@ PROTOTYPES = {
     'hope_ring_before_host': (I, [C.POINTER(Ring), I] + [P] * 5),
     'hope_ring_after_host': (I, [C.POINTER(Ring), I, P, I] + [P] * 4),
     'hope_ring_sample_host': (I, [C.POINTER(Ring), I, I, I64, P, P, U64, U64, P, P, P, C.POINTER(RingBatch)]),
+    'hope_env_ppo_enable': (I, [P, I]),
+    'hope_env_ppo_disable': (I, [P]),
+    'hope_env_ppo_gather': (I, [P, C.POINTER(Ring), P, P, P, I, C.POINTER(PpoBatch), P]),
+    'hope_env_ppo_loss': (I, [P, P, P, P, C.POINTER(PpoBatch), I, D] + [P] * 5),
+    'hope_ppo_gather_host': (I, [C.POINTER(Ring), P, P, P, I64, C.POINTER(PpoBatch)]),
+    'hope_ppo_loss_host': (I, [P, P, P, C.POINTER(PpoBatch), I64, D] + [P] * 4),
     'hope_env_num_scenes': (I, [P]),
     'hope_env_max_obstacles': (I, [P]),
     'hope_env_device_arch': (S, [P]),
@@ -268,6 +281,7 @@ def array_arg(call, name, x, dtype, shape, optional=False):
 _RING_FIELDS = (('lidar', LIDAR_NUM), ('target', TARGET_DIM), ('action_mask', N_ACTION), ('action', 2), ('log_prob', 2), ('reward', None), ('done', None))
 _BATCH_FIELDS = (('obs_lidar', LIDAR_NUM), ('obs_target', TARGET_DIM), ('obs_mask', N_ACTION), ('next_lidar', LIDAR_NUM), ('next_target', TARGET_DIM),
                  ('next_mask', N_ACTION), ('action', 2), ('reward', None), ('done', None))
+_PPO_FIELDS = (('lidar', LIDAR_NUM), ('target', TARGET_DIM), ('mask', N_ACTION), ('action', 2), ('old_lp', None), ('adv', None), ('v_target', None))
 
 
 def ring_desc(call, device, n, horizon, **tensors):
@@ -288,4 +302,16 @@ def ring_batch_desc(call, device, batch, **tensors):
     for name, width in _BATCH_FIELDS:
         setattr(o, name, tensor_arg(call, name, tensors.get(name), torch.float32, (batch,) if width is None else (batch, width), device).value)
     o.idx = tensor_arg(call, 'idx', tensors.get('idx'), torch.int32, (batch, 3), device).value
+    return o
+
+
+def ppo_batch_desc(call, device, batch, **tensors):
+    """the hope_ppo_batch_t over float32 tensors lidar, target, mask, action [batch, width], old_lp, adv, v_target [batch] and idx int32
+    [batch], each checked by tensor_arg; `.batch` of the result is the extent they were checked for"""
+    import torch
+    o = PpoBatch()
+    for name, width in _PPO_FIELDS:
+        setattr(o, name, tensor_arg(call, name, tensors.get(name), torch.float32, (batch,) if width is None else (batch, width), device).value)
+    o.idx = tensor_arg(call, 'idx', tensors.get('idx'), torch.int32, (batch,), device).value
+    o.batch = batch
     return o

@@ -8,6 +8,8 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   DeviceStateNorm      <-> the same through the library's kernels (hope_env_obsnorm) or their host twin
   DeviceEvalTracker    <-> eval()'s per-episode tally   src/evaluation/eval_utils.py:35-57 (hope_env_eval_* or their host twins)
   batched_gae          <-> PPO.update's GAE loop    src/model/agent/ppo_agent.py:258-273
+  DevicePpoBatch       <-> PPO.update's minibatch loop around the forwards   src/model/agent/ppo_agent.py:278-336 (hope_env_ppo_* or
+                                                     their host twins)
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
 import math
@@ -711,6 +713,115 @@ def make_gae(gae, env, agent):
     if not (isinstance(cur, DeviceGae) and cur.env is env):
         agent.gae = DeviceGae(env)
     return agent.gae
+
+
+class PpoMinibatch:
+    """what DevicePpoBatch.gather hands to DevicePpoBatch.backward: the gathered tensors (`t`: lidar, target, mask, action [mb, .],
+    old_lp, adv, v_target [mb], idx int32 [mb]), their descriptor and the extent"""
+
+    def __init__(self, t, desc, mb):
+        self.t, self.desc, self.mb = t, desc, mb
+
+
+class DevicePpoBatch:
+    """The body of BatchedPPO.update's inner loop around the two network forwards over the library's minibatch calls (include/hope_env.h
+    "PPO's minibatch"; rule: csrc/hope_ppo_core.h), so that it can stand in as `agent.minibatch`: `gather` is ONE k_ppo_gather launch
+    instead of seven index launches, `backward` two (k_ppo_loss, k_ppo_merge) and one torch.autograd.backward seeded with the loss's
+    gradients at the networks' outputs, instead of about twenty elementwise launches and their autograd replay.  The loss is computed
+    in float64 from the float32 network outputs, so the seeds differ from the torch path's in the last bits only.
+    `ring`: a rollout.TransitionRing or DeviceTransitionRing; the gather reads its tensors as [n T] rows, so it must be full and start
+    at column 0 (head == 0, size == T: what PPOTrainer updates from, where `ring.ordered()` returns the ring's own tensors).
+    The gathered tensors and the gradients are persistent per minibatch size and overwritten by the next call with that size.  On an
+    env without the library (CPU tensors; tests/fake_env.OracleEnv) the same runs on the host through hope_ppo_gather_host /
+    hope_ppo_loss_host: the rule is one source for both.  The image key stays a torch gather by the same indices."""
+
+    def __init__(self, env, ring):
+        self.env, self.ring = env, ring
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'ppo_gather')
+        self.n, self.T = ring.n, ring.T
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'ppo_gather')
+        self._max = 0                                 # the handle's max_batch
+        self._desc = L.ring_desc('DevicePpoBatch', self.device, self.n, self.T, lidar=ring.obs['lidar'], target=ring.obs['target'],
+                                 action_mask=ring.obs['action_mask'], action=ring.action, log_prob=ring.log_prob, reward=ring.reward, done=ring.done)
+        self._out = {}                                # mb -> PpoMinibatch
+        self._grads = {}                              # mb -> (g_raw, g_log_std, g_value, losses), host path
+
+    def _outputs(self, mb):
+        if mb not in self._out:
+            dev, f = self.device, torch.float32
+            t = {'lidar': torch.zeros((mb, 120), dtype=f, device=dev), 'target': torch.zeros((mb, 5), dtype=f, device=dev),
+                 'mask': torch.zeros((mb, 42), dtype=f, device=dev), 'action': torch.zeros((mb, 2), dtype=f, device=dev),
+                 'old_lp': torch.zeros(mb, dtype=f, device=dev), 'adv': torch.zeros(mb, dtype=f, device=dev),
+                 'v_target': torch.zeros(mb, dtype=f, device=dev), 'idx': torch.zeros(mb, dtype=torch.int32, device=dev)}
+            self._out[mb] = PpoMinibatch(t, L.ppo_batch_desc('DevicePpoBatch.gather', dev, mb, **t), mb)
+        return self._out[mb]
+
+    def bind(self, obs, action, log_prob):
+        """BatchedPPO.update's arguments must be the ring's own tensors (what `ring.ordered()` returns from a full ring that starts at
+        column 0): the gather reads the ring, not them.  ValueError otherwise."""
+        ring = self.ring
+        pairs = [(obs.get(k), v) for k, v in ring.obs.items()] + [(action, ring.action), (log_prob, ring.log_prob)]
+        if any(x is None or x.data_ptr() != v.data_ptr() or x.shape != v.shape for x, v in pairs):
+            raise ValueError('DevicePpoBatch: update() was given other tensors than its ring holds (a full ring that starts at column 0?)')
+
+    def gather(self, adv, v_target, ri):
+        """adv, v_target: float32 with n T elements ([n, T] or flat); ri: int64 [mb] flat transitions (a slice of a permutation).
+        -> (st, batch): st = {'lidar', 'target', 'action_mask'(, 'img')} of the minibatch, batch the PpoMinibatch for `backward`."""
+        ring = self.ring
+        if ring.head != 0 or ring.size != ring.T:
+            raise ValueError(f'DevicePpoBatch reads a full ring that starts at column 0 (head 0, size {ring.T}), not head {ring.head}, size {ring.size}')
+        m = self.n * self.T
+        adv, v_target = (x.detach().to(torch.float32).contiguous().view(-1) for x in (adv, v_target))
+        ri = ri.detach().to(torch.int64).contiguous()
+        mb = int(ri.shape[0])
+        batch = self._outputs(mb)
+        if self.on_device:
+            if mb > self._max:
+                self.env.enable_ppo_batch(mb)
+                self._max = mb
+            self.env.ppo_gather(self._desc, adv, v_target, ri, batch.desc)
+        else:
+            arg = partial(L.tensor_arg, 'hope_ppo_gather_host', device=self.device)
+            ptrs = [arg('adv', adv, torch.float32, (m,)), arg('v_target', v_target, torch.float32, (m,)), arg('index', ri, torch.int64, (mb,))]
+            L.check(self._lib.hope_ppo_gather_host(self._desc, *ptrs, mb, batch.desc), 'hope_ppo_gather_host')
+        t = batch.t
+        st = {'lidar': t['lidar'], 'target': t['target'], 'action_mask': t['mask']}
+        if 'img' in ring.obs:                         # the image key: a torch gather by the same indices
+            img = ring.obs['img']
+            st['img'] = img.reshape((m,) + img.shape[2:])[ri]
+        return {k: st[k] for k in ring.obs}, batch
+
+    def backward(self, raw, value, log_std, batch, clip):
+        """raw [mb, 2]: the actor's output for the gathered observation, NOT clamped; value [mb, 1] or [mb]: the critic's; log_std
+        [1, 2]: the agent's parameter.  The loss call, then one backward pass through both networks from its gradients.
+        -> (actor_loss, critic_loss) as 0-dim tensors (views of a persistent tensor)."""
+        mb = batch.mb
+        r, v, ls = raw.detach().contiguous(), value.detach().reshape(-1).contiguous(), log_std.detach().reshape(-1).contiguous()
+        if self.on_device:
+            g_raw, g_log_std, g_value, losses = self.env.ppo_loss(r, ls, v, batch.desc, mb, clip)
+        else:
+            out = self._grads.get(mb)
+            if out is None:
+                out = self._grads[mb] = tuple(torch.zeros(s, dtype=torch.float32) for s in ((mb, 2), (2,), (mb,), (2,)))
+            g_raw, g_log_std, g_value, losses = out
+            arg = partial(L.tensor_arg, 'hope_ppo_loss_host', dtype=torch.float32, device=self.device)
+            ptrs = [arg('raw', r, shape=(mb, 2)), arg('log_std', ls, shape=(2,)), arg('value', v, shape=(mb,))]
+            gp = [arg(k, x, shape=tuple(x.shape)) for k, x in zip(('g_raw', 'g_log_std', 'g_value', 'losses'), out)]
+            L.check(self._lib.hope_ppo_loss_host(*ptrs, batch.desc, mb, float(clip), *gp), 'hope_ppo_loss_host')
+        torch.autograd.backward((raw, value, log_std), (g_raw, g_value.view(value.shape), g_log_std.view(log_std.shape)))
+        return losses[0], losses[1]
+
+
+def make_ppo_batch(minibatch, env, ring):
+    """the trainers' `minibatch` argument: None (today's torch path: index gathers, the elementwise loss and autograd through it), or
+    'device' -- a DevicePpoBatch over `env` and `ring`, for `agent.minibatch`.  -> the DevicePpoBatch or None."""
+    if minibatch is None:
+        return None
+    if minibatch != 'device':
+        raise ValueError(f"minibatch must be None or 'device', not {minibatch!r}")
+    return DevicePpoBatch(env, ring)
 
 
 class RolloutStorage:

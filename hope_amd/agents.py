@@ -171,12 +171,16 @@ class _AgentCommon:
 class BatchedPPO(_AgentCommon):
     def __init__(self, device='cpu', use_img=False, lr=LR, gamma=GAMMA, lam=0.95, clip_epsilon=0.2, mini_epoch=10,
                  mini_batch=32, tau=TAU, adv_norm=True, state_norm=True, adam_epsilon=1e-8, img_use_tanh=True,
-                 actor_cfg=None, critic_cfg=None, gae=None):
+                 actor_cfg=None, critic_cfg=None, gae=None, minibatch=None):
         """gae: None -- the advantage block after the critic forwards is torch code (agent_glue.batched_gae, _global_mean_std); an
-        `agent_glue.DeviceGae` -- it is one call of the library (three launches), see `advantages`."""
+        `agent_glue.DeviceGae` -- it is one call of the library (three launches), see `advantages`.
+        minibatch: None -- the inner loop of `update` gathers by index and computes the loss in torch, autograd differentiates it; an
+        `agent_glue.DevicePpoBatch` -- the gather is one call of the library, the loss and its gradients at the networks' outputs
+        another (three launches in all), and autograd runs through the two networks only."""
         self.device = torch.device(device)
         self.keys = _obs_keys(use_img)
         self.gae = gae
+        self.minibatch = minibatch
         self.gamma, self.lam, self.clip, self.mini_epoch, self.mini_batch, self.tau, self.adv_norm = \
             gamma, lam, clip_epsilon, mini_epoch, mini_batch, tau, adv_norm
         self.actor = P.HopeNet(actor_cfg or P.actor_configs(use_img=use_img), img_use_tanh).to(self.device)
@@ -219,6 +223,8 @@ class BatchedPPO(_AgentCommon):
     def update(self, obs, action, reward, done, old_log_prob, last_obs, generator=None, perms=None):
         """PPO.update (:236-349) over the [N, T] transitions collected since the last update.  `perms` (optional list of
         index permutations, one per epoch) replaces the internal shuffle (tests)."""
+        if self.minibatch is not None:
+            self.minibatch.bind(obs, action, old_log_prob)        # it gathers from its ring: these must be the ring's own tensors
         adv, v_target = self.advantages(obs, reward, done, last_obs)
         n, t = reward.shape
         m = n * t
@@ -231,16 +237,23 @@ class BatchedPPO(_AgentCommon):
             perm = perms[ep] if perms is not None else torch.randperm(m, device=self.device, generator=generator)
             for i in range(0, m, mb):
                 ri = perm[i:i + mb]
-                st = {k: v[ri] for k, v in flat.items()}
-                mean = torch.clamp(self.actor(st), -1, 1)
-                lp = P.gaussian_log_prob(mean, self.log_std.expand_as(mean), action[ri]).sum(1, keepdim=True)
-                ratio = (lp - old_lp[ri]).exp()
-                a = adv[ri]
-                actor_loss = -torch.min(ratio * a, torch.clamp(ratio, 1 - self.clip, 1 + self.clip) * a).mean()
-                critic_loss = F.mse_loss(self.critic(st), v_target[ri])
-                self.actor_opt.zero_grad(set_to_none=True)
-                self.critic_opt.zero_grad(set_to_none=True)
-                (actor_loss + critic_loss).backward()             # disjoint parameter sets: same grads as two backward()s
+                if self.minibatch is not None:                    # gather; the two forwards, no clamp in torch; the loss's gradients back
+                    st, batch = self.minibatch.gather(adv, v_target, ri)
+                    raw, value = self.actor(st), self.critic(st)
+                    self.actor_opt.zero_grad(set_to_none=True)
+                    self.critic_opt.zero_grad(set_to_none=True)
+                    actor_loss, critic_loss = self.minibatch.backward(raw, value, self.log_std, batch, self.clip)
+                else:
+                    st = {k: v[ri] for k, v in flat.items()}
+                    mean = torch.clamp(self.actor(st), -1, 1)
+                    lp = P.gaussian_log_prob(mean, self.log_std.expand_as(mean), action[ri]).sum(1, keepdim=True)
+                    ratio = (lp - old_lp[ri]).exp()
+                    a = adv[ri]
+                    actor_loss = -torch.min(ratio * a, torch.clamp(ratio, 1 - self.clip, 1 + self.clip) * a).mean()
+                    critic_loss = F.mse_loss(self.critic(st), v_target[ri])
+                    self.actor_opt.zero_grad(set_to_none=True)
+                    self.critic_opt.zero_grad(set_to_none=True)
+                    (actor_loss + critic_loss).backward()         # disjoint parameter sets: same grads as two backward()s
                 self.allreduce_bytes += D.allreduce_gradients(params)
                 self.actor_opt.step()
                 self.critic_opt.step()

@@ -80,6 +80,7 @@ class ParkingBatch:
         self.chosen_action = self.chosen_action_f32 = self.chosen_idx = self.chosen_log_prob = self.chosen_probs = None
         self.norm_lidar = self.norm_target = self.gae_sums = self._gae_out = None
         self.eval_alive = self.eval_word = self.eval_done = self._eval_rec = None
+        self._ppo_out = {}                            # mb -> (g_raw, g_log_std, g_value, losses) of ppo_loss
         self.pool_size = self.n_dlp_cases = None
         self._refresher_filling = False
 
@@ -631,6 +632,56 @@ class ParkingBatch:
         mp = arg('last_mask', last_mask, torch.float32, (n, L.N_ACTION))
         L.check(self.lib.hope_env_ring_sample(self.h, r, int(head), int(size), int(batch), sp, jp, L.seed64(seed), L.seed64(counter), lp, tp, mp, out,
                                               self._stream()), 'hope_env_ring_sample')
+
+    # -- PPO's minibatch on the device (hope_env.h; rule: csrc/hope_ppo_core.h) ----------------------------------------
+    def enable_ppo_batch(self, max_batch):
+        """the gather of a PPO minibatch by a permutation's indices and the clipped loss with its gradients as three kernels
+        (k_ppo_gather, k_ppo_loss, k_ppo_merge).  max_batch: the largest minibatch; a larger one later reallocates, an equal or
+        smaller one changes nothing.  Off by default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_ppo_enable(self.h, int(max_batch)), 'hope_env_ppo_enable')
+        return self
+
+    def disable_ppo_batch(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_ppo_disable(self.h), 'hope_env_ppo_disable')
+        return self
+
+    @staticmethod
+    def _ppo_batch_arg(call, name, desc):
+        if not isinstance(desc, L.PpoBatch) or not hasattr(desc, 'batch'):
+            raise L.HopeError(f'{call}: {name} must be a hope_amd._lib.PpoBatch (ppo_batch_desc), got {type(desc).__name__}')
+        return desc
+
+    def ppo_gather(self, ring_desc, adv, v_target, index, out_desc):
+        """out_desc (a `_lib.PpoBatch`, ppo_batch_desc) takes the transitions index (int64 [batch], flat: scene * T + column) of the ring
+        `ring_desc` (a `_lib.Ring`): observation, action, summed log-probability, and adv / v_target (float32 [n * T]) at the same
+        places; an index out of range gives a zero row with idx -1.  One launch on the current stream, no host synchronisation."""
+        r = self._ring_arg('hope_env_ppo_gather', ring_desc)
+        o = self._ppo_batch_arg('hope_env_ppo_gather', 'out_desc', out_desc)
+        arg = partial(L.tensor_arg, 'hope_env_ppo_gather', device=self.device)
+        m = r.n * r.T
+        ap, vp = arg('adv', adv, torch.float32, (m,)), arg('v_target', v_target, torch.float32, (m,))
+        ip = arg('index', index, torch.int64, (o.batch,))
+        L.check(self.lib.hope_env_ppo_gather(self.h, r, ap, vp, ip, o.batch, o, self._stream()), 'hope_env_ppo_gather')
+
+    def ppo_loss(self, raw, log_std, value, batch_desc, mb, clip):
+        """the clipped surrogate and the critic's squared error of the minibatch `batch_desc` (its action, old_lp, adv, v_target) and
+        their gradients: raw [mb, 2] the actor's output before its clamp, log_std [2], value [mb], float32 contiguous.
+        -> (g_raw [mb, 2], g_log_std [2], g_value [mb], losses [2] = actor, critic): persistent tensors per mb, overwritten by the next
+        call with that mb.  Two launches on the current stream, no host synchronisation."""
+        b = self._ppo_batch_arg('hope_env_ppo_loss', 'batch_desc', batch_desc)
+        mb = int(mb)
+        if mb != b.batch:
+            raise L.HopeError(f'hope_env_ppo_loss: mb must be the extent of batch_desc ({b.batch}), got {mb}')
+        arg = partial(L.tensor_arg, 'hope_env_ppo_loss', dtype=torch.float32, device=self.device)
+        rp, lp, vp = arg('raw', raw, shape=(mb, 2)), arg('log_std', log_std, shape=(2,)), arg('value', value, shape=(mb,))
+        out = self._ppo_out.get(mb)
+        if out is None:
+            out = self._ppo_out[mb] = tuple(torch.zeros(s, dtype=torch.float32, device=self.device) for s in ((mb, 2), (2,), (mb,), (2,)))
+        gp = [arg(k, x, shape=tuple(x.shape)) for k, x in zip(('g_raw', 'g_log_std', 'g_value', 'losses'), out)]
+        L.check(self.lib.hope_env_ppo_loss(self.h, rp, lp, vp, b, mb, float(clip), *gp, self._stream()), 'hope_env_ppo_loss')
+        return out
 
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
     def enable_eval_tracker(self):

@@ -1,5 +1,5 @@
 // hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
-// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring -- and their host twins.  They share nothing with the
+// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring, PPO's minibatch -- and their host twins.  They share nothing with the
 // step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "hope_evaltrack_kernel.h"
 #include "hope_gae_kernel.h"
 #include "hope_ring_kernel.h"
+#include "hope_ppo_kernel.h"
 
 using namespace hope;
 
@@ -21,6 +22,7 @@ using namespace hope;
 #define EVAL_ON(h, name) HOPE_NEED((h)->evalt.on, name, "the evaluation tracker is off (hope_env_eval_enable first)")
 #define GAE_ON(h, name) HOPE_NEED((h)->gae.on, name, "the advantage block is off (hope_env_gae_enable first)")
 #define RING_ON(h, name) HOPE_NEED((h)->ring.on, name, "the transition ring is off (hope_env_ring_enable first)")
+#define PPO_ON(h, name) HOPE_NEED((h)->ppo.on, name, "the minibatch is off (hope_env_ppo_enable first)")
 
 // What every hope_env_*_enable does with a feature's device buffer: allocate it if absent, fill it (from `src`, or with zeros) and
 // wait.  On any failure the buffer is freed and *buf is null; the caller then puts the feature's struct back to "off" (*_free).
@@ -83,6 +85,11 @@ void hope::ring_free(hope_env_t* h) {
     if (h->ring.part) hipFree(h->ring.part);
     if (h->ring.cnt) hipFree(h->ring.cnt);
     h->ring = hope_env::Ring{};
+}
+
+void hope::ppo_free(hope_env_t* h) {
+    if (h->ppo.part) hipFree(h->ppo.part);
+    h->ppo = hope_env::Ppo{};
 }
 
 // the ring descriptor of a hope_env_ring_* call `name`: every tensor there and aligned to its element, n and T in range
@@ -618,6 +625,88 @@ int hope_ring_sample_host(const hope_ring_t* ring, int head, int size, int64_t b
     const int rc = rg_sample_host(ring, head, size, batch, s, j, seed, counter, last_lidar, last_target, last_mask, out);
     if (rc != HOPE_OK)
         return fail(rc, "hope_ring_sample_host: bad argument (a null ring, tensor, last_* or out, n or T < 1, head outside 0 .. T - 1, size outside 1 .. T, batch < 1, or s without j or the reverse)");
+    return HOPE_OK;
+}
+
+// ---- PPO's minibatch (include/hope_env.h; kernels: hope_ppo_kernel.h, rule: hope_ppo_core.h) ----
+int hope_env_ppo_enable(hope_env_t* h, int max_batch) {
+    HOPE_ENTER(h, "hope_env_ppo_enable");
+    if (max_batch < 1 || max_batch > HOPE_PPO_MAX_BATCH) return fail(HOPE_EINVAL, "hope_env_ppo_enable: max_batch must be 1 .. " + std::to_string(HOPE_PPO_MAX_BATCH));
+    if (h->ppo.on && max_batch <= h->ppo.max_batch) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // loss calls in flight use the partials that a larger max_batch replaces
+    ppo_free(h);
+    const int rc = device_buffer("hope_env_ppo_enable", &h->ppo.part, (size_t)PB_SUMS * (size_t)pb_chunks(max_batch) * sizeof(double));
+    if (rc != HOPE_OK) { ppo_free(h); return rc; }
+    h->ppo.max_batch = max_batch;
+    h->ppo.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_ppo_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_ppo_disable");
+    return feature_disable(h, ppo_free);
+}
+
+int hope_env_ppo_gather(hope_env_t* h, const hope_ring_t* ring, const float* adv, const float* v_target, const int64_t* index, int batch,
+                        const hope_ppo_batch_t* out, void* stream) {
+    HOPE_ENTER(h, "hope_env_ppo_gather");
+    PPO_ON(h, "hope_env_ppo_gather");
+    RING_ARG(h, ring, "hope_env_ppo_gather");
+    if (!adv || !v_target || !index) return fail(HOPE_EINVAL, "hope_env_ppo_gather: null adv / v_target / index");
+    if (batch < 1 || batch > h->ppo.max_batch) return fail(HOPE_EINVAL, "hope_env_ppo_gather: batch must be 1 .. max_batch (" + std::to_string(h->ppo.max_batch) + ")");
+    if (!out) return fail(HOPE_EINVAL, "hope_env_ppo_gather: null out");
+    if (!pb_batch_ok(out)) return fail(HOPE_EINVAL, "hope_env_ppo_gather: null tensor in out");
+    const uintptr_t all = (uintptr_t)adv | (uintptr_t)v_target | (uintptr_t)out->lidar | (uintptr_t)out->target | (uintptr_t)out->mask | (uintptr_t)out->action |
+                          (uintptr_t)out->old_lp | (uintptr_t)out->adv | (uintptr_t)out->v_target | (uintptr_t)out->idx;
+    if ((all & 3) || ((uintptr_t)index & 7)) return fail(HOPE_EINVAL, "hope_env_ppo_gather: misaligned buffer (index 8 bytes, every other tensor 4)");
+    HOPE_ON_DEVICE(h);
+    const uintptr_t a16 = (uintptr_t)ring->lidar | (uintptr_t)out->lidar;
+    const uintptr_t a8 = (uintptr_t)ring->action_mask | (uintptr_t)ring->action | (uintptr_t)ring->log_prob | (uintptr_t)out->mask | (uintptr_t)out->action;
+    const dim3 grid((unsigned)batch), block(64);
+    if (!(a16 & 15) && !(a8 & 7)) hipLaunchKernelGGL(k_ppo_gather<4>, grid, block, 0, (hipStream_t)stream, *ring, adv, v_target, index, *out);
+    else hipLaunchKernelGGL(k_ppo_gather<1>, grid, block, 0, (hipStream_t)stream, *ring, adv, v_target, index, *out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_ppo_loss(hope_env_t* h, const float* raw, const float* log_std, const float* value, const hope_ppo_batch_t* batch, int mb, double clip,
+                      float* g_raw, float* g_log_std, float* g_value, float* losses, void* stream) {
+    HOPE_ENTER(h, "hope_env_ppo_loss");
+    PPO_ON(h, "hope_env_ppo_loss");
+    if (!raw || !log_std || !value || !g_raw || !g_log_std || !g_value || !losses)
+        return fail(HOPE_EINVAL, "hope_env_ppo_loss: null raw / log_std / value / g_raw / g_log_std / g_value / losses");
+    if (!batch) return fail(HOPE_EINVAL, "hope_env_ppo_loss: null batch");
+    if (!batch->action || !batch->old_lp || !batch->adv || !batch->v_target) return fail(HOPE_EINVAL, "hope_env_ppo_loss: null tensor in batch (action / old_lp / adv / v_target)");
+    if (mb < 1 || mb > h->ppo.max_batch) return fail(HOPE_EINVAL, "hope_env_ppo_loss: mb must be 1 .. max_batch (" + std::to_string(h->ppo.max_batch) + ")");
+    if (!pb_clip_ok(clip)) return fail(HOPE_EINVAL, "hope_env_ppo_loss: clip must be finite and >= 0");
+    const uintptr_t pair = (uintptr_t)raw | (uintptr_t)batch->action | (uintptr_t)g_raw;
+    const uintptr_t all = pair | (uintptr_t)log_std | (uintptr_t)value | (uintptr_t)batch->old_lp | (uintptr_t)batch->adv | (uintptr_t)batch->v_target |
+                          (uintptr_t)g_log_std | (uintptr_t)g_value | (uintptr_t)losses;
+    if (all & 3) return fail(HOPE_EINVAL, "hope_env_ppo_loss: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const long long nk = pb_chunks(mb);                           // <= the partials' room: mb <= max_batch
+    hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)nk), dim3(64), 0, (hipStream_t)stream, raw, log_std, value, (const float*)batch->action,
+                       (const float*)batch->old_lp, (const float*)batch->adv, (const float*)batch->v_target, mb, clip, (pair & 7) ? 0 : 1, g_raw, g_value, nk,
+                       h->ppo.part);
+    hipLaunchKernelGGL(k_ppo_merge, dim3(1), dim3(64), 0, (hipStream_t)stream, nk, (double)mb, h->ppo.part, losses, g_log_std);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_ppo_gather_host(const hope_ring_t* ring, const float* adv, const float* v_target, const int64_t* index, int64_t batch, const hope_ppo_batch_t* out) {
+    const int rc = pb_gather_host(ring, adv, v_target, index, batch, out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_ppo_gather_host: bad argument (a null ring, tensor, adv, v_target, index or out, n or T < 1, or batch < 1)");
+    return HOPE_OK;
+}
+
+int hope_ppo_loss_host(const float* raw, const float* log_std, const float* value, const hope_ppo_batch_t* batch, int64_t mb, double clip, float* g_raw,
+                       float* g_log_std, float* g_value, float* losses) {
+    const int rc = pb_loss_host(raw, log_std, value, batch, mb, clip, g_raw, g_log_std, g_value, losses);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_ppo_loss_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_ppo_loss_host: bad argument (a null raw / log_std / value / batch / output, a null action / old_lp / adv / v_target in batch, mb < 1, or a clip that is negative or not finite)");
     return HOPE_OK;
 }
 

@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -229,6 +229,9 @@ struct hope_env {
     // the transition ring (hope_ring_kernel.h): the chunk partials of a step's tally, part = the reward sums ([chunks]) and cnt = the
     // done / success counts ([chunks][2]), room for ceil(n / 64) chunks; the ring's tensors and the totals are the caller's
     struct Ring { bool on = false; double* part = nullptr; int32_t* cnt = nullptr; } ring;
+    // PPO's minibatch (hope_ppo_kernel.h): part = the chunk partials of the loss call's four sums ([4][chunks of the call], room for
+    // ceil(max_batch / 64) chunks)
+    struct Ppo { bool on = false; double* part = nullptr; int max_batch = 0; } ppo;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -244,4 +247,5 @@ void onorm_free(hope_env_t* h);
 void evalt_free(hope_env_t* h);
 void gae_free(hope_env_t* h);
 void ring_free(hope_env_t* h);
+void ppo_free(hope_env_t* h);
 }  // namespace hope

@@ -484,8 +484,11 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None):
+                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None):
         """ring: as HopeRollout.
+        minibatch: None -- the inner loop of the agent's update is torch code (seven index launches per minibatch, about twenty for the
+        loss, as many again in autograd); 'device' -- the agent's `minibatch` becomes an agent_glue.DevicePpoBatch over `env` and this
+        trainer's ring (either class): one launch for the gather, two for the loss and its gradients.
         curriculum: as HopeRollout; without an update_every of its own the draw weights are rebuilt after each PPO update
         gae: None -- the agent's advantage block is torch code (a Python loop along the horizon); 'device' -- the agent's `gae` becomes
         an agent_glue.DeviceGae over `env`: GAE, the critic's target and the advantages' normalisation in three launches."""
@@ -495,6 +498,11 @@ class PPOTrainer(HopeRollout):
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring)
         self.gae = G.make_gae(gae, env, agent)
+        self.minibatch = G.make_ppo_batch(minibatch, env, self.ring)
+        if self.minibatch is not None:
+            if not hasattr(agent, 'minibatch'):
+                raise ValueError("minibatch='device' needs an agent with a minibatch loop (BatchedPPO)")
+            agent.minibatch = self.minibatch
         self.updates = 0
 
     def step(self):

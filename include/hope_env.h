@@ -870,6 +870,60 @@ int hope_ring_sample_host(const hope_ring_t *ring, int head, int size, int64_t b
                           uint64_t seed, uint64_t counter, const float *last_lidar, const float *last_target, const float *last_mask,
                           const hope_ring_batch_t *out);
 
+/* ---- PPO's minibatch (additive to ABI 8) ----------------------------------------------------------------------------------------
+ * What the inner loop of BatchedPPO.update does around the two network forwards (the reference's PPO.update,
+ * src/model/agent/ppo_agent.py:278-336): the gather of a minibatch from the ring by a permutation's indices, and the clipped
+ * surrogate, the critic's squared error and their gradients with respect to the networks' outputs and log_std.  Three kernels:
+ * k_ppo_gather (a wave per item), k_ppo_loss (a lane per item: its gradients and the chunk's share of the four sums), k_ppo_merge
+ * (one wave: the chunk partials' trees).  The sums have one arithmetic order, independent of the launch geometry.  The handle holds
+ * the chunk partials only.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule
+ * and the bit-equal host twins: hope_amd/csrc/hope_ppo_core.h, DESIGN.md 5k. */
+#define HOPE_PPO_MAX_BATCH 1048576
+/* a gathered minibatch: float32, contiguous */
+typedef struct hope_ppo_batch_t {
+    float *lidar;          /* [mb][120] */
+    float *target;         /* [mb][5] */
+    float *mask;           /* [mb][42] */
+    float *action;         /* [mb][2] */
+    float *old_lp;         /* [mb]: the pair of log-probabilities summed */
+    float *adv;            /* [mb] */
+    float *v_target;       /* [mb] */
+    int32_t *idx;          /* [mb]: the flat transition scene * T + column; -1: a refused row */
+} hope_ppo_batch_t;
+/* allocate the chunk partials (4 x ceil(max_batch / 64) doubles), 1 <= max_batch <= HOPE_PPO_MAX_BATCH.  On an enabled handle a
+ * larger max_batch reallocates, an equal or smaller one changes nothing.  Host-synchronous. */
+int hope_env_ppo_enable(hope_env_t *h, int max_batch);
+/* free them.  Host-synchronous (calls in flight use them). */
+int hope_env_ppo_disable(hope_env_t *h);
+/* The two calls below are asynchronous on `stream`; they wait for nothing, never synchronise the host and do not join a deferred
+ * search.  The structs are HOST memory, read during the call; everything they and the other arguments point to is DEVICE memory,
+ * aligned to its element (float32 and int32 4, int64 8 bytes).  HOPE_ESTATE before hope_env_ppo_enable; HOPE_EINVAL for a NULL or
+ * misaligned pointer, a number out of range or a clip that is not finite; on any error nothing is launched and the handle stays
+ * usable.
+ *
+ * item b of 1 <= batch <= max_batch takes the ring's flat transition index[b] = scene * T + column (int64 [batch]; the ring as
+ * hope_env_ring_*: 1 <= ring->n <= N, 1 <= ring->T <= HOPE_RING_MAX_T): lidar, target, action_mask and action word for word, the two
+ * log-probabilities summed, adv and v_target (float32 [n * T], e.g. hope_env_gae's outputs) and the index itself.  An index outside
+ * 0 .. n * T - 1 gives a zero row and idx -1.  One launch; with the lidar bases (ring and out) 16-byte and the mask / action bases
+ * and the ring's log_prob 8-byte aligned a lane moves 16 / 8 bytes, otherwise 4; the results do not depend on that. */
+int hope_env_ppo_gather(hope_env_t *h, const hope_ring_t *ring, const float *adv, const float *v_target, const int64_t *index,
+                        int batch, const hope_ppo_batch_t *out, void *stream);
+/* the loss of 1 <= mb <= max_batch items and its gradients: raw [mb][2] is the actor's output BEFORE its clamp to [-1, 1],
+ * log_std [2], value [mb] the critic's output; action, old_lp, adv and v_target are read from `batch` (its other fields are not
+ * used).  clip is finite and >= 0.  Outputs: g_raw [mb][2], g_log_std [2], g_value [mb] -- the gradients of actor loss + critic
+ * loss, the seeds of one backward pass through both networks -- and losses [2] = {actor loss, critic loss}.  Two launches, the
+ * partials are the handle's, so calls belong on one stream; with raw, action and g_raw 8-byte aligned a lane moves a pair at once;
+ * the results do not depend on that. */
+int hope_env_ppo_loss(hope_env_t *h, const float *raw, const float *log_std, const float *value, const hope_ppo_batch_t *batch,
+                      int mb, double clip, float *g_raw, float *g_log_std, float *g_value, float *losses, void *stream);
+/* The same over HOST arrays: pure host code from the same source, no handle, no device; bit-equal to the kernels.  No alignment
+ * requirements, no upper bound on n, T, batch or mb.  HOPE_EINVAL for a NULL required pointer, n or T < 1, batch or mb < 1, or a
+ * clip that is negative or not finite. */
+int hope_ppo_gather_host(const hope_ring_t *ring, const float *adv, const float *v_target, const int64_t *index, int64_t batch,
+                         const hope_ppo_batch_t *out);
+int hope_ppo_loss_host(const float *raw, const float *log_std, const float *value, const hope_ppo_batch_t *batch, int64_t mb,
+                       double clip, float *g_raw, float *g_log_std, float *g_value, float *losses);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
