@@ -46,6 +46,10 @@ def main():
     ap.add_argument('--device-ppo-batch', action='store_true',
                     help="also run a short PPO loop with the minibatch on the device (minibatch='device': k_ppo_gather, then k_ppo_loss / "
                          'k_ppo_merge per minibatch instead of seven index launches, the elementwise loss and autograd through it)')
+    ap.add_argument('--device-sac-update', action='store_true',
+                    help="also run a short SAC loop with the update's arithmetic on the device (sac_update='device': k_sac_sample, k_sac_critic, "
+                         'k_sac_seed, k_sac_policy and k_sac_merge between the network forwards instead of the elementwise lines and autograd '
+                         'through them)')
     ap.add_argument('--device-eval', action='store_true',
                     help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
                          'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
@@ -161,6 +165,19 @@ def main():
             al, cl = tr.agent.last_losses
             print(f'  device ppo batch: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f'last minibatch: actor loss {al:.5f}, critic loss {cl:.5f}')
+    if args.device_sac_update:
+        from hope_amd import agents as A
+        from hope_amd.rollout import SACTrainer
+        tr = SACTrainer(env, A.BatchedSAC(device=dev, use_img=False, batch_size=min(args.scenes, 4096)), horizon=4, update_every=2, seed=rank,
+                        use_planner='device' if args.device_planner else True, obs_norm='device' if args.device_norm else None,
+                        ring='device' if args.device_ring else None, sac_update='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        losses = [x for x in (tr.step() for _ in range(16)) if x is not None]
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f'  device sac update: 16 SAC steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f'last update: actor loss {losses[-1][0]:.5f}, critic loss {losses[-1][1]:.5f}, temperature {float(tr.agent.alpha):.5f}')
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

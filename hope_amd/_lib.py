@@ -28,6 +28,7 @@ OBSNORM_LIDAR, OBSNORM_TARGET, OBSNORM_COLS, OBSNORM_UPDATE, OBSNORM_NORMALIZE =
 GAE_SUMS, GAE_NORMALIZE, GAE_MAX_T = 0x1, 0x2, 4096
 RING_MAX_T, RING_MAX_BATCH = 4096, 1 << 20
 PPO_MAX_BATCH = 1 << 20
+SAC_MAX_BATCH = 1 << 20
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
 
@@ -193,6 +194,16 @@ PROTOTYPES = {
     'hope_env_ppo_loss': (I, [P, P, P, P, C.POINTER(PpoBatch), I, D] + [P] * 5),
     'hope_ppo_gather_host': (I, [C.POINTER(Ring), P, P, P, I64, C.POINTER(PpoBatch)]),
     'hope_ppo_loss_host': (I, [P, P, P, C.POINTER(PpoBatch), I64, D] + [P] * 4),
+    'hope_env_sac_enable': (I, [P, I]),
+    'hope_env_sac_disable': (I, [P]),
+    'hope_env_sac_sample': (I, [P, P, P, P, I, P, P, P]),
+    'hope_env_sac_critic': (I, [P] * 9 + [D, I] + [P] * 5),
+    'hope_env_sac_seed': (I, [P, P, P, I, P, P, P]),
+    'hope_env_sac_policy': (I, [P] * 8 + [D, I] + [P] * 5),
+    'hope_sac_sample_host': (I, [P, P, P, I64, P, P]),
+    'hope_sac_critic_host': (I, [P] * 8 + [D, I64] + [P] * 4),
+    'hope_sac_seed_host': (I, [P, P, I64, P, P]),
+    'hope_sac_policy_host': (I, [P] * 7 + [D, I64] + [P] * 4),
     'hope_env_num_scenes': (I, [P]),
     'hope_env_max_obstacles': (I, [P]),
     'hope_env_device_arch': (S, [P]),

@@ -10,6 +10,7 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   batched_gae          <-> PPO.update's GAE loop    src/model/agent/ppo_agent.py:258-273
   DevicePpoBatch       <-> PPO.update's minibatch loop around the forwards   src/model/agent/ppo_agent.py:278-336 (hope_env_ppo_* or
                                                      their host twins)
+  DeviceSacUpdate      <-> SACAgent.update between its forwards   src/model/agent/sac_agent.py:250-337 (hope_env_sac_* or their host twins)
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
 import math
@@ -822,6 +823,106 @@ def make_ppo_batch(minibatch, env, ring):
     if minibatch != 'device':
         raise ValueError(f"minibatch must be None or 'device', not {minibatch!r}")
     return DevicePpoBatch(env, ring)
+
+
+class DeviceSacUpdate:
+    """The arithmetic of BatchedSAC.update between its seven network forwards over the library's calls (include/hope_env.h "SAC's
+    update"; rule: csrc/hope_sac_core.h), so that it can stand in as `agent.update_block`: the reparameterised sample is ONE launch
+    (k_sac_sample), the Q target with the critics' losses and their gradients two (k_sac_critic, k_sac_merge), the actor loss's
+    gradient at the critic outputs one (k_sac_seed), and the actor and temperature losses with their gradients at the actor's output,
+    log_std and log_alpha two (k_sac_policy, k_sac_merge) -- instead of some eighty elementwise launches and their autograd replay.
+    Autograd then runs through the networks only.  All arithmetic is float64 on the float32 network outputs, so the gradients differ
+    from the torch path's in the last bits only.  The temperature is read on the device: no host synchronisation.
+    The outputs are persistent per batch size and overwritten by the next call with that size.  On an env without the library (CPU
+    tensors; tests/fake_env.OracleEnv) the same runs on the host through hope_sac_*_host: the rule is one source for both."""
+
+    def __init__(self, env):
+        self.env = env
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'sac_sample')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'sac_sample')
+        self._max = 0                                 # the handle's max_batch
+        self._out = {}                                # (call, B) -> outputs, host path
+
+    def _room(self, b):
+        if self.on_device and b > self._max:
+            self.env.enable_sac_update(b)
+            self._max = b
+
+    def _host(self, call, b, ins, scalars, shapes):
+        """hope_sac_<call>_host over CPU tensors: ins = [(name, tensor, shape)], scalars = [(position among the arguments, value)],
+        shapes = the outputs' (None: the float64 scalar) -> the persistent outputs"""
+        name = f'hope_sac_{call}_host'
+        out = self._out.get((call, b))
+        if out is None:
+            out = self._out[(call, b)] = tuple(torch.zeros((), dtype=torch.float64) if s is None else torch.zeros(s, dtype=torch.float32) for s in shapes)
+        args = [L.tensor_arg(name, k, x, torch.float64 if s == () else torch.float32, s, self.device) for k, x, s in ins]
+        for at, v in scalars:
+            args.insert(at, v)
+        args += [L.tensor_arg(name, f'output {i}', x, x.dtype, tuple(x.shape), self.device) for i, x in enumerate(out)]
+        L.check(getattr(self._lib, name)(*args), name)
+        return out
+
+    @staticmethod
+    def _f32(x, shape):
+        return x.detach().to(torch.float32).reshape(shape).contiguous()
+
+    def sample(self, raw, log_std, eps):
+        """raw [B, 2]: the actor's output, NOT clamped; log_std [1, 2]: the agent's parameter; eps [B, 2]: the normal draw
+        -> (action [B, 2], lp [B]) without a graph"""
+        b = int(raw.shape[0])
+        r, ls, e = self._f32(raw, (b, 2)), self._f32(log_std, (2,)), self._f32(eps, (b, 2))
+        self._room(b)
+        if self.on_device:
+            return self.env.sac_sample(r, ls, e)
+        return self._host('sample', b, [('raw', r, (b, 2)), ('log_std', ls, (2,)), ('eps', e, (b, 2))], [(3, b)], ((b, 2), (b,)))
+
+    def critic(self, q1, q2, qt1, qt2, next_lp, reward, done, log_alpha, gamma):
+        """q1, q2, qt1, qt2, reward, done: [B, 1] or [B]; next_lp [B]; log_alpha: the agent's float64 scalar
+        -> (q_target [B], g_q1 [B], g_q2 [B], losses [2])"""
+        b = int(q1.shape[0])
+        names = ('q1', 'q2', 'qt1', 'qt2', 'next_lp', 'reward', 'done')
+        t = [self._f32(x, (b,)) for x in (q1, q2, qt1, qt2, next_lp, reward, done)]
+        la = log_alpha.detach()
+        self._room(b)
+        if self.on_device:
+            return self.env.sac_critic(*t, la, gamma)
+        return self._host('critic', b, [(k, x, (b,)) for k, x in zip(names, t)] + [('log_alpha', la, ())], [(8, float(gamma)), (9, b)],
+                          ((b,), (b,), (b,), (2,)))
+
+    def seed(self, q1, q2):
+        """q1, q2 [B, 1] or [B]: the critics at the sampled action -> (s1 [B], s2 [B])"""
+        b = int(q1.shape[0])
+        t1, t2 = self._f32(q1, (b,)), self._f32(q2, (b,))
+        self._room(b)
+        if self.on_device:
+            return self.env.sac_seed(t1, t2)
+        return self._host('seed', b, [('q1', t1, (b,)), ('q2', t2, (b,))], [(2, b)], ((b,), (b,)))
+
+    def policy(self, raw, log_std, eps, q1, q2, g_action, log_alpha, target_entropy):
+        """raw, log_std, eps as for `sample`; q1, q2 as for `seed`; g_action [B, 2]: autograd's gradient at the sampled action for the
+        seeds -> (g_raw [B, 2], g_log_std [2], g_log_alpha (float64 scalar), losses [2] = actor loss, temperature loss)"""
+        b = int(raw.shape[0])
+        r, ls, e, g = self._f32(raw, (b, 2)), self._f32(log_std, (2,)), self._f32(eps, (b, 2)), self._f32(g_action, (b, 2))
+        t1, t2 = self._f32(q1, (b,)), self._f32(q2, (b,))
+        la = log_alpha.detach()
+        self._room(b)
+        if self.on_device:
+            return self.env.sac_policy(r, ls, e, t1, t2, g, la, target_entropy)
+        return self._host('policy', b, [('raw', r, (b, 2)), ('log_std', ls, (2,)), ('eps', e, (b, 2)), ('q1', t1, (b,)), ('q2', t2, (b,)),
+                                        ('g_action', g, (b, 2)), ('log_alpha', la, ())], [(7, float(target_entropy)), (8, b)],
+                          ((b, 2), (2,), None, (2,)))
+
+
+def make_sac_update(kind, env):
+    """the trainers' `sac_update` argument: None (today's torch path: the elementwise lines of BatchedSAC.update and autograd through
+    them), or 'device' -- a DeviceSacUpdate over `env`, for `agent.update_block`.  -> the DeviceSacUpdate or None."""
+    if kind is None:
+        return None
+    if kind != 'device':
+        raise ValueError(f"sac_update must be None or 'device', not {kind!r}")
+    return DeviceSacUpdate(env)
 
 
 class RolloutStorage:

@@ -264,8 +264,12 @@ class BatchedPPO(_AgentCommon):
 
 class BatchedSAC(_AgentCommon):
     def __init__(self, device='cpu', use_img=False, lr=LR, gamma=GAMMA, tau=0.005, batch_size=32,
-                 initial_temperature=0.01, learn_temperature=True, state_norm=True, img_use_tanh=True):
+                 initial_temperature=0.01, learn_temperature=True, state_norm=True, img_use_tanh=True, update_block=None):
+        """update_block: None -- `update` computes the sample, the Q target and the three losses in torch and autograd differentiates
+        them; an `agent_glue.DeviceSacUpdate` -- they are calls of the library (eight launches in all) that also return the losses'
+        gradients at the networks' outputs, and autograd runs through the networks only (`_update_with_block`)."""
         self.device = torch.device(device)
+        self.update_block = update_block
         self.keys = _obs_keys(use_img)
         self.gamma, self.tau, self.batch_size, self.learn_temperature = gamma, tau, batch_size, learn_temperature
         self.target_entropy = -2.0                                                                   # -action_dim (:51)
@@ -297,6 +301,8 @@ class BatchedSAC(_AgentCommon):
     def update(self, batch, noise=None):
         """one SAC update (:263-337) on a batch {'obs', 'next_obs' (normalised dicts), 'action', 'reward', 'done'}.
         `noise` = (eps for the next-state action, eps for the policy-loss action), tests only."""
+        if self.update_block is not None:
+            return self._update_with_block(batch, noise)
         st, nst = batch['obs'], batch['next_obs']
         action, reward, done = batch['action'], batch['reward'].view(-1, 1), batch['done'].view(-1, 1)
         alpha = self.alpha.detach().to(reward.dtype)
@@ -334,3 +340,42 @@ class BatchedSAC(_AgentCommon):
         _soft_update(self.critic_target1, self.critic1, self.tau)
         _soft_update(self.critic_target2, self.critic2, self.tau)
         return float(actor_loss.detach()), float(q1_loss.detach())
+
+    def _update_with_block(self, batch, noise=None):
+        """`update` with the arithmetic between the forwards in `self.update_block`: the same forwards in the same order and the same
+        draws of eps, so the same torch seed gives both paths the same noise; no requires_grad toggling over the critic parameters."""
+        blk = self.update_block
+        st, nst = batch['obs'], batch['next_obs']
+        action, reward, done = batch['action'], batch['reward'], batch['done']
+        with torch.no_grad():
+            raw = self.actor(nst)
+            eps = torch.randn_like(raw) if noise is None else noise[0]
+            na, nlp = blk.sample(raw, self.log_std, eps)
+            qt1, qt2 = self.critic_target1(nst, na), self.critic_target2(nst, na)
+        q1, q2 = self.critic1(st, action), self.critic2(st, action)
+        _, g_q1, g_q2, q_losses = blk.critic(q1, q2, qt1, qt2, nlp, reward, done, self.log_alpha, self.gamma)
+        self.critic_opt1.zero_grad(set_to_none=True)
+        self.critic_opt2.zero_grad(set_to_none=True)
+        torch.autograd.backward((q1, q2), (g_q1.view(q1.shape), g_q2.view(q2.shape)))
+        self.allreduce_bytes += D.allreduce_gradients(list(self.critic1.parameters()) + list(self.critic2.parameters()))
+        self.critic_opt1.step()
+        self.critic_opt2.step()
+        raw = self.actor(st)
+        eps = torch.randn_like(raw) if noise is None else noise[1]
+        a = blk.sample(raw, self.log_std, eps)[0].detach().requires_grad_()           # a leaf: autograd stops at the sampled action
+        q1, q2 = self.critic1(st, a), self.critic2(st, a)
+        s1, s2 = blk.seed(q1, q2)
+        g_action, = torch.autograd.grad((q1, q2), (a,), (s1.view(q1.shape), s2.view(q2.shape)))
+        g_raw, g_log_std, g_log_alpha, p_losses = blk.policy(raw, self.log_std, eps, q1, q2, g_action, self.log_alpha, self.target_entropy)
+        self.actor_opt.zero_grad(set_to_none=True)
+        torch.autograd.backward((raw, self.log_std), (g_raw, g_log_std.view(self.log_std.shape)))
+        self.allreduce_bytes += D.allreduce_gradients(list(self.actor.parameters()) + [self.log_std])
+        self.actor_opt.step()
+        if self.learn_temperature:
+            self.alpha_opt.zero_grad(set_to_none=True)
+            self.log_alpha.grad = g_log_alpha
+            self.allreduce_bytes += D.allreduce_gradients([self.log_alpha])
+            self.alpha_opt.step()
+        _soft_update(self.critic_target1, self.critic1, self.tau)
+        _soft_update(self.critic_target2, self.critic2, self.tau)
+        return float(p_losses[0]), float(q_losses[0])

@@ -81,6 +81,7 @@ class ParkingBatch:
         self.norm_lidar = self.norm_target = self.gae_sums = self._gae_out = None
         self.eval_alive = self.eval_word = self.eval_done = self._eval_rec = None
         self._ppo_out = {}                            # mb -> (g_raw, g_log_std, g_value, losses) of ppo_loss
+        self._sac_out = {}                            # (call, B) -> the outputs of sac_sample / sac_critic / sac_seed / sac_policy
         self.pool_size = self.n_dlp_cases = None
         self._refresher_filling = False
 
@@ -681,6 +682,80 @@ class ParkingBatch:
             out = self._ppo_out[mb] = tuple(torch.zeros(s, dtype=torch.float32, device=self.device) for s in ((mb, 2), (2,), (mb,), (2,)))
         gp = [arg(k, x, shape=tuple(x.shape)) for k, x in zip(('g_raw', 'g_log_std', 'g_value', 'losses'), out)]
         L.check(self.lib.hope_env_ppo_loss(self.h, rp, lp, vp, b, mb, float(clip), *gp, self._stream()), 'hope_env_ppo_loss')
+        return out
+
+    # -- SAC's update on the device (hope_env.h; rule: csrc/hope_sac_core.h) -------------------------------------------
+    def enable_sac_update(self, max_batch):
+        """the arithmetic of BatchedSAC.update between its network forwards as kernels (k_sac_sample, k_sac_critic, k_sac_seed,
+        k_sac_policy, k_sac_merge).  max_batch: the largest batch; a larger one later reallocates, an equal or smaller one changes
+        nothing.  Off by default."""
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_sac_enable(self.h, int(max_batch)), 'hope_env_sac_enable')
+        return self
+
+    def disable_sac_update(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_sac_disable(self.h), 'hope_env_sac_disable')
+        return self
+
+    def _sac_outputs(self, call, batch, shapes):
+        """the persistent outputs of `call` for this batch size: float32 tensors of `shapes` (a shape of None: a float64 scalar)"""
+        out = self._sac_out.get((call, batch))
+        if out is None:
+            out = self._sac_out[(call, batch)] = tuple(
+                torch.zeros((), dtype=torch.float64, device=self.device) if s is None else torch.zeros(s, dtype=torch.float32, device=self.device)
+                for s in shapes)
+        return out
+
+    def sac_sample(self, raw, log_std, eps):
+        """raw [B, 2] the actor's output before its clamp, log_std [2], eps [B, 2] the normal draw, float32 contiguous
+        -> (action [B, 2], lp [B]): persistent tensors per B, overwritten by the next call with that B.  One launch on the current
+        stream, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_sac_sample', dtype=torch.float32, device=self.device)
+        b = int(raw.shape[0]) if hasattr(raw, 'shape') and len(raw.shape) == 2 else None
+        ins = [arg('raw', raw, shape=(b, 2)), arg('log_std', log_std, shape=(2,)), arg('eps', eps, shape=(b, 2))]
+        out = self._sac_outputs('sample', b, ((b, 2), (b,)))
+        L.check(self.lib.hope_env_sac_sample(self.h, *ins, b, *(arg(k, x, shape=tuple(x.shape)) for k, x in zip(('action', 'lp'), out)), self._stream()),
+                'hope_env_sac_sample')
+        return out
+
+    def sac_critic(self, q1, q2, qt1, qt2, next_lp, reward, done, log_alpha, gamma):
+        """q1, q2 (the critics at the stored action), qt1, qt2 (the target critics at the sampled next action), next_lp, reward, done:
+        float32 [B] contiguous; log_alpha: a float64 scalar tensor on the device (read there)
+        -> (q_target [B], g_q1 [B], g_q2 [B], losses [2]): persistent per B.  Two launches, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_sac_critic', dtype=torch.float32, device=self.device)
+        b = int(q1.shape[0]) if hasattr(q1, 'shape') and len(q1.shape) == 1 else None
+        ins = [arg(k, x, shape=(b,)) for k, x in zip(('q1', 'q2', 'qt1', 'qt2', 'next_lp', 'reward', 'done'), (q1, q2, qt1, qt2, next_lp, reward, done))]
+        la = L.tensor_arg('hope_env_sac_critic', 'log_alpha', log_alpha, torch.float64, (), self.device)
+        out = self._sac_outputs('critic', b, ((b,), (b,), (b,), (2,)))
+        outs = [arg(k, x, shape=tuple(x.shape)) for k, x in zip(('q_target', 'g_q1', 'g_q2', 'losses'), out)]
+        L.check(self.lib.hope_env_sac_critic(self.h, *ins, la, float(gamma), b, *outs, self._stream()), 'hope_env_sac_critic')
+        return out
+
+    def sac_seed(self, q1, q2):
+        """q1, q2: the critics at the sampled action, float32 [B] -> (s1 [B], s2 [B]), the gradient of -mean(min(q1, q2)) at them:
+        persistent per B.  One launch, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_sac_seed', dtype=torch.float32, device=self.device)
+        b = int(q1.shape[0]) if hasattr(q1, 'shape') and len(q1.shape) == 1 else None
+        ins = [arg('q1', q1, shape=(b,)), arg('q2', q2, shape=(b,))]
+        out = self._sac_outputs('seed', b, ((b,), (b,)))
+        L.check(self.lib.hope_env_sac_seed(self.h, *ins, b, *(arg(k, x, shape=(b,)) for k, x in zip(('s1', 's2'), out)), self._stream()), 'hope_env_sac_seed')
+        return out
+
+    def sac_policy(self, raw, log_std, eps, q1, q2, g_action, log_alpha, target_entropy):
+        """raw, log_std, eps as for sac_sample; q1, q2 [B] the critics at the sampled action; g_action [B, 2] the gradient the seeds give
+        there; log_alpha: a float64 scalar tensor on the device
+        -> (g_raw [B, 2], g_log_std [2], g_log_alpha (a float64 scalar tensor), losses [2] = actor, temperature): persistent per B.
+        Two launches, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_sac_policy', dtype=torch.float32, device=self.device)
+        b = int(raw.shape[0]) if hasattr(raw, 'shape') and len(raw.shape) == 2 else None
+        ins = [arg('raw', raw, shape=(b, 2)), arg('log_std', log_std, shape=(2,)), arg('eps', eps, shape=(b, 2)), arg('q1', q1, shape=(b,)),
+               arg('q2', q2, shape=(b,)), arg('g_action', g_action, shape=(b, 2))]
+        la = L.tensor_arg('hope_env_sac_policy', 'log_alpha', log_alpha, torch.float64, (), self.device)
+        out = self._sac_outputs('policy', b, ((b, 2), (2,), None, (2,)))
+        outs = [arg('g_raw', out[0], shape=(b, 2)), arg('g_log_std', out[1], shape=(2,)),
+                L.tensor_arg('hope_env_sac_policy', 'g_log_alpha', out[2], torch.float64, (), self.device), arg('losses', out[3], shape=(2,))]
+        L.check(self.lib.hope_env_sac_policy(self.h, *ins, la, float(target_entropy), b, *outs, self._stream()), 'hope_env_sac_policy')
         return out
 
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------

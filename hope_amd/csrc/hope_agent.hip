@@ -1,5 +1,5 @@
 // hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
-// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring, PPO's minibatch -- and their host twins.  They share nothing with the
+// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring, PPO's minibatch, SAC's update -- and their host twins.  They share nothing with the
 // step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "hope_gae_kernel.h"
 #include "hope_ring_kernel.h"
 #include "hope_ppo_kernel.h"
+#include "hope_sac_kernel.h"
 
 using namespace hope;
 
@@ -23,6 +24,7 @@ using namespace hope;
 #define GAE_ON(h, name) HOPE_NEED((h)->gae.on, name, "the advantage block is off (hope_env_gae_enable first)")
 #define RING_ON(h, name) HOPE_NEED((h)->ring.on, name, "the transition ring is off (hope_env_ring_enable first)")
 #define PPO_ON(h, name) HOPE_NEED((h)->ppo.on, name, "the minibatch is off (hope_env_ppo_enable first)")
+#define SAC_ON(h, name) HOPE_NEED((h)->sac.on, name, "the SAC update is off (hope_env_sac_enable first)")
 
 // What every hope_env_*_enable does with a feature's device buffer: allocate it if absent, fill it (from `src`, or with zeros) and
 // wait.  On any failure the buffer is freed and *buf is null; the caller then puts the feature's struct back to "off" (*_free).
@@ -90,6 +92,11 @@ void hope::ring_free(hope_env_t* h) {
 void hope::ppo_free(hope_env_t* h) {
     if (h->ppo.part) hipFree(h->ppo.part);
     h->ppo = hope_env::Ppo{};
+}
+
+void hope::sac_free(hope_env_t* h) {
+    if (h->sac.part) hipFree(h->sac.part);
+    h->sac = hope_env::Sac{};
 }
 
 // the ring descriptor of a hope_env_ring_* call `name`: every tensor there and aligned to its element, n and T in range
@@ -707,6 +714,131 @@ int hope_ppo_loss_host(const float* raw, const float* log_std, const float* valu
     if (rc == HOPE_ENOMEM) return fail(rc, "hope_ppo_loss_host: out of memory for the chunk partials");
     if (rc != HOPE_OK)
         return fail(rc, "hope_ppo_loss_host: bad argument (a null raw / log_std / value / batch / output, a null action / old_lp / adv / v_target in batch, mb < 1, or a clip that is negative or not finite)");
+    return HOPE_OK;
+}
+
+// ---- SAC's update (include/hope_env.h; kernels: hope_sac_kernel.h, rule: hope_sac_core.h) ----
+int hope_env_sac_enable(hope_env_t* h, int max_batch) {
+    HOPE_ENTER(h, "hope_env_sac_enable");
+    if (max_batch < 1 || max_batch > HOPE_SAC_MAX_BATCH) return fail(HOPE_EINVAL, "hope_env_sac_enable: max_batch must be 1 .. " + std::to_string(HOPE_SAC_MAX_BATCH));
+    if (h->sac.on && max_batch <= h->sac.max_batch) return HOPE_OK;
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                         // calls in flight use the partials that a larger max_batch replaces
+    sac_free(h);
+    const int rc = device_buffer("hope_env_sac_enable", &h->sac.part, (size_t)SU_SUMS * (size_t)su_chunks(max_batch) * sizeof(double));
+    if (rc != HOPE_OK) { sac_free(h); return rc; }
+    h->sac.max_batch = max_batch;
+    h->sac.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_sac_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_sac_disable");
+    return feature_disable(h, sac_free);
+}
+
+// the batch of a hope_env_sac_* call `name`: 1 .. max_batch
+#define SAC_BATCH(h, batch, name)                                                                                                           \
+    do {                                                                                                                                    \
+        if ((batch) < 1 || (batch) > (h)->sac.max_batch)                                                                                    \
+            return fail(HOPE_EINVAL, std::string(name) + ": batch must be 1 .. max_batch (" + std::to_string((h)->sac.max_batch) + ")");  \
+    } while (0)
+
+int hope_env_sac_sample(hope_env_t* h, const float* raw, const float* log_std, const float* eps, int batch, float* action, float* lp, void* stream) {
+    HOPE_ENTER(h, "hope_env_sac_sample");
+    SAC_ON(h, "hope_env_sac_sample");
+    if (!raw || !log_std || !eps || !action || !lp) return fail(HOPE_EINVAL, "hope_env_sac_sample: null raw / log_std / eps / action / lp");
+    SAC_BATCH(h, batch, "hope_env_sac_sample");
+    const uintptr_t pair = (uintptr_t)raw | (uintptr_t)eps | (uintptr_t)action;
+    if ((pair | (uintptr_t)log_std | (uintptr_t)lp) & 3) return fail(HOPE_EINVAL, "hope_env_sac_sample: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_sac_sample, dim3((unsigned)su_chunks(batch)), dim3(64), 0, (hipStream_t)stream, raw, log_std, eps, batch, (pair & 7) ? 0 : 1, action, lp);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_sac_critic(hope_env_t* h, const float* q1, const float* q2, const float* qt1, const float* qt2, const float* next_lp, const float* reward,
+                        const float* done, const double* log_alpha, double gamma, int batch, float* q_target, float* g_q1, float* g_q2, float* losses,
+                        void* stream) {
+    HOPE_ENTER(h, "hope_env_sac_critic");
+    SAC_ON(h, "hope_env_sac_critic");
+    if (!q1 || !q2 || !qt1 || !qt2 || !next_lp || !reward || !done || !log_alpha || !q_target || !g_q1 || !g_q2 || !losses)
+        return fail(HOPE_EINVAL, "hope_env_sac_critic: null q1 / q2 / qt1 / qt2 / next_lp / reward / done / log_alpha / q_target / g_q1 / g_q2 / losses");
+    SAC_BATCH(h, batch, "hope_env_sac_critic");
+    if (!ga_finite(gamma)) return fail(HOPE_EINVAL, "hope_env_sac_critic: gamma must be finite");
+    const uintptr_t all = (uintptr_t)q1 | (uintptr_t)q2 | (uintptr_t)qt1 | (uintptr_t)qt2 | (uintptr_t)next_lp | (uintptr_t)reward | (uintptr_t)done |
+                          (uintptr_t)q_target | (uintptr_t)g_q1 | (uintptr_t)g_q2 | (uintptr_t)losses;
+    if ((all & 3) || ((uintptr_t)log_alpha & 7)) return fail(HOPE_EINVAL, "hope_env_sac_critic: misaligned buffer (log_alpha 8 bytes, every other tensor 4)");
+    HOPE_ON_DEVICE(h);
+    const long long nk = su_chunks(batch);                        // <= the partials' room: batch <= max_batch
+    hipLaunchKernelGGL(k_sac_critic, dim3((unsigned)nk), dim3(64), 0, (hipStream_t)stream, q1, q2, qt1, qt2, next_lp, reward, done, log_alpha, gamma, batch,
+                       q_target, g_q1, g_q2, nk, h->sac.part);
+    hipLaunchKernelGGL(k_sac_merge<SU_CRITIC_SUMS>, dim3(1), dim3(64), 0, (hipStream_t)stream, nk, (double)batch, h->sac.part, log_alpha, losses,
+                       (float*)nullptr, (double*)nullptr);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_sac_seed(hope_env_t* h, const float* q1, const float* q2, int batch, float* s1, float* s2, void* stream) {
+    HOPE_ENTER(h, "hope_env_sac_seed");
+    SAC_ON(h, "hope_env_sac_seed");
+    if (!q1 || !q2 || !s1 || !s2) return fail(HOPE_EINVAL, "hope_env_sac_seed: null q1 / q2 / s1 / s2");
+    SAC_BATCH(h, batch, "hope_env_sac_seed");
+    if (((uintptr_t)q1 | (uintptr_t)q2 | (uintptr_t)s1 | (uintptr_t)s2) & 3) return fail(HOPE_EINVAL, "hope_env_sac_seed: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_sac_seed, dim3((unsigned)su_chunks(batch)), dim3(64), 0, (hipStream_t)stream, q1, q2, batch, s1, s2);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_env_sac_policy(hope_env_t* h, const float* raw, const float* log_std, const float* eps, const float* q1, const float* q2, const float* g_action,
+                        const double* log_alpha, double target_entropy, int batch, float* g_raw, float* g_log_std, double* g_log_alpha, float* losses,
+                        void* stream) {
+    HOPE_ENTER(h, "hope_env_sac_policy");
+    SAC_ON(h, "hope_env_sac_policy");
+    if (!raw || !log_std || !eps || !q1 || !q2 || !g_action || !log_alpha || !g_raw || !g_log_std || !g_log_alpha || !losses)
+        return fail(HOPE_EINVAL, "hope_env_sac_policy: null raw / log_std / eps / q1 / q2 / g_action / log_alpha / g_raw / g_log_std / g_log_alpha / losses");
+    SAC_BATCH(h, batch, "hope_env_sac_policy");
+    if (!ga_finite(target_entropy)) return fail(HOPE_EINVAL, "hope_env_sac_policy: target_entropy must be finite");
+    const uintptr_t pair = (uintptr_t)raw | (uintptr_t)eps | (uintptr_t)g_action | (uintptr_t)g_raw;
+    const uintptr_t all = pair | (uintptr_t)log_std | (uintptr_t)q1 | (uintptr_t)q2 | (uintptr_t)g_log_std | (uintptr_t)losses;
+    if ((all & 3) || (((uintptr_t)log_alpha | (uintptr_t)g_log_alpha) & 7))
+        return fail(HOPE_EINVAL, "hope_env_sac_policy: misaligned buffer (log_alpha and g_log_alpha 8 bytes, every other tensor 4)");
+    HOPE_ON_DEVICE(h);
+    const long long nk = su_chunks(batch);                        // <= the partials' room: batch <= max_batch
+    hipLaunchKernelGGL(k_sac_policy, dim3((unsigned)nk), dim3(64), 0, (hipStream_t)stream, raw, log_std, eps, q1, q2, g_action, log_alpha, target_entropy, batch,
+                       (pair & 7) ? 0 : 1, g_raw, nk, h->sac.part);
+    hipLaunchKernelGGL(k_sac_merge<SU_POLICY_SUMS>, dim3(1), dim3(64), 0, (hipStream_t)stream, nk, (double)batch, h->sac.part, log_alpha, losses, g_log_std,
+                       g_log_alpha);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+int hope_sac_sample_host(const float* raw, const float* log_std, const float* eps, int64_t batch, float* action, float* lp) {
+    const int rc = su_sample_host(raw, log_std, eps, batch, action, lp);
+    if (rc != HOPE_OK) return fail(rc, "hope_sac_sample_host: bad argument (a null raw / log_std / eps / action / lp, or batch < 1)");
+    return HOPE_OK;
+}
+
+int hope_sac_critic_host(const float* q1, const float* q2, const float* qt1, const float* qt2, const float* next_lp, const float* reward, const float* done,
+                         const double* log_alpha, double gamma, int64_t batch, float* q_target, float* g_q1, float* g_q2, float* losses) {
+    const int rc = su_critic_host(q1, q2, qt1, qt2, next_lp, reward, done, log_alpha, gamma, batch, q_target, g_q1, g_q2, losses);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_sac_critic_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK) return fail(rc, "hope_sac_critic_host: bad argument (a null input or output, batch < 1, or a gamma that is not finite)");
+    return HOPE_OK;
+}
+
+int hope_sac_seed_host(const float* q1, const float* q2, int64_t batch, float* s1, float* s2) {
+    const int rc = su_seed_host(q1, q2, batch, s1, s2);
+    if (rc != HOPE_OK) return fail(rc, "hope_sac_seed_host: bad argument (a null q1 / q2 / s1 / s2, or batch < 1)");
+    return HOPE_OK;
+}
+
+int hope_sac_policy_host(const float* raw, const float* log_std, const float* eps, const float* q1, const float* q2, const float* g_action,
+                         const double* log_alpha, double target_entropy, int64_t batch, float* g_raw, float* g_log_std, double* g_log_alpha, float* losses) {
+    const int rc = su_policy_host(raw, log_std, eps, q1, q2, g_action, log_alpha, target_entropy, batch, g_raw, g_log_std, g_log_alpha, losses);
+    if (rc == HOPE_ENOMEM) return fail(rc, "hope_sac_policy_host: out of memory for the chunk partials");
+    if (rc != HOPE_OK) return fail(rc, "hope_sac_policy_host: bad argument (a null input or output, batch < 1, or a target_entropy that is not finite)");
     return HOPE_OK;
 }
 

@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -232,6 +232,9 @@ struct hope_env {
     // PPO's minibatch (hope_ppo_kernel.h): part = the chunk partials of the loss call's four sums ([4][chunks of the call], room for
     // ceil(max_batch / 64) chunks)
     struct Ppo { bool on = false; double* part = nullptr; int max_batch = 0; } ppo;
+    // SAC's update (hope_sac_kernel.h): part = the chunk partials of the critic call's two sums and the policy call's four ([4][chunks
+    // of the call], room for ceil(max_batch / 64) chunks)
+    struct Sac { bool on = false; double* part = nullptr; int max_batch = 0; } sac;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -248,4 +251,5 @@ void evalt_free(hope_env_t* h);
 void gae_free(hope_env_t* h);
 void ring_free(hope_env_t* h);
 void ppo_free(hope_env_t* h);
+void sac_free(hope_env_t* h);
 }  // namespace hope

@@ -525,11 +525,19 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None):
+                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, sac_update=None):
         """chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used
-        ring: as HopeRollout; with 'device' the batch is one k_ring_sample launch"""
+        ring: as HopeRollout; with 'device' the batch is one k_ring_sample launch
+        sac_update: None -- the agent's update computes the sample, the Q target and the losses in torch and autograd differentiates
+        them; 'device' -- the agent's `update_block` becomes an agent_glue.DeviceSacUpdate over `env`: eight launches between the
+        network forwards, autograd through the networks only."""
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring)
+        self.sac_update = G.make_sac_update(sac_update, env)
+        if self.sac_update is not None:
+            if not hasattr(agent, 'update_block'):
+                raise ValueError("sac_update='device' needs an agent with an update block (BatchedSAC)")
+            agent.update_block = self.sac_update
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

@@ -924,6 +924,61 @@ int hope_ppo_gather_host(const hope_ring_t *ring, const float *adv, const float 
 int hope_ppo_loss_host(const float *raw, const float *log_std, const float *value, const hope_ppo_batch_t *batch, int64_t mb,
                        double clip, float *g_raw, float *g_log_std, float *g_value, float *losses);
 
+/* ---- SAC's update (additive to ABI 8) --------------------------------------------------------------------------------------------
+ * What BatchedSAC.update does between its seven network forwards (the reference's SACAgent.update,
+ * src/model/agent/sac_agent.py:250-337): the reparameterised sample with its log-probability, the Q target with the two critics'
+ * squared errors and their gradients, the gradient of the actor loss at the two critic outputs, and -- from what autograd returns
+ * for it at the sampled action -- the gradients of the actor loss at the actor's output and log_std and of the temperature loss at
+ * log_alpha.  Kernels: k_sac_sample, k_sac_critic, k_sac_seed, k_sac_policy (a lane per item) and k_sac_merge (one wave: the chunk
+ * partials' trees).  The sums have one arithmetic order, independent of the launch geometry.  The handle holds the chunk partials
+ * only.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  The rule and the bit-equal
+ * host twins: hope_amd/csrc/hope_sac_core.h, DESIGN.md 5l. */
+#define HOPE_SAC_MAX_BATCH 1048576
+/* allocate the chunk partials (4 x ceil(max_batch / 64) doubles), 1 <= max_batch <= HOPE_SAC_MAX_BATCH.  On an enabled handle a
+ * larger max_batch reallocates, an equal or smaller one changes nothing.  Host-synchronous. */
+int hope_env_sac_enable(hope_env_t *h, int max_batch);
+/* free them.  Host-synchronous (calls in flight use them). */
+int hope_env_sac_disable(hope_env_t *h);
+/* The four calls below are asynchronous on `stream`; they wait for nothing, never synchronise the host and do not join a deferred
+ * search.  Every pointer is DEVICE memory, float32 and contiguous, aligned to 4 bytes; log_alpha and g_log_alpha are float64 scalars
+ * aligned to 8 bytes (the temperature is read on the device).  1 <= batch <= max_batch.  HOPE_ESTATE before hope_env_sac_enable;
+ * HOPE_EINVAL for a NULL or misaligned pointer, a batch out of range or a gamma / target_entropy that is not finite; on any error
+ * nothing is launched and the handle stays usable.  With the [batch][2] arrays of a call 8-byte aligned a lane moves a pair at
+ * once; the results do not depend on that.  The critic and policy calls use the handle's partials, so calls belong on one stream.
+ *
+ * raw [batch][2] is the actor's output BEFORE its clamp to [-1, 1], log_std [2], eps [batch][2] the standard normal draw:
+ * action [batch][2] = clamp(clamp(raw) + exp(log_std) eps), lp [batch] its log-probability summed over the pair.  One launch. */
+int hope_env_sac_sample(hope_env_t *h, const float *raw, const float *log_std, const float *eps, int batch, float *action, float *lp,
+                        void *stream);
+/* q1, q2 [batch]: the critics at the stored action; qt1, qt2 [batch]: the target critics at the sampled next action, next_lp
+ * [batch] its log-probability; reward, done [batch].  Outputs: q_target [batch] = reward + (1 - done) gamma (min(qt1, qt2) -
+ * alpha next_lp), g_q1, g_q2 [batch] the gradients of the two mean squared errors at q1 and q2, losses [2] the two errors.  Two
+ * launches. */
+int hope_env_sac_critic(hope_env_t *h, const float *q1, const float *q2, const float *qt1, const float *qt2, const float *next_lp,
+                        const float *reward, const float *done, const double *log_alpha, double gamma, int batch, float *q_target,
+                        float *g_q1, float *g_q2, float *losses, void *stream);
+/* q1, q2 [batch]: the critics at the sampled action.  s1, s2 [batch]: the gradient of -mean(min(q1, q2)) at q1 and q2 (a tie gives
+ * half to each).  One launch. */
+int hope_env_sac_seed(hope_env_t *h, const float *q1, const float *q2, int batch, float *s1, float *s2, void *stream);
+/* raw, log_std, eps as for the sample; q1, q2 as for the seed; g_action [batch][2]: the gradient that the seeds give at the sampled
+ * action.  Outputs: g_raw [batch][2] and g_log_std [2], the gradients of the actor loss mean(alpha lp - min(q1, q2)) at raw and
+ * log_std; g_log_alpha, the gradient of the temperature loss at log_alpha (float64); losses [2] = {actor loss, temperature loss}.
+ * Two launches. */
+int hope_env_sac_policy(hope_env_t *h, const float *raw, const float *log_std, const float *eps, const float *q1, const float *q2,
+                        const float *g_action, const double *log_alpha, double target_entropy, int batch, float *g_raw,
+                        float *g_log_std, double *g_log_alpha, float *losses, void *stream);
+/* The same over HOST arrays: pure host code from the same source, no handle, no device; bit-equal to the kernels.  No alignment
+ * requirements, no upper bound on batch.  HOPE_EINVAL for a NULL pointer, batch < 1, or a gamma / target_entropy that is not
+ * finite. */
+int hope_sac_sample_host(const float *raw, const float *log_std, const float *eps, int64_t batch, float *action, float *lp);
+int hope_sac_critic_host(const float *q1, const float *q2, const float *qt1, const float *qt2, const float *next_lp,
+                         const float *reward, const float *done, const double *log_alpha, double gamma, int64_t batch,
+                         float *q_target, float *g_q1, float *g_q2, float *losses);
+int hope_sac_seed_host(const float *q1, const float *q2, int64_t batch, float *s1, float *s2);
+int hope_sac_policy_host(const float *raw, const float *log_std, const float *eps, const float *q1, const float *q2,
+                         const float *g_action, const double *log_alpha, double target_entropy, int64_t batch, float *g_raw,
+                         float *g_log_std, double *g_log_alpha, float *losses);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
