@@ -31,6 +31,13 @@ PPO_MAX_BATCH = 1 << 20
 SAC_MAX_BATCH = 1 << 20
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
+# hope_env_step_plan: words ahead of the chains / of a chain's scene ids, flag bits, kernel numbers
+STEPPLAN_HEAD, STEPPLAN_CHAIN_HEAD = 3, 5
+STEPPLAN_SPLIT, STEPPLAN_PIPE, STEPPLAN_FUSE_KIN, STEPPLAN_AUTO_SUBS = 0x1, 0x2, 0x4, 0x8
+STEPPLAN_MOTION_ONE_LAUNCH, STEPPLAN_MOTION_FUSED_KIN, STEPPLAN_MOTION_TIMING, STEPPLAN_MOTION_SPLIT, STEPPLAN_MOTION_PAIR = 0, 1, 2, 3, 4
+STEPPLAN_OBS_IN_STEP, STEPPLAN_OBS_SPLIT, STEPPLAN_OBS_PAIR = 0, 1, 2
+MOTION_KERNELS = ('one_launch', 'one_launch_fused_kin', 'timing', 'split_one_scene', 'pair')
+OBS_KERNELS = ('in_step', 'split_one_scene', 'pair')
 
 
 class HopeError(RuntimeError):
@@ -92,6 +99,7 @@ PROTOTYPES = {
     'hope_env_upload_tables': (I, [P] * 4),
     'hope_env_set_scenes': (I, [P, P, I] + [P] * 5),
     'hope_env_step': (I, [P, P, P, U32, C.POINTER(StepOut), P]),
+    'hope_env_step_plan': (I, [P, U32, I, P, I]),
     'hope_env_wait_rs': (I, [P, P]),
     'hope_env_last_step': (I, [P, P]),
     'hope_env_wait_rs_step': (I, [P, U64, P]),

@@ -354,6 +354,28 @@ class ParkingBatch:
         L.check(self.lib.hope_env_step(self.h, xp, ap, stages, C.byref(self._out), self._stream()), 'hope_env_step')
         return self
 
+    def step_plan(self, stages=L.STAGE_ALL, has_action=True, defer_rs=False):
+        """the launch plan of the next step(stages=..., defer_rs=...) (has_action=False: of reset_obs) as the library computes it
+        (hope_env_step_plan: a test hook; nothing is launched).  -> dict(split, pipe, fuse_kin, auto_subs: bool, chains: list, in
+        launch order, of dict(tile_class, tile_cap, motion, obs: names of _lib.MOTION_KERNELS / OBS_KERNELS, scenes: int32 ids in
+        list order -- entries 2b and 2b + 1 share a wave of the pair kernels))"""
+        if defer_rs:
+            stages |= L.DEFER_RS
+        if self.image and (stages & L.STAGE_ALL) == L.STAGE_ALL:
+            stages |= L.STAGE_IMG
+        stages |= self._action_bits
+        out = np.zeros(L.STEPPLAN_HEAD + 2 * L.STEPPLAN_CHAIN_HEAD + self.n, np.int32)
+        L.check(self.lib.hope_env_step_plan(self.h, stages, 1 if has_action else 0, out.ctypes, len(out)), 'hope_env_step_plan')
+        flags, chains, w = int(out[1]), [], L.STEPPLAN_HEAD
+        for _ in range(int(out[2])):
+            c, cap, motion, obs, m = (int(v) for v in out[w:w + L.STEPPLAN_CHAIN_HEAD])
+            w += L.STEPPLAN_CHAIN_HEAD
+            chains.append(dict(tile_class=c, tile_cap=cap, motion=L.MOTION_KERNELS[motion], obs=L.OBS_KERNELS[obs], scenes=out[w:w + m].copy()))
+            w += m
+        assert w == out[0]
+        return dict(split=bool(flags & L.STEPPLAN_SPLIT), pipe=bool(flags & L.STEPPLAN_PIPE), fuse_kin=bool(flags & L.STEPPLAN_FUSE_KIN),
+                    auto_subs=bool(flags & L.STEPPLAN_AUTO_SUBS), chains=chains)
+
     def last_step(self):
         """sequence number of the most recent step() / reset_obs() of this handle (hope_env_last_step)"""
         g = C.c_uint64(0)

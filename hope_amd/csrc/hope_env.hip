@@ -986,6 +986,7 @@ static int rebuild_class_lists(hope_env_t* h) {
         }
     }
     h->cls_count[0] = (int)l0.size(); h->cls_count[1] = (int)l1.size();
+    h->cls_list_host[0] = l0; h->cls_list_host[1] = l1;     // (host mirror: hope_env_step_plan)
     if (!l0.empty()) HIPCHK(hipMemcpy(h->cls_list[0], l0.data(), l0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (!l1.empty()) HIPCHK(hipMemcpy(h->cls_list[1], l1.data(), l1.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->slot_cls, h->slot_cls_host.data(), (size_t)h->n, hipMemcpyHostToDevice));
@@ -1084,6 +1085,10 @@ constexpr int AUTO_SUBS_RANGE[4] = {32768, 1 << 30, 4096, 32768};
 
 enum MotionKernel { MOTION_ONE_LAUNCH, MOTION_FUSED_KIN, MOTION_TIMING, MOTION_SPLIT, MOTION_PAIR };
 enum ObsKernel { OBS_IN_STEP, OBS_SPLIT, OBS_PAIR };     // OBS_IN_STEP: the one-launch step kernel computes the observation
+static_assert(MOTION_ONE_LAUNCH == HOPE_STEPPLAN_MOTION_ONE_LAUNCH && MOTION_FUSED_KIN == HOPE_STEPPLAN_MOTION_FUSED_KIN &&
+              MOTION_TIMING == HOPE_STEPPLAN_MOTION_TIMING && MOTION_SPLIT == HOPE_STEPPLAN_MOTION_SPLIT && MOTION_PAIR == HOPE_STEPPLAN_MOTION_PAIR &&
+              OBS_IN_STEP == HOPE_STEPPLAN_OBS_IN_STEP && OBS_SPLIT == HOPE_STEPPLAN_OBS_SPLIT && OBS_PAIR == HOPE_STEPPLAN_OBS_PAIR,
+              "hope_env_step_plan reports these numbers (include/hope_env.h)");
 
 struct StepPlan {
     struct Chain {
@@ -1104,6 +1109,12 @@ struct StepPlan {
     bool fuse_kin;                // one-launch step kernel with the kinematics fused in
     bool auto_subs;               // two sub-chains of one tile class
 };
+
+// cycle accounting build (tools/step_timing.py); read once per process
+static bool step_timing_build() {
+    static const bool on = getenv("HOPE_STEP_TIMING") != nullptr;
+    return on;
+}
 
 // What one step enqueues (no HIP calls).
 static StepPlan plan_step(const hope_env_t* h, uint32_t stages, bool want_rs, bool overlap, int has_action, bool step_timing) {
@@ -1178,7 +1189,7 @@ static int enqueue_step(hope_env_t* h, const void* actions, const uint8_t* activ
     const uint8_t* active_rs = active ? h->active_snap : nullptr;   // what the Reeds-Shepp chain reads instead of the caller's mask
     const bool of64 = h->flags & HOPE_F_OBS_F64, af64 = h->flags & HOPE_F_ACTION_F64;
     const dim3 block(WAVE);
-    static const bool step_timing = getenv("HOPE_STEP_TIMING") != nullptr;      // cycle accounting build (tools/step_timing.py)
+    const bool step_timing = step_timing_build();
     const bool want_rs = (stages & HOPE_STAGE_RS) && out->rs_word;
     const StepPlan pl = plan_step(h, stages, want_rs, overlap, has_action, step_timing);
     auto stream = [&](Role r) { return r == ROLE_CALLER ? s : h->side[r]; };
@@ -2460,6 +2471,31 @@ int hope_env_step(hope_env_t* h, const void* actions, const uint8_t* active, uin
                   const hope_step_out* out, void* stream) {
     HOPE_ENTER_AS(h, "hope_env_step", "null argument");
     return launch_step(h, actions, active, stages, out, stream, 1);
+}
+
+// Test hook: the plan the next hope_env_step / hope_env_reset_obs with these stages would enqueue (launch_step's stage rule, then
+// plan_step with enqueue_step's arguments; the search as with out->rs_word given).  No HIP call, no state change.
+int hope_env_step_plan(hope_env_t* h, uint32_t stages, int has_action, int32_t* out, int cap) {
+    HOPE_ENTER(h, "hope_env_step_plan");
+    if (!out || cap < 0) return fail(HOPE_EINVAL, "hope_env_step_plan: null argument");
+    if (!h->have_scenes) return fail(HOPE_ESTATE, "hope_env_step_plan: hope_env_set_scenes has not been called");
+    if (!has_action) stages &= ~HOPE_STAGE_MOTION;
+    if (stages & HOPE_STAGE_RS) stages |= HOPE_STAGE_REWARD;
+    const StepPlan pl = plan_step(h, stages, (stages & HOPE_STAGE_RS) != 0, (h->flags & HOPE_F_OVERLAP) != 0, has_action ? 1 : 0, step_timing_build());
+    long long need = HOPE_STEPPLAN_HEAD;
+    for (int i = 0; i < pl.n_chain; i++) need += HOPE_STEPPLAN_CHAIN_HEAD + (pl.chain[i].b - pl.chain[i].a);
+    if (need > cap) return fail(HOPE_EINVAL, "hope_env_step_plan: cap is too small: " + std::to_string(need) + " words are needed");
+    int32_t* w = out;
+    *w++ = (int32_t)need;
+    *w++ = (pl.split ? HOPE_STEPPLAN_SPLIT : 0) | (pl.pipe ? HOPE_STEPPLAN_PIPE : 0) | (pl.fuse_kin ? HOPE_STEPPLAN_FUSE_KIN : 0) | (pl.auto_subs ? HOPE_STEPPLAN_AUTO_SUBS : 0);
+    *w++ = pl.n_chain;
+    for (int i = 0; i < pl.n_chain; i++) {
+        const StepPlan::Chain& ch = pl.chain[i];
+        *w++ = ch.c; *w++ = ch.tile_cap; *w++ = (int32_t)ch.motion; *w++ = (int32_t)ch.obs_kernel; *w++ = ch.b - ch.a;
+        const std::vector<int32_t>& l = h->cls_list_host[ch.c];
+        for (int j = ch.a; j < ch.b; j++) *w++ = l[j];
+    }
+    return HOPE_OK;
 }
 
 int hope_env_wait_rs(hope_env_t* h, void* stream) {

@@ -108,6 +108,7 @@ struct hope_env {
     // per tile class (0: n_obst <= SMALL_TILE, 1: larger) dense scene lists; classes are static between set_scenes calls
     int32_t* cls_list[2] = {nullptr, nullptr};
     int cls_count[2] = {0, 0};
+    std::vector<int32_t> cls_list_host[2];       // the same lists on the host (hope_env_step_plan)
     std::vector<int32_t> n_obst_host;
     std::vector<uint8_t> slot_cls_host;          // draw / launch class of every scene slot (0: <= 32 obstacles, 1: larger lots)
     uint8_t* slot_cls = nullptr;                 // the same on the device

@@ -380,6 +380,31 @@ int hope_debug_math(int fn, int n, const double *a, const double *b, double *out
  * n_obst is read by fn 5 only (0..32).  HOPE_EINVAL for n < 0, a null pointer, an unknown fn, n_obst out of range.  Additive to ABI 8. */
 int hope_debug_geom(int fn, int n, int n_obst, const double *in, void *out, void *stream);
 
+/* Test hook: the launch plan of the NEXT hope_env_step (has_action != 0) or hope_env_reset_obs (has_action == 0) with these `stages`,
+ * computed by the function the step itself calls, from the same handle state and the same HOPE_SPLIT_MIN / HOPE_AUTO_CHAINS reads, for a
+ * step whose out->rs_word is given.  No HIP call, no change of state.  out: HOST array of `cap` int32 words --
+ *   [0] words written  [1] HOPE_STEPPLAN_* flag bits  [2] number of chains, then per chain, in launch order:
+ *   tile class (0: <= 32 obstacles), LDS tile capacity, motion kernel (HOPE_STEPPLAN_MOTION_*), observation kernel (HOPE_STEPPLAN_OBS_*),
+ *   number of scenes m, and the m scene ids in the order of the chain's launch list (block b of a one-scene kernel steps entry b; a
+ *   wave of the pair kernels steps entries 2b and 2b + 1).
+ * 3 + 2 * 5 + N words always suffice.  HOPE_EINVAL for a null `out` or a `cap` below the words needed (the message gives the number; nothing
+ * is written), HOPE_ESTATE before hope_env_set_scenes.  Additive to ABI 8. */
+#define HOPE_STEPPLAN_HEAD 3
+#define HOPE_STEPPLAN_CHAIN_HEAD 5
+#define HOPE_STEPPLAN_SPLIT 0x1               /* two-launch step kernel: motion launch, then the observation launch */
+#define HOPE_STEPPLAN_PIPE 0x2                /* pipelined (HOPE_DEFER_RS): the search streams stay unjoined */
+#define HOPE_STEPPLAN_FUSE_KIN 0x4            /* one-launch step kernel that computes its sub-step poses itself: no k_kinematics launch */
+#define HOPE_STEPPLAN_AUTO_SUBS 0x8           /* two sub-chains of one tile class */
+#define HOPE_STEPPLAN_MOTION_ONE_LAUNCH 0     /* k_env_step, all parts, behind k_kinematics (or action-less) */
+#define HOPE_STEPPLAN_MOTION_FUSED_KIN 1      /* k_env_step, all parts, kinematics fused in */
+#define HOPE_STEPPLAN_MOTION_TIMING 2         /* the cycle-accounting build of k_env_step (HOPE_STEP_TIMING) */
+#define HOPE_STEPPLAN_MOTION_SPLIT 3          /* k_env_step, motion part only, one scene per wave */
+#define HOPE_STEPPLAN_MOTION_PAIR 4           /* k_motion_pair, two scenes per wave */
+#define HOPE_STEPPLAN_OBS_IN_STEP 0           /* the one-launch step kernel computes the observation */
+#define HOPE_STEPPLAN_OBS_SPLIT 1             /* k_env_step, observation part only */
+#define HOPE_STEPPLAN_OBS_PAIR 2              /* k_obs_pair */
+int hope_env_step_plan(hope_env_t *h, uint32_t stages, int has_action, int32_t *out, int cap);
+
 /* Test hook (pure host code, no device needed): the count-interval table hope_env_upload_tables derives from dist_star / hull_base for
  * the action-mask stage (hope_amd/csrc/hope_step_kernel.h MASK_LUT_*): lut_out [(120 * 128 + 1)][32] uint16, scale_out [120] bins per
  * metre.  tests/test_mask_lut.py checks its bracketing property against the float64 table (action_mask.py:166-177).  HOPE_EINVAL, with

@@ -89,7 +89,7 @@ def test_create_rejects_bad_arguments_and_removed_flags():
 @pytest.mark.parametrize('case', ['step_before_tables', 'step_before_scenes', 'n_obst_too_large', 'scene_id_out_of_range', 'null_arrays',
                                   'img_without_flag', 'redraw_without_reset', 'redraw_without_pool', 'pool_without_class', 'null_out',
                                   'null_actions', 'profile_without_flag', 'stale_wait_rs_step', 'null_masks', 'commit_beyond_staging',
-                                  'bad_draw_class', 'restore_without_pool', 'debug_geom_bad_arguments'])
+                                  'bad_draw_class', 'restore_without_pool', 'debug_geom_bad_arguments', 'step_plan_bad_arguments'])
 def test_misuse_returns_its_code_and_leaves_the_handle_usable(case):
     lib = _lib()
     arrays = _scene_arrays()
@@ -216,6 +216,20 @@ def test_misuse_returns_its_code_and_leaves_the_handle_usable(case):
         assert lib.hope_debug_geom(5, 1, 33, pa, po, None) == EINVAL and 'n_obst' in _err()
         assert lib.hope_debug_geom(5, 1, -1, pa, po, None) == EINVAL
         assert lib.hope_debug_geom(5, 0, 32, pa, po, None) == OK                                 # (no case: nothing is launched)
+    elif case == 'step_plan_bad_arguments':
+        full = L.STEPPLAN_HEAD + 2 * L.STEPPLAN_CHAIN_HEAD + N
+        plan = np.full(full, -77, np.int32)
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, None, full) == EINVAL
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, plan.ctypes.data, -1) == EINVAL
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, plan.ctypes.data, N) == EINVAL and 'cap is too small' in _err()
+        assert (plan == -77).all()                                                               # a refused call writes nothing
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, plan.ctypes.data, full) == OK
+        assert L.STEPPLAN_HEAD + L.STEPPLAN_CHAIN_HEAD + N <= plan[0] <= full and (plan[plan[0]:] == -77).all()
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, plan.ctypes.data, int(plan[0]) - 1) == EINVAL
+        assert lib.hope_env_step_plan(h, L.STAGE_ALL, 1, plan.ctypes.data, int(plan[0])) == OK   # exactly the words needed
+        fresh = _create()
+        assert lib.hope_env_step_plan(fresh, L.STAGE_ALL, 1, plan.ctypes.data, full) == ESTATE and 'set_scenes' in _err()
+        assert lib.hope_env_destroy(fresh) == OK
 
     # ---- the handle still works: its next steps equal a fresh twin's -------------------------------------------------------------
     if case == 'pool_without_class':

@@ -328,8 +328,10 @@ FORMS = {'one_launch': ('1000000000', False), 'two_launch_pair_kernels': ('1', F
 
 
 def _stages():
+    """STAGE_ALL: without the search stage the launcher takes the one-launch form whatever HOPE_SPLIT_MIN says (the Reeds-Shepp
+    outputs are not compared here)"""
     from hope_amd import _lib as L
-    return L.STAGE_MOTION | L.STAGE_OBS | L.STAGE_REWARD
+    return L.STAGE_ALL
 
 
 def _oracle(sc, n=None):
@@ -366,14 +368,44 @@ def scene_reference(moving):
     return sc, census, ref_reset, ref_step
 
 
-def _env(sc, large=False):
+def _env(sc, form=None):
+    """form None: the classes as set_scene_arrays leaves them (all small; the overlapped handle hands the last 42 % of the ids to the
+    large-tile chain).  A name of FORMS: both chains non-empty with the ADVERSARIAL scenes in the chain whose kernel the form names --
+    the small-tile chain (pair kernels) or, `large`, the large-tile chain -- and the plain scenes in the other, nothing handed over"""
     from hope_amd import ParkingBatch
     n = len(sc['nob'])
-    env = ParkingBatch(n, MO, obs_dtype=torch.float64, action_dtype=torch.float64, overlap=True)
-    env.set_scene_arrays(np.arange(n), sc['start'], sc['dest'], sc['bbox'], sc['verts'], sc['nob'])
-    if large:
-        env.set_draw_class(np.arange(n), 1)
+    large = form is not None and FORMS[form][1]
+    if form is not None and FORMS[form][0] == '1':
+        os.environ['HOPE_CLS1_FRAC'] = '0'
+    try:
+        env = ParkingBatch(n, MO, obs_dtype=torch.float64, action_dtype=torch.float64, overlap=True)
+        env.set_scene_arrays(np.arange(n), sc['start'], sc['dest'], sc['bbox'], sc['verts'], sc['nob'])
+        if form is not None and FORMS[form][0] == '1':
+            env.set_draw_class(np.nonzero(sc['adv'] if large else ~sc['adv'])[0], 1)
+    finally:
+        os.environ.pop('HOPE_CLS1_FRAC', None)
     return env
+
+
+KERNELS = {'one_launch': ('one_launch_fused_kin', 'in_step', None), 'two_launch_pair_kernels': ('pair', 'pair', 32),
+           'two_launch_large_tile': ('split_one_scene', 'split_one_scene', MO)}
+
+
+def _assert_routing(env, sc, form, has_action=True, every=True):
+    """through the launch plan: the adversarial scenes (`every`: all of them, else some) are stepped by the kernels the form names"""
+    plan = env.step_plan(stages=_stages(), has_action=has_action)
+    motion, obs, cap = KERNELS[form]
+    if not has_action and motion == 'pair':
+        motion = 'split_one_scene'                                # (the action-less step has no pair motion kernel; its observation is k_obs_pair's)
+    named = [c for c in plan['chains'] if (c['motion'], c['obs']) == (motion, obs) and cap in (None, c['tile_cap'])]
+    ids = np.concatenate([c['scenes'] for c in named]) if named else np.zeros(0, np.int32)
+    adv = np.nonzero(sc['adv'])[0]
+    inside = np.isin(adv, ids)
+    print(f"launch plan ({form}, {'step' if has_action else 'reset_obs'}): split {plan['split']}, fused kinematics {plan['fuse_kin']}; " +
+          '; '.join(f"tile class {c['tile_class']} capacity {c['tile_cap']}: {len(c['scenes'])} scenes, motion {c['motion']}, observation {c['obs']}"
+                    for c in plan['chains']) + f'; adversarial scenes in the named kernel {int(inside.sum())} of {len(adv)}')
+    assert plan['split'] == (FORMS[form][0] == '1') and len(plan['chains']) == 2
+    assert inside.all() if every else inside.sum() >= 0.4 * len(adv)
 
 
 def _check(env, ref, tag):
@@ -403,9 +435,11 @@ def test_start_pose_touching_reset_and_zero_action_step(form):
     split, large = FORMS[form]
     os.environ['HOPE_SPLIT_MIN'] = split
     try:
-        env = _env(sc, large)
+        env = _env(sc, form)
+        _assert_routing(env, sc, form, has_action=False)
         env.reset_obs(stages=_stages())
         _check(env, ref_reset, (form, 'reset'))
+        _assert_routing(env, sc, form)
         env.step(torch.from_numpy(sc['action']).to(env.device), stages=_stages())
         _check(env, ref_step, (form, 'zero action'))
         _report(f'reset_obs ({form})', sc, census['reset'], ref_reset)
@@ -425,9 +459,10 @@ def test_moving_step_touching_at_a_sub_step(form):
     split, large = FORMS[form]
     os.environ['HOPE_SPLIT_MIN'] = split
     try:
-        env = _env(sc, large)
+        env = _env(sc, form)
         env.reset_obs(stages=_stages())
         _check(env, ref_reset, (form, 'reset'))
+        _assert_routing(env, sc, form)
         env.step(torch.from_numpy(sc['action']).to(env.device), stages=_stages())
         _check(env, ref_step, (form, 'moving'))
         _report(f'moving step ({form})', sc, census['step'], ref_step)
@@ -488,6 +523,8 @@ def test_turnover_onto_a_start_pose_that_touches(form):
         env.set_redraw_seed(7)
         env.reset_obs(stages=_stages())
         env.upload_state(t=np.full(n, 200, np.int32))             # every episode that goes on runs out of time in this step
+        # (the slots draw from the pool's small class, so every scene keeps its class: the last 42 % of the ids are in the large-tile chain)
+        _assert_routing(env, sc, form, every=form == 'one_launch')
         a = torch.from_numpy(sc['action']).to(env.device)
         env.step(a, stages=_stages(), auto_reset=True, fresh=True)
         torch.cuda.synchronize()
