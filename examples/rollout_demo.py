@@ -50,6 +50,9 @@ def main():
                     help="also run a short SAC loop with the update's arithmetic on the device (sac_update='device': k_sac_sample, k_sac_critic, "
                          'k_sac_seed, k_sac_policy and k_sac_merge between the network forwards instead of the elementwise lines and autograd '
                          'through them)')
+    ap.add_argument('--device-actor', action='store_true',
+                    help="also run a short PPO loop with the actor's inference forward on the device (actor='device': one fused "
+                         'k_policy_forward launch per step instead of the torch module, k_policy_pack after every update)')
     ap.add_argument('--device-eval', action='store_true',
                     help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
                          'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
@@ -178,6 +181,21 @@ def main():
         if rank == 0:
             print(f'  device sac update: 16 SAC steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f'last update: actor loss {losses[-1][0]:.5f}, critic loss {losses[-1][1]:.5f}, temperature {float(tr.agent.alpha):.5f}')
+    if args.device_actor:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        tr = PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
+                        seed=rank, use_planner='device' if args.device_planner else True,
+                        chooser='device' if args.device_chooser else None, obs_norm='device' if args.device_norm else None,
+                        gae='device' if args.device_gae else None, ring='device' if args.device_ring else None, actor='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(16):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f'  device actor: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f'{tr.device_actor.packs} parameter packs')
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

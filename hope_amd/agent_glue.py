@@ -11,8 +11,10 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
   DevicePpoBatch       <-> PPO.update's minibatch loop around the forwards   src/model/agent/ppo_agent.py:278-336 (hope_env_ppo_* or
                                                      their host twins)
   DeviceSacUpdate      <-> SACAgent.update between its forwards   src/model/agent/sac_agent.py:250-337 (hope_env_sac_* or their host twins)
+  DeviceActor          <-> the actor's inference forward   src/model/network.py:34-187 (hope_env_policy_forward or its host twin)
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
+import ctypes as C
 import math
 from functools import partial
 
@@ -923,6 +925,87 @@ def make_sac_update(kind, env):
     if kind != 'device':
         raise ValueError(f"sac_update must be None or 'device', not {kind!r}")
     return DeviceSacUpdate(env)
+
+
+class DeviceActor:
+    """The actor's inference forward over the library's fused kernel (include/hope_env.h "the policy's inference forward"; rule:
+    csrc/hope_policy_core.h), so that it can stand in as `agent.device_actor`: `actor(nobs)` returns what
+    `torch.clamp(net(nobs), -1, 1)` returns, from ONE launch (k_policy_forward) instead of the net's hundred.  Every Linear is the
+    float32 fmaf chain of the matrix cores, the rest float64 rounded once, so the result differs from torch's float32 forward by
+    rounding only.  The parameters are re-packed (one more launch, k_policy_pack) when they changed: the key is the parameters'
+    storage and the sum of their version counters, which in-place optimiser steps and load_state_dict both advance; an unchanged
+    net costs no launch (`packs` counts the loads).  A handle holds one set of packed parameters: two actors over one env each re-pack
+    when the other ran in between (a second net is better served by an env of its own).  With an image the net's encoder (convolutions, re_embed_img) runs in torch and
+    its token goes in ready-made.  On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same forward runs on the
+    host through hope_policy_forward_host: the rule is one source for both.  ValueError for a net of another configuration."""
+
+    def __init__(self, env, net):
+        self.shape = L.policy_shape(net)                  # before any state changes
+        self.env, self.net = env, net
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'policy_forward')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'policy_forward')
+        self.packs = 0
+        self._key = self._params = self._held = None
+        self._max = 0
+
+    def _net_key(self):
+        ps = list(self.net.parameters())
+        return tuple(p.data_ptr() for p in ps), sum(p._version for p in ps)
+
+    def _load(self):
+        if self.on_device:
+            self.env.policy_load(self.net)
+            self.env._policy_owner = self
+        else:
+            self._params, self._held = L.policy_params('hope_policy_forward_host', self.net, self.device)
+        self.packs += 1
+
+    @torch.no_grad()
+    def __call__(self, nobs):
+        f32 = lambda k: nobs[k].detach().to(torch.float32).contiguous()  # noqa: E731
+        lidar, target, mask = f32('lidar'), f32('target'), f32('action_mask')
+        b = int(lidar.shape[0])
+        token = nobs.get('img_token')                     # [B, 128], when the caller already has it
+        if token is not None:
+            token = token.detach().to(torch.float32).contiguous()
+        elif self.shape[0] == 4:
+            img = nobs['img']
+            if img.dtype == torch.uint8:                  # as HopeNet.tokens
+                img = img.to(torch.float32) * (1.0 / 255.0)
+            token = self.net.re_embed_img(self.net.embed_img(img)).to(torch.float32).contiguous()
+        mine = True
+        if self.on_device:                                # a handle holds ONE shape and ONE set of packed parameters: take them back if another actor had them
+            if b > self._max or self.env._policy_shape != self.shape:
+                self._max = max(self._max, b)
+                self.env.enable_policy(*self.shape, max_batch=self._max)
+            mine = self.env._policy_owner is self
+        key = self._net_key()
+        if key != self._key or not mine:
+            self._load()
+            self._key = key
+        if self.on_device:
+            out = self.env.policy_forward(lidar, target, mask, token)
+        else:
+            name = 'hope_policy_forward_host'
+            out = torch.zeros((b, self.shape[1]), dtype=torch.float32)
+            arg = partial(L.tensor_arg, name, dtype=torch.float32, device=self.device)
+            L.check(self._lib.hope_policy_forward_host(C.byref(self._params), *self.shape, arg('lidar', lidar, shape=(b, L.LIDAR_NUM)),
+                                                       arg('target', target, shape=(b, L.TARGET_DIM)), arg('action_mask', mask, shape=(b, L.N_ACTION)),
+                                                       arg('img_token', token, shape=(b, 128), optional=True), b, arg('out', out, shape=tuple(out.shape))), name)
+        return torch.clamp(out, -1, 1)
+
+
+def make_actor(kind, env, agent):
+    """the `actor` argument of rollouts, trainers and evaluators: None (today's torch forward, with the fast-policy levers if they
+    are on), or 'device' -- a DeviceActor over `env` and the agent's actor, set as `agent.device_actor`.  -> the DeviceActor or None."""
+    if kind is None:
+        return None
+    if kind != 'device':
+        raise ValueError(f"actor must be None or 'device', not {kind!r}")
+    agent.device_actor = DeviceActor(env, agent.actor)
+    return agent.device_actor
 
 
 class RolloutStorage:

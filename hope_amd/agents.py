@@ -99,6 +99,9 @@ class _AgentCommon:
 
     @torch.no_grad()
     def policy_mean(self, nobs):
+        da = getattr(self, 'device_actor', None)         # an agent_glue.DeviceActor (make_actor): the fused forward of the library
+        if da is not None:
+            return da(nobs)
         f = getattr(self, '_fast', None)
         if f is None or not f['graph'] or not nobs['lidar'].is_cuda:
             return torch.clamp(self._actor_infer(nobs), -1, 1)                   # ppo_agent.py:137

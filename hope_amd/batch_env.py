@@ -82,6 +82,8 @@ class ParkingBatch:
         self.eval_alive = self.eval_word = self.eval_done = self._eval_rec = None
         self._ppo_out = {}                            # mb -> (g_raw, g_log_std, g_value, losses) of ppo_loss
         self._sac_out = {}                            # (call, B) -> the outputs of sac_sample / sac_critic / sac_seed / sac_policy
+        self._policy_shape, self._policy_out, self._policy_held = None, {}, None   # enable_policy's shape, B -> out, the loaded net's tensors
+        self._policy_owner = None                     # the agent_glue.DeviceActor whose parameters the handle holds (one set per handle)
         self.pool_size = self.n_dlp_cases = None
         self._refresher_filling = False
 
@@ -778,6 +780,57 @@ class ParkingBatch:
         outs = [arg('g_raw', out[0], shape=(b, 2)), arg('g_log_std', out[1], shape=(2,)),
                 L.tensor_arg('hope_env_sac_policy', 'g_log_alpha', out[2], torch.float64, (), self.device), arg('losses', out[3], shape=(2,))]
         L.check(self.lib.hope_env_sac_policy(self.h, *ins, la, float(target_entropy), b, *outs, self._stream()), 'hope_env_sac_policy')
+        return out
+
+    # -- the policy's inference forward on the device (hope_env.h; rule: csrc/hope_policy_core.h) ----------------------
+    def enable_policy(self, n_tokens=3, out_dim=2, tanh_out=True, max_batch=None):
+        """HopeNet's inference forward for the reference configuration as one fused kernel (k_policy_forward) over parameters that
+        k_policy_pack lays out in the handle.  n_tokens 3, or 4 with a ready-made image token; out_dim 2 with tanh_out for an actor,
+        1 without for a PPO critic; max_batch: the largest batch (default: the env's scenes).  Another shape drops the loaded
+        parameters.  ValueError for a shape that is not compiled in.  Off by default."""
+        shape = (int(n_tokens), int(out_dim), int(bool(tanh_out)))
+        if shape[0] not in (3, 4) or shape[1] not in (1, 2):
+            raise ValueError(f'enable_policy: n_tokens must be 3 or 4 and out_dim 1 or 2, not {n_tokens} and {out_dim}')
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_policy_enable(self.h, *shape, int(self.n if max_batch is None else max_batch)), 'hope_env_policy_enable')
+        if shape != self._policy_shape:
+            self._policy_shape, self._policy_out, self._policy_held, self._policy_owner = shape, {}, None, None
+        return self
+
+    def disable_policy(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_policy_disable(self.h), 'hope_env_policy_disable')
+        self._policy_shape, self._policy_out, self._policy_held, self._policy_owner = None, {}, None, None
+        return self
+
+    def policy_load(self, module):
+        """pack the parameters of `module` (a policy.HopeNet of the enabled shape, float32 on this device) into the handle: one
+        launch on the current stream, no host synchronisation; the module's tensors are held until the next load.  ValueError for a
+        net of another configuration (nothing changes)."""
+        shape = L.policy_shape(module)
+        if self._policy_shape is None:
+            raise L.HopeError('hope_env_policy_load: the policy forward is off (enable_policy first)')
+        if shape != self._policy_shape:
+            raise ValueError(f'policy_load: the net is (n_tokens, out_dim, tanh_out) = {shape}, the handle was enabled for {self._policy_shape}')
+        p, keep = L.policy_params('hope_env_policy_load', module, self.device)
+        L.check(self.lib.hope_env_policy_load(self.h, C.byref(p), self._stream()), 'hope_env_policy_load')
+        self._policy_held, self._policy_owner = keep, None
+        return self
+
+    def policy_forward(self, lidar, target, mask, img_token=None, out=None):
+        """lidar [B, 120], target [B, 5], mask [B, 42], img_token [B, 128] (n_tokens 4) or None: float32 contiguous
+        -> out [B, out_dim], a persistent tensor per B (overwritten by the next call with that B) unless `out` is given.  One launch
+        on the current stream, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_policy_forward', dtype=torch.float32, device=self.device)
+        b = int(lidar.shape[0]) if hasattr(lidar, 'shape') and len(lidar.shape) == 2 else None
+        ins = [arg('lidar', lidar, shape=(b, L.LIDAR_NUM)), arg('target', target, shape=(b, L.TARGET_DIM)), arg('mask', mask, shape=(b, L.N_ACTION)),
+               arg('img_token', img_token, shape=(b, 128), optional=True)]
+        od = self._policy_shape[1] if self._policy_shape is not None else 2
+        if out is None:
+            out = self._policy_out.get(b)
+            if out is None:
+                out = self._policy_out[b] = torch.zeros((b, od), dtype=torch.float32, device=self.device)
+        L.check(self.lib.hope_env_policy_forward(self.h, *ins, b, arg('out', out, shape=(b, od)), self._stream()), 'hope_env_policy_forward')
         return out
 
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------

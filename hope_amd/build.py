@@ -6,7 +6,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, 'csrc')
 _ROOT = os.path.dirname(_HERE)
-SOURCES = ['hope_env.hip', 'hope_agent.hip', 'hope_rs.hip', 'hope_bev.hip', 'hope_scenegen.cpp']
+SOURCES = ['hope_env.hip', 'hope_agent.hip', 'hope_policy.hip', 'hope_rs.hip', 'hope_bev.hip', 'hope_scenegen.cpp']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
          '-Wno-unused-value', '-pthread']
 

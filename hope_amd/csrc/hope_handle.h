@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -236,6 +236,9 @@ struct hope_env {
     // SAC's update (hope_sac_kernel.h): part = the chunk partials of the critic call's two sums and the policy call's four ([4][chunks
     // of the call], room for ceil(max_batch / 64) chunks)
     struct Sac { bool on = false; double* part = nullptr; int max_batch = 0; } sac;
+    // the fused policy forward (hope_policy_kernel.h): packed = the parameters in the forward's layout (hope_policy_core.h pc_layout),
+    // written by k_policy_pack on the caller's stream; loaded: a hope_env_policy_load has been enqueued since the enable
+    struct Policy { bool on = false, loaded = false; int n_tokens = 0, out_dim = 0, tanh_out = 0, max_batch = 0; float* packed = nullptr; } policy;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -253,4 +256,6 @@ void gae_free(hope_env_t* h);
 void ring_free(hope_env_t* h);
 void ppo_free(hope_env_t* h);
 void sac_free(hope_env_t* h);
+// hope_policy.hip
+void policy_free(hope_env_t* h);
 }  // namespace hope

@@ -1,0 +1,123 @@
+// hope_policy.hip -- the policy's inference forward of the C ABI (include/hope_env.h "the policy's inference forward"): the packed
+// parameter buffer of the handle, k_policy_pack / k_policy_forward (hope_policy_kernel.h) and the host twin (hope_policy_core.h).
+// Shares nothing with the other features but the handle (hope_handle.h); its kernels are instantiated here and nowhere else.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "hope_handle.h"
+#include "hope_policy_kernel.h"
+
+using namespace hope;
+
+static_assert(sizeof(hope_policy_params_t) == PC_NPARAM * sizeof(const float*), "hope_policy_params_t is PC_NPARAM pointers, in pc_layout's order");
+
+void hope::policy_free(hope_env_t* h) {
+    if (h->policy.packed) hipFree(h->policy.packed);
+    h->policy = hope_env::Policy{};
+}
+
+template <int T>
+static int policy_launch(hope_env_t* h, const PcLayout& L, const float* lidar, const float* target, const float* mask, const float* img, int batch, float* out,
+                         hipStream_t st) {
+    static bool lds_set[64] = {};                              // per device: the kernel's dynamic LDS is above the default limit
+    if (h->device >= 0 && h->device < 64 && !lds_set[h->device]) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_policy_forward<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds_bytes(T)));
+        lds_set[h->device] = true;
+    }
+    hipLaunchKernelGGL(k_policy_forward<T>, dim3((unsigned)((batch + PK_TILE - 1) / PK_TILE)), dim3(PK_THREADS), pk_lds_bytes(T), st, (const float*)h->policy.packed,
+                       L, lidar, target, mask, img, (long long)batch, h->policy.out_dim, h->policy.tanh_out, out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
+}
+
+extern "C" {
+
+int hope_env_policy_enable(hope_env_t* h, int n_tokens, int out_dim, int tanh_out, int max_batch) {
+    HOPE_ENTER(h, "hope_env_policy_enable");
+    if (!pc_shape_ok(n_tokens, out_dim, tanh_out))
+        return fail(HOPE_EINVAL, "hope_env_policy_enable: the shape is fixed: n_tokens 3 or 4, out_dim 1 or 2, tanh_out 0 or 1");
+    if (max_batch < 1 || max_batch > HOPE_POLICY_MAX_BATCH)
+        return fail(HOPE_EINVAL, "hope_env_policy_enable: max_batch must be 1 .. " + std::to_string(HOPE_POLICY_MAX_BATCH));
+    hope_env::Policy& p = h->policy;
+    if (p.on && p.n_tokens == n_tokens && p.out_dim == out_dim && p.tanh_out == tanh_out) {
+        if (max_batch > p.max_batch) p.max_batch = max_batch;
+        return HOPE_OK;
+    }
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                            // calls in flight read the buffer that another shape replaces
+    policy_free(h);
+    const PcLayout L = pc_layout(n_tokens, out_dim);
+    hipError_t e_ = hipMalloc((void**)&p.packed, (size_t)L.total * sizeof(float));
+    if (e_ != hipSuccess) {
+        p.packed = nullptr;
+        return fail(HOPE_ENOMEM, std::string("hope_env_policy_enable: ") + hipGetErrorString(e_));
+    }
+    e_ = hipMemset(p.packed, 0, (size_t)L.total * sizeof(float));
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    if (e_ != hipSuccess) {
+        policy_free(h);
+        return fail(HOPE_EHIP, std::string("hope_env_policy_enable: ") + hipGetErrorString(e_));
+    }
+    p.n_tokens = n_tokens; p.out_dim = out_dim; p.tanh_out = tanh_out; p.max_batch = max_batch;
+    p.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_policy_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_policy_disable");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    policy_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_policy_load(hope_env_t* h, const hope_policy_params_t* p, void* stream) {
+    HOPE_ENTER(h, "hope_env_policy_load");
+    HOPE_NEED(h->policy.on, "hope_env_policy_load", "the policy forward is off (hope_env_policy_enable first)");
+    if (!p) return fail(HOPE_EINVAL, "hope_env_policy_load: null parameter struct");
+    PkPtrs ptrs;
+    uintptr_t bits = 0;
+    for (int i = 0; i < PC_NPARAM; ++i) {
+        ptrs.t[i] = ((const float* const*)p)[i];
+        if (!ptrs.t[i]) return fail(HOPE_EINVAL, "hope_env_policy_load: null tensor (field " + std::to_string(i) + " of hope_policy_params_t)");
+        bits |= (uintptr_t)ptrs.t[i];
+    }
+    if (bits & 3) return fail(HOPE_EINVAL, "hope_env_policy_load: misaligned tensor (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const PcLayout L = pc_layout(h->policy.n_tokens, h->policy.out_dim);
+    hipLaunchKernelGGL(k_policy_pack, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ptrs, L, h->policy.packed);
+    HIPCHK(hipGetLastError());
+    h->policy.loaded = true;
+    return HOPE_OK;
+}
+
+int hope_env_policy_forward(hope_env_t* h, const float* lidar, const float* target, const float* mask, const float* img_token, int batch, float* out,
+                            void* stream) {
+    HOPE_ENTER(h, "hope_env_policy_forward");
+    HOPE_NEED(h->policy.on, "hope_env_policy_forward", "the policy forward is off (hope_env_policy_enable first)");
+    HOPE_NEED(h->policy.loaded, "hope_env_policy_forward", "no parameters yet (hope_env_policy_load first)");
+    if (!lidar || !target || !mask || !out) return fail(HOPE_EINVAL, "hope_env_policy_forward: null lidar / target / mask / out");
+    if ((h->policy.n_tokens == 4) != (img_token != nullptr))
+        return fail(HOPE_EINVAL, h->policy.n_tokens == 4 ? "hope_env_policy_forward: n_tokens is 4: the image token is missing"
+                                                         : "hope_env_policy_forward: n_tokens is 3: there is no image token");
+    if (batch < 1 || batch > h->policy.max_batch)
+        return fail(HOPE_EINVAL, "hope_env_policy_forward: batch must be 1 .. max_batch (" + std::to_string(h->policy.max_batch) + ")");
+    if (((uintptr_t)lidar | (uintptr_t)target | (uintptr_t)mask | (uintptr_t)img_token | (uintptr_t)out) & 3)
+        return fail(HOPE_EINVAL, "hope_env_policy_forward: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const PcLayout L = pc_layout(h->policy.n_tokens, h->policy.out_dim);
+    if (h->policy.n_tokens == 4) return policy_launch<4>(h, L, lidar, target, mask, img_token, batch, out, (hipStream_t)stream);
+    return policy_launch<3>(h, L, lidar, target, mask, nullptr, batch, out, (hipStream_t)stream);
+}
+
+int hope_policy_forward_host(const hope_policy_params_t* host_params, int n_tokens, int out_dim, int tanh_out, const float* lidar, const float* target,
+                             const float* mask, const float* img_token, int64_t batch, float* out) {
+    const int rc = pc_forward_host(host_params, n_tokens, out_dim, tanh_out, lidar, target, mask, img_token, batch, out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_policy_forward_host: bad argument (a null parameter, input or output, n_tokens not 3 or 4, out_dim not 1 or 2, tanh_out not 0 or 1, "
+                        "an image token that does not go with n_tokens, or batch < 1)");
+    return HOPE_OK;
+}
+
+}  // extern "C"

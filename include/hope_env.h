@@ -1004,6 +1004,52 @@ int hope_sac_policy_host(const float *raw, const float *log_std, const float *ep
                          const float *g_action, const double *log_alpha, double target_entropy, int64_t batch, float *g_raw,
                          float *g_log_std, double *g_log_alpha, float *losses);
 
+/* ---- the policy's inference forward (additive to ABI 8) ----------------------------------------------------------------------------
+ * HopeNet's forward (hope_amd/policy.py; the reference's MultiObsEmbedding with the attention trunk, src/model/network.py:34-187)
+ * for the reference's configuration as ONE kernel, k_policy_forward: embed 128, two-layer embedding MLPs with tanh, one pre-norm
+ * encoder layer (8 heads x 32, bias-free qkv, a 128-wide token MLP), a (n_tokens x 128) -> 128 -> out_dim head.  n_tokens = 3
+ * (lidar 120, target 5, action mask 42) or 4: the fourth token is handed in ready-made as [batch][128] (the image encoder's
+ * convolutions and re_embed_img stay with the caller).  out_dim 1 or 2, the output tanh on or off, so a PPO critic runs through
+ * the same code.  Every Linear is a k-ascending float32 fmaf chain from its bias (the f32-input matrix instruction), everything
+ * else float64 rounded once; the order is fixed in hope_amd/csrc/hope_policy_core.h, so the host twin below gives the same bits.
+ * A row's result depends on that row only.  Off until enabled; with it off no launch, pointer or output of any other entry point
+ * differs.  DESIGN.md 5m. */
+#define HOPE_POLICY_MAX_BATCH 1048576
+/* the float32 parameter tensors as torch holds them, [out][in] row-major and contiguous */
+typedef struct hope_policy_params {
+    const float *lidar_w1, *lidar_b1, *lidar_w2, *lidar_b2;      /* embed_lidar.0 [128][120], [128]; embed_lidar.2 [128][128], [128] */
+    const float *target_w1, *target_b1, *target_w2, *target_b2;  /* embed_tgt.0 [128][5], .2 */
+    const float *mask_w1, *mask_b1, *mask_w2, *mask_b2;          /* embed_am.0 [128][42], .2 */
+    const float *ln1_g, *ln1_b;                                  /* net.encoder.layers.0.0.norm [128] */
+    const float *qkv_w;                                          /* ...layers.0.0.fn.to_qkv [768][128], no bias */
+    const float *out_w, *out_b;                                  /* ...layers.0.0.fn.to_out.0 [128][256], [128] */
+    const float *ln2_g, *ln2_b;                                  /* ...layers.0.1.norm [128] */
+    const float *ff1_w, *ff1_b, *ff2_w, *ff2_b;                  /* ...layers.0.1.fn.net.0 and .3 [128][128], [128] */
+    const float *head1_w, *head1_b;                              /* net.output.0 [128][n_tokens * 128], [128] */
+    const float *head2_w, *head2_b;                              /* net.output.2 [out_dim][128], [out_dim] */
+} hope_policy_params_t;
+/* allocate the packed parameter buffer for this shape.  n_tokens 3 or 4, out_dim 1 or 2, tanh_out 0 or 1, 1 <= max_batch <=
+ * HOPE_POLICY_MAX_BATCH, anything else HOPE_EINVAL.  Enabling again with the same shape keeps the loaded parameters and takes the
+ * larger max_batch; another shape drops them (a load must follow).  Host-synchronous. */
+int hope_env_policy_enable(hope_env_t *h, int n_tokens, int out_dim, int tanh_out, int max_batch);
+/* free it.  Host-synchronous (calls in flight use it). */
+int hope_env_policy_disable(hope_env_t *h);
+/* p: a HOST struct of DEVICE pointers, each aligned to 4 bytes.  k_policy_pack copies the tensors into the handle's buffer, in the
+ * layout that the forward loads coalesced: one launch on `stream`, no host synchronisation; the tensors must stay unchanged until
+ * it has run.  HOPE_ESTATE before the enable; HOPE_EINVAL for a NULL struct or a NULL or misaligned tensor (nothing is launched, the
+ * buffer keeps what it had). */
+int hope_env_policy_load(hope_env_t *h, const hope_policy_params_t *p, void *stream);
+/* lidar [batch][120], target [batch][5], mask [batch][42], img_token [batch][128] (n_tokens 4) or NULL (n_tokens 3), out
+ * [batch][out_dim]: DEVICE memory, float32, contiguous, aligned to 4 bytes.  One launch on `stream` (ceil(batch / 32) workgroups),
+ * no host synchronisation.  HOPE_ESTATE before the enable or before the first load; HOPE_EINVAL for a NULL or misaligned pointer,
+ * a batch outside 1 .. max_batch, or an image token that does not go with n_tokens; on any error nothing is launched. */
+int hope_env_policy_forward(hope_env_t *h, const float *lidar, const float *target, const float *mask, const float *img_token,
+                            int batch, float *out, void *stream);
+/* The same over HOST arrays and a struct of HOST pointers: pure host code from the same source, no handle, no device; bit-equal
+ * to the kernel.  No alignment requirements, no upper bound on batch.  HOPE_EINVAL for a NULL pointer, a shape as above, batch < 1. */
+int hope_policy_forward_host(const hope_policy_params_t *host_params, int n_tokens, int out_dim, int tanh_out, const float *lidar,
+                             const float *target, const float *mask, const float *img_token, int64_t batch, float *out);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
