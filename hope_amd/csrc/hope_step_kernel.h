@@ -584,14 +584,37 @@ __device__ __forceinline__ double quad_bcast(double v) {
 // [0.8, 1) 2^k), so the remainder r = x - 20 q0 is representable and the fma delivers it exactly; x / 20 = q0 + r / 20, and
 // q0 + r R differs from it by at most 2^-54 ulp.  That cannot move it across a rounding boundary: with x = X 2^e (X a 53-bit
 // integer) the quotient is 4 X / 5 or 8 X / 5 ulps, whose distance to any midpoint m + 1/2 is an odd integer over 10: >= 0.1 ulp.
-// So RN(q0 + r R) = RN(x / 20) for every x without under- / overflow (the terms here are ~1e-3 .. 1e-1).  Pose parity (tolerance
-// 0.0, tests/test_gpu_parity.py) compares the sums of these quotients with the oracle's plain divisions.
+// So RN(q0 + r R) = RN(x / 20) -- PROVIDED q0 and the quotient are normal numbers: the proof uses the relative error of RN(x R), the
+// representability of r (a multiple of 4 ulp(q0), at most 20 ulp(q0): fine whenever ulp(q0) is q0's own, i.e. q0 is normal) and the
+// quotient's ulp being 4 X / 5 or 8 X / 5 of x's.  Both hold from |x| >= 20 2^-1022 < 2^-1017 on (nothing here comes near overflow:
+// |x| <= 0.125).  Below that they fail: among the subnormals the ulp is fixed, x / 20 is an exact tie at every X = 30 + 40 k (the
+// division rounds it to even, the chain rounds q0 down and r R is too small to lift it), and in [1, 20) 2^-1022 q0 is subnormal and a
+// fraction of a percent of the x differ (tests/motion_reward_cases.py: div20_search emulates the three operations exactly).  Such
+// terms are reachable through the public step -- a speed action of a few hundred subnormal ulps, or an ordinary speed at a heading of
+// a few hundred -- so the callers keep div_by_20 to its domain (div20_plain below) and divide plainly outside of it.  Pose parity
+// (tolerance 0.0, tests/test_gpu_parity.py; the tiny terms: tests/test_gpu_motion_reward.py) compares the sums of these quotients with
+// the oracle's plain divisions.
 static_assert(MINI_ITER == 20, "div_by_20");
 __device__ __forceinline__ double div_by_20(double x) {
     const double R = 0.05;
     const double q0 = x * R;
     const double r = fma(-q0, 20.0, x);
     return copysign(fma(r, R, q0), x);                   // (the quotient has x's sign; the fma chain turns -0 into +0)
+}
+
+// Which terms x = speed * (cos | sin) * STEP_LENGTH may take div_by_20: decided from the factors with integer compares on the high
+// words (|v| < 2^E <=> high word of |v| below (E + 1023) << 20), once per scene for the speed and once per group of sines -- not
+// per term with float64 compares and a branch each, which cost bench.py's step about 1.5 % when tried.  |speed| >= 2^-90 and |sin| >= 2^-900 give
+// |x| >= 2^-990 2^-5 (1 - 2^-51) > 2^-1017, the domain above, with 22 binades to spare.  The cosine needs no test: no double is
+// closer to an odd multiple of pi / 2 than 4.7e-19 > 2^-62 (the worst case of argument reduction over all doubles; 6e-17 among
+// headings of ordinary size), so |cos| >= 2^-62 always, far above the 2^-900 asked of the sine.
+// The sine has no such floor (sin h = h for a tiny heading h), so a bound on |speed| alone would not do.  A lane for which the test
+// fails -- practically never: a zero or absurdly small speed, a heading of exactly 0 or within 2^-900 of it -- divides all its
+// terms plainly, which is right for every x.
+constexpr unsigned DIV20_SPEED_HI = (1023u - 90u) << 20, DIV20_SIN_HI = (1023u - 900u) << 20;
+__device__ __forceinline__ unsigned abs_hi(double v) { return (unsigned)__double2hiint(v) & 0x7fffffffu; }
+__device__ __forceinline__ bool div20_plain(double speed, unsigned min_sin_hi) {
+    return abs_hi(speed) < DIV20_SPEED_HI || min_sin_hi < DIV20_SIN_HI;
 }
 
 // action_rescale (env_wrapper.py:37-50) + KSModel's clip (vehicle.py:85-86): the speed and the heading increment per micro-step
@@ -671,10 +694,21 @@ __global__ __launch_bounds__(64) void k_kinematics(int n, const int32_t* scene_l
             const int k = r - 1;
             out[k] = hj[0]; out[10 + k] = cj[0]; out[20 + k] = sj[0];
         }
+        unsigned msh = abs_hi(sj[0]);
 #pragma unroll
-        for (int j = 0; j < KJ; j++) {
-            terms[4 * j + q][2 * ls] = div_by_20(speed * cj[j] * STEP_LENGTH);      // ... / MINI_ITER, correctly rounded (below)
-            terms[4 * j + q][2 * ls + 1] = div_by_20(speed * sj[j] * STEP_LENGTH);
+        for (int j = 1; j < KJ; j++) msh = min(msh, abs_hi(sj[j]));
+        if (__builtin_expect(div20_plain(speed, msh), 0)) {  // a term could leave div_by_20's domain: the plain division (above)
+#pragma unroll
+            for (int j = 0; j < KJ; j++) {
+                terms[4 * j + q][2 * ls] = speed * cj[j] * STEP_LENGTH / MINI_ITER;
+                terms[4 * j + q][2 * ls + 1] = speed * sj[j] * STEP_LENGTH / MINI_ITER;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KJ; j++) {
+                terms[4 * j + q][2 * ls] = div_by_20(speed * cj[j] * STEP_LENGTH);  // ... / MINI_ITER, correctly rounded (above)
+                terms[4 * j + q][2 * ls + 1] = div_by_20(speed * sj[j] * STEP_LENGTH);
+            }
         }
         ssync();
         if (lane < 2 * KIN_SCENES_PER_BLOCK) {
@@ -777,6 +811,10 @@ __device__ __forceinline__ void wave_kinematics(const void* actions, int scene, 
         }
     }
     double acc = lane == 0 ? x0 : y0;                     // lane 0: x, lane 1: y
+    unsigned msh = abs_hi(sm[0]);
+#pragma unroll
+    for (int j = 1; j < NJ; j++) msh = min(msh, abs_hi(sm[j]));
+    const bool plain = div20_plain(speed, msh);           // a term of this lane could leave div_by_20's domain (see there)
 #pragma unroll
     for (int ph = 0; ph < 2; ph++) {                      // micro-steps [0, 128) and [128, 200): 2 x 128 doubles of region A
         ssync();
@@ -784,8 +822,14 @@ __device__ __forceinline__ void wave_kinematics(const void* actions, int scene, 
         for (int jj = 0; jj < 2; jj++) {
             const int j = 2 * ph + jj, m = lane + WAVE * j;
             if (m < NM) {
-                scr[2 * (m - 2 * WAVE * ph)] = div_by_20(speed * cm[j] * STEP_LENGTH);       // ... / MINI_ITER, correctly rounded
-                scr[2 * (m - 2 * WAVE * ph) + 1] = div_by_20(speed * sm[j] * STEP_LENGTH);
+                const double tx = speed * cm[j] * STEP_LENGTH, ty = speed * sm[j] * STEP_LENGTH;
+                if (__builtin_expect(plain, 0)) {
+                    scr[2 * (m - 2 * WAVE * ph)] = tx / MINI_ITER;
+                    scr[2 * (m - 2 * WAVE * ph) + 1] = ty / MINI_ITER;
+                } else {
+                    scr[2 * (m - 2 * WAVE * ph)] = div_by_20(tx);                            // ... / MINI_ITER, correctly rounded
+                    scr[2 * (m - 2 * WAVE * ph) + 1] = div_by_20(ty);
+                }
             }
         }
         ssync();
