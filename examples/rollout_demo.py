@@ -53,6 +53,10 @@ def main():
     ap.add_argument('--device-actor', action='store_true',
                     help="also run a short PPO loop with the actor's inference forward on the device (actor='device': one fused "
                          'k_policy_forward launch per step instead of the torch module, k_policy_pack after every update)')
+    ap.add_argument('--device-img-encoder', action='store_true',
+                    help="also run a short PPO loop of an agent WITH the image token on an env that renders the bird's-eye image, the "
+                         "actor's forward and its image encoder on the device (actor='device', img_encoder='device': k_imgenc_conv and "
+                         'k_imgenc_head on the env\'s uint8 image instead of the MIOpen convolutions, then k_policy_forward)')
     ap.add_argument('--device-eval', action='store_true',
                     help="run the evaluation with its per-episode bookkeeping on the device (tracker='device': k_eval_override and k_eval_track "
                          'per step instead of the torch one-liners, and one host synchronisation every 8 steps instead of every step)')
@@ -196,6 +200,23 @@ def main():
         if rank == 0:
             print(f'  device actor: 16 PPO steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                   f'{tr.device_actor.packs} parameter packs')
+    if args.device_img_encoder:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer
+        n_img = min(args.scenes, 8192)
+        env_img = ParkingBatch(n_img, 128, device=dev, image=True)
+        env_img.set_scenes(np.arange(n_img), [uniq[i % len(uniq)] for i in range(n_img)])
+        tr = PPOTrainer(env_img, A.BatchedPPO(device=dev, use_img=True, mini_batch=min(n_img, 4096), mini_epoch=1), horizon=4, seed=rank,
+                        actor='device', img_encoder='device')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(8):
+            tr.step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f'  device image encoder: 8 PPO steps of {n_img} scenes ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                  f'{tr.device_actor.img_encoder.packs} encoder packs, {tr.device_actor.packs} actor packs')
+        env_img.close()
     if args.device_pool > 0:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

@@ -927,6 +927,67 @@ def make_sac_update(kind, env):
     return DeviceSacUpdate(env)
 
 
+class DeviceImgEncoder:
+    """The image token of a HopeNet over the library's image encoder (include/hope_env.h "the image encoder's inference forward";
+    rule: csrc/hope_imgenc_core.h): `enc(img)` takes img uint8 [B, 3, 64, 64] and returns what
+    `net.re_embed_img(net.embed_img(img.float() * (1 / 255)))` returns, float32 [B, 128], from two launches (k_imgenc_conv,
+    k_imgenc_head).  The 14 encoder tensors are re-packed (one more launch, k_imgenc_pack) when they changed: the key is their storage
+    and the sum of their version counters, as DeviceActor's, taken over these tensors only; `packs` counts the loads.  A handle holds
+    one set of packed encoder tensors: two encoders over one env each re-pack when the other ran in between.  On an env without the
+    library (CPU tensors) the same forward runs on the host through hope_imgenc_forward_host.  A float image is not this path's
+    input: it goes through torch, as it always did.  ValueError for a net of another configuration."""
+
+    def __init__(self, env, net):
+        self.act = L.imgenc_shape(net)                    # before any state changes
+        self.env, self.net = env, net
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'img_encoder_forward')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'img_encoder_forward')
+        self.packs = 0
+        self._key = self._params = self._held = None
+        self._max = 0
+
+    def _net_key(self):
+        sd = dict(self.net.named_parameters())
+        ps = [sd[key] for _, key, _ in L.IMGENC_FIELDS]     # the 14 encoder tensors only
+        return tuple(p.data_ptr() for p in ps), sum(p._version for p in ps)
+
+    def _load(self):
+        if self.on_device:
+            self.env.img_encoder_load(self.net)
+            self.env._imgenc_owner = self
+        else:
+            self._params, self._held = L.imgenc_params('hope_imgenc_forward_host', self.net, self.device)
+        self.packs += 1
+
+    @torch.no_grad()
+    def __call__(self, img, features=False):
+        if img.dtype != torch.uint8:                      # not the device path's input
+            return self.net.re_embed_img(self.net.embed_img(img.to(torch.float32))).to(torch.float32).contiguous()
+        img = img.detach().contiguous()
+        b = int(img.shape[0])
+        mine = True
+        if self.on_device:
+            if b > self._max or self.env._imgenc_act != self.act:
+                self._max = max(self._max, b)
+                self.env.enable_img_encoder(self.act, max_batch=self._max)
+            mine = self.env._imgenc_owner is self
+        key = self._net_key()
+        if key != self._key or not mine:
+            self._load()
+            self._key = key
+        if self.on_device:
+            return self.env.img_encoder_forward(img, features=features)
+        name = 'hope_imgenc_forward_host'
+        token = torch.zeros((b, 128), dtype=torch.float32)
+        feat = torch.zeros((b, 2048), dtype=torch.float32) if features else None
+        L.check(self._lib.hope_imgenc_forward_host(C.byref(self._params), self.act, L.tensor_arg(name, 'img', img, torch.uint8, (b, 3, 64, 64), self.device), b,
+                                                   L.tensor_arg(name, 'token', token, torch.float32, (b, 128), self.device),
+                                                   L.tensor_arg(name, 'features', feat, torch.float32, (b, 2048), self.device, optional=True)), name)
+        return (token, feat) if features else token
+
+
 class DeviceActor:
     """The actor's inference forward over the library's fused kernel (include/hope_env.h "the policy's inference forward"; rule:
     csrc/hope_policy_core.h), so that it can stand in as `agent.device_actor`: `actor(nobs)` returns what
@@ -935,12 +996,18 @@ class DeviceActor:
     rounding only.  The parameters are re-packed (one more launch, k_policy_pack) when they changed: the key is the parameters'
     storage and the sum of their version counters, which in-place optimiser steps and load_state_dict both advance; an unchanged
     net costs no launch (`packs` counts the loads).  A handle holds one set of packed parameters: two actors over one env each re-pack
-    when the other ran in between (a second net is better served by an env of its own).  With an image the net's encoder (convolutions, re_embed_img) runs in torch and
-    its token goes in ready-made.  On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same forward runs on the
+    when the other ran in between (a second net is better served by an env of its own).  With an image the net's encoder (convolutions, re_embed_img) runs in torch by
+    default and its token goes in ready-made; img_encoder='device' sends a uint8 image through a DeviceImgEncoder instead (two more
+    launches, the 128-float token the only intermediate torch sees; a float image still goes through torch).  On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same forward runs on the
     host through hope_policy_forward_host: the rule is one source for both.  ValueError for a net of another configuration."""
 
-    def __init__(self, env, net):
+    def __init__(self, env, net, img_encoder=None):
         self.shape = L.policy_shape(net)                  # before any state changes
+        if img_encoder not in (None, 'device'):
+            raise ValueError(f"img_encoder must be None or 'device', not {img_encoder!r}")
+        if img_encoder == 'device' and self.shape[0] != 4:
+            raise ValueError("img_encoder='device' needs a net with an image token (use_img)")
+        self.img_encoder = DeviceImgEncoder(env, net) if img_encoder == 'device' else None
         self.env, self.net = env, net
         self.device = torch.device(env.device)
         self.on_device = hasattr(env, 'policy_forward')
@@ -972,9 +1039,12 @@ class DeviceActor:
             token = token.detach().to(torch.float32).contiguous()
         elif self.shape[0] == 4:
             img = nobs['img']
-            if img.dtype == torch.uint8:                  # as HopeNet.tokens
-                img = img.to(torch.float32) * (1.0 / 255.0)
-            token = self.net.re_embed_img(self.net.embed_img(img)).to(torch.float32).contiguous()
+            if self.img_encoder is not None and img.dtype == torch.uint8:
+                token = self.img_encoder(img)
+            else:
+                if img.dtype == torch.uint8:              # as HopeNet.tokens
+                    img = img.to(torch.float32) * (1.0 / 255.0)
+                token = self.net.re_embed_img(self.net.embed_img(img)).to(torch.float32).contiguous()
         mine = True
         if self.on_device:                                # a handle holds ONE shape and ONE set of packed parameters: take them back if another actor had them
             if b > self._max or self.env._policy_shape != self.shape:
@@ -997,14 +1067,22 @@ class DeviceActor:
         return torch.clamp(out, -1, 1)
 
 
-def make_actor(kind, env, agent):
+def make_actor(kind, env, agent, img_encoder=None):
     """the `actor` argument of rollouts, trainers and evaluators: None (today's torch forward, with the fast-policy levers if they
-    are on), or 'device' -- a DeviceActor over `env` and the agent's actor, set as `agent.device_actor`.  -> the DeviceActor or None."""
+    are on), or 'device' -- a DeviceActor over `env` and the agent's actor, set as `agent.device_actor`.  img_encoder: None (the
+    image encoder stays in torch) or 'device' (a DeviceImgEncoder inside the DeviceActor): valid only with actor='device' and an
+    agent whose actor takes an image, ValueError otherwise.  -> the DeviceActor or None."""
+    if img_encoder not in (None, 'device'):
+        raise ValueError(f"img_encoder must be None or 'device', not {img_encoder!r}")
     if kind is None:
+        if img_encoder is not None:
+            raise ValueError("img_encoder='device' needs actor='device'")
         return None
     if kind != 'device':
         raise ValueError(f"actor must be None or 'device', not {kind!r}")
-    agent.device_actor = DeviceActor(env, agent.actor)
+    if img_encoder is not None and not getattr(agent.actor, 'use_img', False):
+        raise ValueError("img_encoder='device' needs an agent with an image token (use_img)")
+    agent.device_actor = DeviceActor(env, agent.actor, img_encoder=img_encoder)
     return agent.device_actor
 
 

@@ -84,6 +84,8 @@ class ParkingBatch:
         self._sac_out = {}                            # (call, B) -> the outputs of sac_sample / sac_critic / sac_seed / sac_policy
         self._policy_shape, self._policy_out, self._policy_held = None, {}, None   # enable_policy's shape, B -> out, the loaded net's tensors
         self._policy_owner = None                     # the agent_glue.DeviceActor whose parameters the handle holds (one set per handle)
+        self._imgenc_act, self._imgenc_max, self._imgenc_out, self._imgenc_held = None, 0, {}, None   # enable_img_encoder's act and room, B -> (token, features)
+        self._imgenc_owner = None                     # the agent_glue.DeviceImgEncoder whose parameters the handle holds
         self.pool_size = self.n_dlp_cases = None
         self._refresher_filling = False
 
@@ -832,6 +834,65 @@ class ParkingBatch:
                 out = self._policy_out[b] = torch.zeros((b, od), dtype=torch.float32, device=self.device)
         L.check(self.lib.hope_env_policy_forward(self.h, *ins, b, arg('out', out, shape=(b, od)), self._stream()), 'hope_env_policy_forward')
         return out
+
+    # -- the image encoder's inference forward on the device (hope_env.h; rule: csrc/hope_imgenc_core.h) ----------------
+    def enable_img_encoder(self, act='tanh', max_batch=None):
+        """HopeNet's image token (the two convolution blocks, fc1, output_mean, re_embed_img) for the reference configuration as two
+        kernels (k_imgenc_conv, k_imgenc_head) over parameters that k_imgenc_pack lays out in the handle.  act: 'tanh' or 'leaky';
+        max_batch: the largest batch (default: the env's scenes); the handle keeps a feature buffer of 8 KiB per image of it.  Independent
+        of enable_policy.  Off by default."""
+        if act not in ('tanh', 'leaky', 0, 1):
+            raise ValueError(f"enable_img_encoder: act must be 'tanh' or 'leaky', not {act!r}")
+        a = {'tanh': 0, 'leaky': 1}.get(act, act)
+        mb = int(self.n if max_batch is None else max_batch)
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_imgenc_enable(self.h, a, mb), 'hope_env_imgenc_enable')
+        self._imgenc_act, self._imgenc_max = a, max(self._imgenc_max, mb)
+        return self
+
+    def disable_img_encoder(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_imgenc_disable(self.h), 'hope_env_imgenc_disable')
+        self._imgenc_act, self._imgenc_max, self._imgenc_out, self._imgenc_held, self._imgenc_owner = None, 0, {}, None, None
+        return self
+
+    def img_encoder_load(self, module):
+        """pack the 14 encoder tensors of `module` (a policy.HopeNet with an image token, float32 on this device) into the handle: one
+        launch on the current stream, no host synchronisation; the tensors are held until the next load.  ValueError for a net of
+        another configuration or activation (nothing changes)."""
+        act = L.imgenc_shape(module)
+        if self._imgenc_act is None:
+            raise L.HopeError('hope_env_imgenc_load: the image encoder is off (enable_img_encoder first)')
+        if act != self._imgenc_act:
+            raise ValueError(f"img_encoder_load: the net's encoder activation is {('tanh', 'leaky')[act]}, the handle was enabled for "
+                             f"{('tanh', 'leaky')[self._imgenc_act]}")
+        p, keep = L.imgenc_params('hope_env_imgenc_load', module, self.device)
+        L.check(self.lib.hope_env_imgenc_load(self.h, C.byref(p), self._stream()), 'hope_env_imgenc_load')
+        self._imgenc_held, self._imgenc_owner = keep, None
+        return self
+
+    def img_encoder_forward(self, img, out=None, features=False):
+        """img uint8 [B, 3, 64, 64] contiguous (the env's own `img` goes in without a copy) -> token float32 [B, 128], a persistent
+        tensor per B (overwritten by the next call with that B) unless `out` is given.  features: True -> (token, features [B, 2048],
+        persistent per B), or a float32 [B, 2048] tensor to receive them.  Two launches on the current stream, no host synchronisation."""
+        name = 'hope_env_imgenc_forward'
+        b = int(img.shape[0]) if hasattr(img, 'shape') and len(img.shape) == 4 else None
+        im = L.tensor_arg(name, 'img', img, torch.uint8, (b, 3, 64, 64), self.device)
+        keep = self._imgenc_out.setdefault(b, [None, None])
+        if out is None:
+            if keep[0] is None:
+                keep[0] = torch.zeros((b, 128), dtype=torch.float32, device=self.device)
+            out = keep[0]
+        feat = None
+        if features is True:
+            if keep[1] is None:
+                keep[1] = torch.zeros((b, 2048), dtype=torch.float32, device=self.device)
+            feat = keep[1]
+        elif features is not False and features is not None:
+            feat = features
+        L.check(self.lib.hope_env_imgenc_forward(self.h, im, b, L.tensor_arg(name, 'out', out, torch.float32, (b, 128), self.device),
+                                                 L.tensor_arg(name, 'features', feat, torch.float32, (b, 2048), self.device, optional=True), self._stream()), name)
+        return out if feat is None else (out, feat)
 
     # -- bookkeeping of an evaluation run on the device (hope_env.h; rule: csrc/hope_evaltrack_core.h) ------------------
     def enable_eval_tracker(self):

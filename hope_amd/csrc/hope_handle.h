@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward, the image encoder).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -239,6 +239,9 @@ struct hope_env {
     // the fused policy forward (hope_policy_kernel.h): packed = the parameters in the forward's layout (hope_policy_core.h pc_layout),
     // written by k_policy_pack on the caller's stream; loaded: a hope_env_policy_load has been enqueued since the enable
     struct Policy { bool on = false, loaded = false; int n_tokens = 0, out_dim = 0, tanh_out = 0, max_batch = 0; float* packed = nullptr; } policy;
+    // the image encoder (hope_imgenc_kernel.h): packed = the 14 tensors in the kernels' layout (hope_imgenc_core.h IE_OFF_*), written by
+    // k_imgenc_pack on the caller's stream; feat = the features between the two kernels, [max_batch][2048]; loaded: as for the policy
+    struct ImgEnc { bool on = false, loaded = false; int act = 0, max_batch = 0; float* packed = nullptr; float* feat = nullptr; } imgenc;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -258,4 +261,5 @@ void ppo_free(hope_env_t* h);
 void sac_free(hope_env_t* h);
 // hope_policy.hip
 void policy_free(hope_env_t* h);
+void imgenc_free(hope_env_t* h);
 }  // namespace hope

@@ -1,5 +1,7 @@
 // hope_policy.hip -- the policy's inference forward of the C ABI (include/hope_env.h "the policy's inference forward"): the packed
-// parameter buffer of the handle, k_policy_pack / k_policy_forward (hope_policy_kernel.h) and the host twin (hope_policy_core.h).
+// parameter buffer of the handle, k_policy_pack / k_policy_forward (hope_policy_kernel.h) and the host twin (hope_policy_core.h);
+// and the image encoder's ("the image encoder's inference forward"): k_imgenc_pack / k_imgenc_conv / k_imgenc_head
+// (hope_imgenc_kernel.h) and its twin (hope_imgenc_core.h).  The two features share no state.
 // Shares nothing with the other features but the handle (hope_handle.h); its kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -7,6 +9,7 @@
 
 #include "hope_handle.h"
 #include "hope_policy_kernel.h"
+#include "hope_imgenc_kernel.h"
 
 using namespace hope;
 
@@ -15,6 +18,32 @@ static_assert(sizeof(hope_policy_params_t) == PC_NPARAM * sizeof(const float*), 
 void hope::policy_free(hope_env_t* h) {
     if (h->policy.packed) hipFree(h->policy.packed);
     h->policy = hope_env::Policy{};
+}
+
+static_assert(sizeof(hope_imgenc_params_t) == IE_NPARAM * sizeof(const float*), "hope_imgenc_params_t is IE_NPARAM pointers, in IE_OFF_*'s order");
+
+void hope::imgenc_free(hope_env_t* h) {
+    if (h->imgenc.packed) hipFree(h->imgenc.packed);
+    if (h->imgenc.feat) hipFree(h->imgenc.feat);
+    h->imgenc = hope_env::ImgEnc{};
+}
+
+template <int ACT>
+static int imgenc_launch(hope_env_t* h, const uint8_t* img, long long batch, float* token, float* feat, hipStream_t st, int stages = 3) {
+    static bool lds_set[64] = {};                              // per device: the conv kernel's dynamic LDS is above the default limit
+    if (h->device >= 0 && h->device < 64 && !lds_set[h->device]) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_imgenc_conv<ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IK_CONV_LDS));
+        lds_set[h->device] = true;
+    }
+    if (stages & 1) {
+        hipLaunchKernelGGL(k_imgenc_conv<ACT>, dim3((unsigned)batch), dim3(IK_CONV_THREADS), IK_CONV_LDS, st, (const float*)h->imgenc.packed, img, feat);
+        HIPCHK(hipGetLastError());
+    }
+    if (!(stages & 2)) return HOPE_OK;
+    hipLaunchKernelGGL(k_imgenc_head<ACT>, dim3((unsigned)((batch + IK_TILE - 1) / IK_TILE)), dim3(IK_THREADS), 0, st, (const float*)h->imgenc.packed,
+                       (const float*)feat, batch, token);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
 }
 
 template <int T>
@@ -117,6 +146,102 @@ int hope_policy_forward_host(const hope_policy_params_t* host_params, int n_toke
     if (rc != HOPE_OK)
         return fail(rc, "hope_policy_forward_host: bad argument (a null parameter, input or output, n_tokens not 3 or 4, out_dim not 1 or 2, tanh_out not 0 or 1, "
                         "an image token that does not go with n_tokens, or batch < 1)");
+    return HOPE_OK;
+}
+
+int hope_env_imgenc_enable(hope_env_t* h, int act, int max_batch) {
+    HOPE_ENTER(h, "hope_env_imgenc_enable");
+    if (!ie_act_ok(act)) return fail(HOPE_EINVAL, "hope_env_imgenc_enable: act must be 0 (tanh) or 1 (LeakyReLU)");
+    if (max_batch < 1 || max_batch > HOPE_IMGENC_MAX_BATCH)
+        return fail(HOPE_EINVAL, "hope_env_imgenc_enable: max_batch must be 1 .. " + std::to_string(HOPE_IMGENC_MAX_BATCH));
+    hope_env::ImgEnc& p = h->imgenc;
+    if (p.on && max_batch <= p.max_batch) {
+        p.act = act;                                           // the packed words do not depend on act
+        return HOPE_OK;
+    }
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                            // calls in flight use the feature buffer that a larger one replaces
+    float *packed = p.packed, *feat = nullptr;
+    hipError_t e_ = hipSuccess;
+    if (!packed) {
+        e_ = hipMalloc((void**)&packed, (size_t)IE_TOTAL * sizeof(float));
+        if (e_ == hipSuccess) e_ = hipMemset(packed, 0, (size_t)IE_TOTAL * sizeof(float));
+        else packed = nullptr;
+    }
+    if (e_ == hipSuccess) {
+        e_ = hipMalloc((void**)&feat, (size_t)max_batch * IE_FEAT * sizeof(float));
+        if (e_ != hipSuccess) feat = nullptr;
+    }
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    if (e_ != hipSuccess) {                                    // the state from before the call stays
+        if (feat) hipFree(feat);
+        if (packed && packed != p.packed) hipFree(packed);
+        return fail(e_ == hipErrorOutOfMemory ? HOPE_ENOMEM : HOPE_EHIP, std::string("hope_env_imgenc_enable: ") + hipGetErrorString(e_));
+    }
+    if (p.feat) hipFree(p.feat);
+    p.packed = packed; p.feat = feat; p.act = act; p.max_batch = max_batch;
+    p.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_imgenc_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_imgenc_disable");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    imgenc_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_imgenc_load(hope_env_t* h, const hope_imgenc_params_t* p, void* stream) {
+    HOPE_ENTER(h, "hope_env_imgenc_load");
+    HOPE_NEED(h->imgenc.on, "hope_env_imgenc_load", "the image encoder is off (hope_env_imgenc_enable first)");
+    if (!p) return fail(HOPE_EINVAL, "hope_env_imgenc_load: null parameter struct");
+    IkPtrs ptrs;
+    uintptr_t bits = 0;
+    for (int i = 0; i < IE_NPARAM; ++i) {
+        ptrs.t[i] = ((const float* const*)p)[i];
+        if (!ptrs.t[i]) return fail(HOPE_EINVAL, "hope_env_imgenc_load: null tensor (field " + std::to_string(i) + " of hope_imgenc_params_t)");
+        bits |= (uintptr_t)ptrs.t[i];
+    }
+    if (bits & 3) return fail(HOPE_EINVAL, "hope_env_imgenc_load: misaligned tensor (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_imgenc_pack, dim3((unsigned)((IE_TOTAL + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ptrs, h->imgenc.packed);
+    HIPCHK(hipGetLastError());
+    h->imgenc.loaded = true;
+    return HOPE_OK;
+}
+
+int hope_env_imgenc_forward(hope_env_t* h, const uint8_t* img, int64_t batch, float* token, float* feat_or_null, void* stream) {
+    HOPE_ENTER(h, "hope_env_imgenc_forward");
+    HOPE_NEED(h->imgenc.on, "hope_env_imgenc_forward", "the image encoder is off (hope_env_imgenc_enable first)");
+    HOPE_NEED(h->imgenc.loaded, "hope_env_imgenc_forward", "no parameters yet (hope_env_imgenc_load first)");
+    if (!img || !token) return fail(HOPE_EINVAL, "hope_env_imgenc_forward: null img / token");
+    if (batch < 1 || batch > h->imgenc.max_batch)
+        return fail(HOPE_EINVAL, "hope_env_imgenc_forward: batch must be 1 .. max_batch (" + std::to_string(h->imgenc.max_batch) + ")");
+    if (((uintptr_t)img | (uintptr_t)token | (uintptr_t)feat_or_null) & 3)
+        return fail(HOPE_EINVAL, "hope_env_imgenc_forward: misaligned buffer (img, token and feat 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    float* const feat = feat_or_null ? feat_or_null : h->imgenc.feat;
+    if (h->imgenc.act == 0) return imgenc_launch<0>(h, img, batch, token, feat, (hipStream_t)stream);
+    return imgenc_launch<1>(h, img, batch, token, feat, (hipStream_t)stream);
+}
+
+int hope_debug_imgenc_stage(hope_env_t* h, int stage, const uint8_t* img, int64_t batch, float* token, float* feat, void* stream) {
+    HOPE_ENTER(h, "hope_debug_imgenc_stage");
+    HOPE_NEED(h->imgenc.on && h->imgenc.loaded, "hope_debug_imgenc_stage", "the image encoder is off or has no parameters yet");
+    if ((stage != 0 && stage != 1) || !feat || (stage == 0 ? !img : !token) || batch < 1 || batch > h->imgenc.max_batch ||
+        (((uintptr_t)img | (uintptr_t)token | (uintptr_t)feat) & 3))
+        return fail(HOPE_EINVAL, "hope_debug_imgenc_stage: stage 0 (img -> feat) or 1 (feat -> token), non-null 4-byte aligned buffers, batch 1 .. max_batch");
+    HOPE_ON_DEVICE(h);
+    if (h->imgenc.act == 0) return imgenc_launch<0>(h, img, batch, token, feat, (hipStream_t)stream, 1 << stage);
+    return imgenc_launch<1>(h, img, batch, token, feat, (hipStream_t)stream, 1 << stage);
+}
+
+int hope_imgenc_forward_host(const hope_imgenc_params_t* host_params, int act, const uint8_t* img, int64_t batch, float* token, float* feat_or_null) {
+    const int rc = ie_forward_host(host_params, act, img, batch, token, feat_or_null);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_imgenc_forward_host: bad argument (a null parameter, image or token, act not 0 or 1, batch < 1, or img / token / feat not "
+                        "aligned to 4 bytes)");
     return HOPE_OK;
 }
 

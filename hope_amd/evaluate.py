@@ -25,7 +25,7 @@ TOLERANT_TIME = 200
 
 class BatchedEvaluator:
     def __init__(self, env, agent, post_proc_action=True, use_planner=True, seed=0, chooser=None, obs_norm=None, tracker=None,
-                 poll_every=8, actor=None):
+                 poll_every=8, actor=None, img_encoder=None):
         """agent: a hope_amd.agents agent (`act(obs, use_mask, generator, planned, executing)`); post_proc_action: PPO's
         mask-weighted choose_action (eval_utils.py:42-43) instead of the plain sample (:44-45).
         chooser: None, or 'device' -- with post_proc_action the choice, the planner's override and the log-probability are one
@@ -39,11 +39,13 @@ class BatchedEvaluator:
         only every `poll_every` steps instead of every step; steps taken with every slot frozen change nothing.  The stuck
         detector's draws are then counter-based, keyed by `seed` (`stuck_uniforms`), not the generator's.
         actor: None, or 'device' -- the actor's forward in `act` is one fused launch of the library (agent_glue.DeviceActor, set as
-        `agent.device_actor`) instead of the torch module's hundred; the means differ by float32 rounding."""
+        `agent.device_actor`) instead of the torch module's hundred; the means differ by float32 rounding.
+        img_encoder: None, or 'device' -- with actor='device' and an agent whose actor takes an image, the image token comes from the
+        library's image encoder (agent_glue.DeviceImgEncoder) instead of the torch convolutions; ValueError otherwise."""
         self.env, self.agent, self.use_mask = env, agent, bool(post_proc_action)
         self.chooser = G.make_chooser(chooser, env, seed)
         self.obs_norm = G.make_obs_norm(obs_norm, env, agent)
-        self.device_actor = G.make_actor(actor, env, agent)
+        self.device_actor = G.make_actor(actor, env, agent, img_encoder=img_encoder)
         self.tracker = G.make_tracker(tracker, env, seed)
         self.poll_every = max(1, int(poll_every))
         if use_planner == 'device':          # the library's planner: one k_plan launch per step (agent_glue.DeviceRsPlanner)

@@ -305,7 +305,7 @@ def make_ring(ring, env, horizon, keys, seed):
 
 class HopeRollout:
     def __init__(self, env, agent, horizon, use_mask=True, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None,
-                 defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, actor=None):
+                 defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, actor=None, img_encoder=None):
         """defer_rs: step the env with two completion points (HOPE_DEFER_RS): the next policy forward is enqueued as soon as the
         observation is written, the planner reads rs_word / rs_lengths (after ParkingBatch.wait_rs) just before its override --
         the same actions as with the joined step, the forward overlaps the Reeds-Shepp kernels.
@@ -337,9 +337,12 @@ class HopeRollout:
         actor: None -- the actor's inference forward is the torch module (about a hundred launches per step; the agent's fast-policy
         levers apply); 'device' -- `agent.device_actor` becomes an agent_glue.DeviceActor over `env`: one fused launch per step
         (k_policy_forward), the parameters re-packed by one more launch after every update.  The means differ from the torch
-        forward's by float32 rounding.  The forwards inside the agent's update stay torch's."""
+        forward's by float32 rounding.  The forwards inside the agent's update stay torch's.
+        img_encoder: None -- with an image the actor's image token is computed by the torch encoder (MIOpen convolutions); 'device' --
+        the DeviceActor sends the env's uint8 image through an agent_glue.DeviceImgEncoder (two launches: k_imgenc_conv,
+        k_imgenc_head).  Only with actor='device' and an agent whose actor takes an image (ValueError otherwise)."""
         self.chooser = G.make_chooser(chooser, env, seed)
-        self.device_actor = G.make_actor(actor, env, agent)
+        self.device_actor = G.make_actor(actor, env, agent, img_encoder=img_encoder)
         self.obs_norm = G.make_obs_norm(obs_norm, env, agent)
         self._nobs = None                             # device norm: the normalised observation the next act takes
         self.curriculum = None
@@ -489,8 +492,8 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None, actor=None):
-        """ring, actor: as HopeRollout.
+                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None, actor=None, img_encoder=None):
+        """ring, actor, img_encoder: as HopeRollout.
         minibatch: None -- the inner loop of the agent's update is torch code (seven index launches per minibatch, about twenty for the
         loss, as many again in autograd); 'device' -- the agent's `minibatch` becomes an agent_glue.DevicePpoBatch over `env` and this
         trainer's ring (either class): one launch for the gather, two for the loss and its gradients.
@@ -502,7 +505,7 @@ class PPOTrainer(HopeRollout):
             curriculum = dict(curriculum, update_every=0)
         super().__init__(env, agent, horizon, use_mask=True, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring,
-                         actor=actor)
+                         actor=actor, img_encoder=img_encoder)
         self.gae = G.make_gae(gae, env, agent)
         self.minibatch = G.make_ppo_batch(minibatch, env, self.ring)
         if self.minibatch is not None:
@@ -531,8 +534,9 @@ class SACTrainer(HopeRollout):
     sample, no action mask), one SAC update every `update_every` env steps on a uniform batch from the ring."""
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
-                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, sac_update=None, actor=None):
-        """actor: as HopeRollout (the policy's mean once the memory is full; the critics' action token keeps them in torch)
+                 pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, sac_update=None, actor=None,
+                 img_encoder=None):
+        """actor, img_encoder: as HopeRollout (the policy's mean once the memory is full; the critics' action token keeps them in torch)
         chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used
         ring: as HopeRollout; with 'device' the batch is one k_ring_sample launch
         sac_update: None -- the agent's update computes the sample, the Q target and the losses in torch and autograd differentiates
@@ -540,7 +544,7 @@ class SACTrainer(HopeRollout):
         network forwards, autograd through the networks only."""
         super().__init__(env, agent, horizon, use_mask=False, seed=seed, use_planner=use_planner, fresh_scenes=fresh_scenes,
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring,
-                         actor=actor)
+                         actor=actor, img_encoder=img_encoder)
         self.sac_update = G.make_sac_update(sac_update, env)
         if self.sac_update is not None:
             if not hasattr(agent, 'update_block'):

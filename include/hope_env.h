@@ -1050,6 +1050,52 @@ int hope_env_policy_forward(hope_env_t *h, const float *lidar, const float *targ
 int hope_policy_forward_host(const hope_policy_params_t *host_params, int n_tokens, int out_dim, int tanh_out, const float *lidar,
                              const float *target, const float *mask, const float *img_token, int64_t batch, float *out);
 
+/* ---- the image encoder's inference forward (additive to ABI 8) ------------------------------------------------------------------
+ * HopeNet's image token (hope_amd/policy.py _ImgEncoder and re_embed_img; the reference's ImgEncoder / ConvBlock,
+ * src/model/network.py:198-299) for img_shape (3, 64, 64), img_conv_layers [4, 8], k_img_conv 3, img_linear_layers [256], embed
+ * 128, as two kernels: k_imgenc_conv (uint8 images -> the 2 048 features behind the two convolution blocks, a workgroup per image,
+ * VALU) and k_imgenc_head (fc1 -> act -> output_mean -> tanh -> re_embed_img.1 on the f32-input matrix instruction, 32 images per
+ * workgroup).  act: 0 tanh, 1 LeakyReLU(0.01).  Every convolution and Linear output is one float32 fmaf chain from its bias in a
+ * fixed order, everything else float64 rounded once; the order is fixed in hope_amd/csrc/hope_imgenc_core.h, so the host twin below
+ * gives the same bits.  An image's result depends on that image only.  Independent of the policy forward above: enabling one leaves
+ * the other as it was.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  DESIGN.md 5n. */
+#define HOPE_IMGENC_MAX_BATCH 262144
+/* the float32 parameter tensors as torch holds them, row-major and contiguous */
+typedef struct hope_imgenc_params {
+    const float *conv1_w, *conv1_b;      /* embed_img.net.0.layer.0 [4][3][3][3], [4] */
+    const float *short1_w, *short1_b;    /* embed_img.net.0.shortcut.0 [4][3][1][1], [4] */
+    const float *conv2_w, *conv2_b;      /* embed_img.net.1.layer.0 [8][4][3][3], [8] */
+    const float *short2_w, *short2_b;    /* embed_img.net.1.shortcut.0 [8][4][1][1], [8] */
+    const float *fc1_w, *fc1_b;          /* embed_img.net.3 [256][2048], [256] */
+    const float *mean_w, *mean_b;        /* embed_img.output_mean [128][256], [128] */
+    const float *re_w, *re_b;            /* re_embed_img.1 [128][128], [128] */
+} hope_imgenc_params_t;
+/* allocate the packed parameter buffer and the feature buffer [max_batch][2048] float32 (8 KiB per image).  act 0 or 1, 1 <=
+ * max_batch <= HOPE_IMGENC_MAX_BATCH, anything else HOPE_EINVAL.  Enabling again keeps the loaded parameters (the packed
+ * words do not depend on act) and takes the new act; a larger max_batch reallocates the feature buffer (host-synchronous). */
+int hope_env_imgenc_enable(hope_env_t *h, int act, int max_batch);
+/* free both.  Host-synchronous (calls in flight use them). */
+int hope_env_imgenc_disable(hope_env_t *h);
+/* p: a HOST struct of DEVICE pointers, each aligned to 4 bytes.  k_imgenc_pack copies the tensors into the handle's buffer (the
+ * convolutions as they are, the three Linear weights [k][out]): one launch on `stream`, no host synchronisation; the tensors must
+ * stay unchanged until it has run.  HOPE_ESTATE before the enable; HOPE_EINVAL for a NULL struct or a NULL or misaligned tensor
+ * (nothing is launched, the buffer keeps what it had). */
+int hope_env_imgenc_load(hope_env_t *h, const hope_imgenc_params_t *p, void *stream);
+/* img [batch][3][64][64] uint8, token [batch][128] float32, feat NULL or [batch][2048] float32 (the features, for tests that
+ * localise a difference; NULL: they stay in the handle's buffer): DEVICE memory, contiguous, aligned to 4 bytes.  Two launches on
+ * `stream`, no host synchronisation; calls share the handle's feature buffer, so they belong on one stream.  HOPE_ESTATE before the
+ * enable or before the first load; HOPE_EINVAL for a NULL or misaligned pointer or a batch outside 1 .. max_batch; on any error
+ * nothing is launched and nothing written. */
+int hope_env_imgenc_forward(hope_env_t *h, const uint8_t *img, int64_t batch, float *token, float *feat_or_null, void *stream);
+/* one of the two kernels alone, for timing (tools/img_encoder_bench.py): stage 0 k_imgenc_conv (img -> feat; token unused), stage 1
+ * k_imgenc_head (feat -> token; img unused).  feat is required.  Checks and errors as hope_env_imgenc_forward. */
+int hope_debug_imgenc_stage(hope_env_t *h, int stage, const uint8_t *img, int64_t batch, float *token, float *feat, void *stream);
+/* The same over HOST arrays and a struct of HOST pointers: pure host code from the same source, no handle, no device; bit-equal
+ * to the kernels.  No upper bound on batch.  HOPE_EINVAL for a NULL pointer (feat_or_null may be NULL), an act that is not 0 or 1,
+ * batch < 1, or img / token / feat not aligned to 4 bytes. */
+int hope_imgenc_forward_host(const hope_imgenc_params_t *host_params, int act, const uint8_t *img, int64_t batch, float *token,
+                             float *feat_or_null);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
