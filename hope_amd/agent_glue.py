@@ -1086,6 +1086,123 @@ def make_actor(kind, env, agent, img_encoder=None):
     return agent.device_actor
 
 
+class DeviceCritics:
+    """The no-gradient forward of up to four critics of one shape over the library's fused kernel (include/hope_env.h "the critics'
+    inference forward"; rule: csrc/hope_critic_core.h), so that it can stand in as `agent.device_critics`: `crit(nobs)` (PPO critics:
+    HopeNets with one linear output) or `crit(nobs, action)` (SacCritics) returns a list of [B, 1] float32 tensors holding what
+    `net(nobs)` / `net(nobs, action)` returns for each net, from ONE launch (k_critic_forward on a grid of tiles x nets) instead of a
+    hundred per net.  which: the indices into `nets` to evaluate, in the order of the result (default: all).  Every Linear is the
+    float32 fmaf chain of the matrix cores, the rest float64 rounded once, so the result differs from torch's float32 forward by
+    rounding only.  Net i lives in slot i of the handle.  A slot is re-packed (one more launch, k_critic_pack) when its net changed:
+    the key, kept per slot, is the parameters' storage and the sum of their version counters, which in-place optimiser steps,
+    `_soft_update` and load_state_dict all advance; an unchanged net costs no launch (`packs[i]` counts the loads of net i).  With an
+    image each net's own encoder (convolutions, re_embed_img) runs in torch and its token goes in ready-made; `nobs['img_token']`
+    [len(which), B, 128], when the caller already has the tokens, is taken instead.  Inputs longer than `chunk` rows (default: the
+    library's largest batch) go through in pieces.  On an env without the library (CPU tensors; tests/fake_env.OracleEnv) the same
+    forward runs on the host through hope_critic_forward_host, a net at a time: the rule is one source for both.  ValueError for a
+    net of another configuration, or nets of different shapes."""
+
+    def __init__(self, env, nets):
+        nets = list(nets)
+        if not 1 <= len(nets) <= L.CRITIC_SLOTS:
+            raise ValueError(f'DeviceCritics takes 1 .. {L.CRITIC_SLOTS} nets, not {len(nets)}')
+        shapes = [L.critic_shape(n) for n in nets]        # before any state changes
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError(f'DeviceCritics: the nets must share one shape (has_img, has_action), got {shapes}')
+        self.shape = shapes[0]
+        self.env, self.nets = env, nets
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'critic_forward')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'critic_forward')
+        self.packs = [0] * len(nets)
+        self._keys, self._params, self._held = [None] * len(nets), [None] * len(nets), [None] * len(nets)
+        self._max = 0
+        self.chunk = L.POLICY_MAX_BATCH
+
+    def _net_key(self, i):
+        ps = list(self.nets[i].parameters())
+        return tuple(p.data_ptr() for p in ps), sum(p._version for p in ps)
+
+    def _load(self, i):
+        if self.on_device:
+            self.env.critic_load(i, self.nets[i])
+            self.env._critic_owner[i] = self
+        else:
+            self._params[i], self._held[i] = L.critic_params('hope_critic_forward_host', self.nets[i], self.device)
+        self.packs[i] += 1
+
+    def _token(self, i, img):
+        net = L.critic_net(self.nets[i])
+        if img.dtype == torch.uint8:                      # as HopeNet.tokens
+            img = img.to(torch.float32) * (1.0 / 255.0)
+        return net.re_embed_img(net.embed_img(img)).to(torch.float32)
+
+    @torch.no_grad()
+    def __call__(self, nobs, action=None, which=None):
+        which = list(range(len(self.nets))) if which is None else [int(i) for i in which]
+        has_img, has_action = self.shape
+        if has_action != int(action is not None):
+            raise ValueError('DeviceCritics: SacCritics take an action, critic HopeNets take none')
+        f32 = lambda x: x.detach().to(torch.float32).contiguous()  # noqa: E731
+        lidar, target, mask = f32(nobs['lidar']), f32(nobs['target']), f32(nobs['action_mask'])
+        act = f32(action) if has_action else None
+        tokens = nobs.get('img_token') if has_img else None   # [len(which), B, 128], when the caller already has them
+        b, n = int(lidar.shape[0]), len(which)
+        c = min(b, int(self.chunk))
+        if self.on_device:                                # the handle holds ONE shape: take it back if other critics had it
+            want = (len(self.nets),) + self.shape
+            if c > self._max or self.env._critic_shape != want:
+                self._max = max(self._max, c)
+                self.env.enable_critics(*want, max_batch=self._max)
+        for i in which:
+            key = self._net_key(i)
+            if key != self._keys[i] or (self.on_device and self.env._critic_owner.get(i) is not self):
+                self._load(i)
+                self._keys[i] = key
+        res = torch.empty((n, b), dtype=torch.float32, device=self.device)
+        for at in range(0, b, c):
+            m = min(c, b - at)
+            rows = slice(at, at + m)
+            tok = None
+            if has_img:
+                tok = f32(tokens[:, rows]) if tokens is not None else torch.stack([self._token(i, nobs['img'][rows]) for i in which]).contiguous()
+            a = act[rows] if has_action else None
+            if self.on_device:
+                r = self.env.critic_forward(which, lidar[rows], target[rows], mask[rows], tok, a, out=res if m == b else None)
+                if m != b:
+                    res[:, rows] = r
+                continue
+            name = 'hope_critic_forward_host'
+            arg = partial(L.tensor_arg, name, dtype=torch.float32, device=self.device)
+            for j, i in enumerate(which):
+                out = torch.zeros((m,), dtype=torch.float32)
+                L.check(self._lib.hope_critic_forward_host(C.byref(self._params[i]), has_img, has_action, arg('lidar', lidar[rows], shape=(m, L.LIDAR_NUM)),
+                                                           arg('target', target[rows], shape=(m, L.TARGET_DIM)), arg('action_mask', mask[rows], shape=(m, L.N_ACTION)),
+                                                           arg('img_token', None if tok is None else tok[j], shape=(m, 128), optional=True),
+                                                           arg('action', a, shape=(m, 2), optional=True), m, arg('out', out, shape=(m,))), name)
+                res[j, rows] = out
+        return [res[j].unsqueeze(1) for j in range(n)]
+
+
+def make_critics(kind, env, agent):
+    """the `critics` argument of rollouts, trainers and evaluators: None (today's torch forwards), or 'device' -- a DeviceCritics over
+    `env` and the agent's no-gradient critics, set as `agent.device_critics`: a BatchedSAC's (critic_target1, critic_target2), a
+    BatchedPPO's (critic, critic_target).  -> the DeviceCritics or None."""
+    if kind is None:
+        return None
+    if kind != 'device':
+        raise ValueError(f"critics must be None or 'device', not {kind!r}")
+    if hasattr(agent, 'critic_target1'):
+        nets = (agent.critic_target1, agent.critic_target2)
+    elif hasattr(agent, 'critic_target'):
+        nets = (agent.critic, agent.critic_target)
+    else:
+        raise ValueError(f"critics='device' needs a BatchedSAC or a BatchedPPO, not {type(agent).__name__}")
+    agent.device_critics = DeviceCritics(env, nets)
+    return agent.device_critics
+
+
 class RolloutStorage:
     """Device-resident [N, T] ring of transitions: the batched stand-in for ReplayMemory (src/model/replay_memory.py)
     as both agents use it -- PPO reads everything in time order (get_items(arange), ppo_agent.py:241), SAC samples

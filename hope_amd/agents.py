@@ -204,20 +204,29 @@ class BatchedPPO(_AgentCommon):
         """GAE block of PPO.update (:255-273).  obs: normalised observations {k: [N,T,...]}, last_obs {k: [N,...]}
         (the observation after the newest transition), reward / done [N,T].  Returns (adv [N,T], v_target [N,T]).
         With `self.gae` set the three critic forwards stay here and everything after them is its call; on the device the results
-        are then persistent tensors of the env, valid until the next call."""
+        are then persistent tensors of the env, valid until the next call.  With `self.device_critics` set (off by default) the three
+        forwards are its two calls: (critic, critic_target) on the block, critic on last_obs."""
         n, t = reward.shape
         flat = {k: v.reshape((n * t,) + v.shape[2:]) for k, v in obs.items()}
 
         def run(net, x):
             m = next(iter(x.values())).shape[0]
             return torch.cat([net({k: v[i:i + chunk] for k, v in x.items()}) for i in range(0, m, chunk)]).squeeze(1)
-        value = run(self.critic, flat).view(n, t)
-        v_last = run(self.critic, last_obs)
+        dc = getattr(self, 'device_critics', None)       # an agent_glue.DeviceCritics over (critic, critic_target) (make_critics)
+        if dc is not None:                               # the three forwards as two launches of the library's fused kernel
+            value, target_value = (v.view(n, t) for v in dc(flat))
+            v_last = dc(last_obs, which=(0,))[0].squeeze(1)
+        else:
+            value = run(self.critic, flat).view(n, t)
+            v_last = run(self.critic, last_obs)
+            target_value = None
         if self.gae is not None:
-            return self.gae(reward, done, value, v_last, run(self.critic_target, flat).view(n, t), self.gamma, self.lam, normalize=self.adv_norm)
+            if target_value is None:
+                target_value = run(self.critic_target, flat).view(n, t)
+            return self.gae(reward, done, value, v_last, target_value, self.gamma, self.lam, normalize=self.adv_norm)
         next_value = torch.cat([value[:, 1:], v_last.unsqueeze(1)], dim=1)
         adv, _ = G.batched_gae(reward, value, next_value, done, self.gamma, self.lam)
-        v_target = adv + run(self.critic_target, flat).view(n, t)
+        v_target = adv + (target_value if target_value is not None else run(self.critic_target, flat).view(n, t))
         if self.adv_norm:
             m, s = _global_mean_std(adv)
             adv = (adv - m) / (s + 1e-5)
@@ -312,7 +321,8 @@ class BatchedSAC(_AgentCommon):
         with torch.no_grad():
             na, nlp = self._sample_action(nst, None if noise is None else noise[0])
             nlp = nlp.sum(-1, keepdim=True)
-            q_t = torch.min(self.critic_target1(nst, na), self.critic_target2(nst, na))
+            dc = getattr(self, 'device_critics', None)   # an agent_glue.DeviceCritics over the two targets (make_critics): one launch
+            q_t = torch.min(*dc(nst, na)) if dc is not None else torch.min(self.critic_target1(nst, na), self.critic_target2(nst, na))
             q_target = reward + (1 - done) * self.gamma * (q_t - alpha * nlp)
         q1_loss = F.mse_loss(self.critic1(st, action), q_target)
         q2_loss = F.mse_loss(self.critic2(st, action), q_target)
@@ -354,7 +364,8 @@ class BatchedSAC(_AgentCommon):
             raw = self.actor(nst)
             eps = torch.randn_like(raw) if noise is None else noise[0]
             na, nlp = blk.sample(raw, self.log_std, eps)
-            qt1, qt2 = self.critic_target1(nst, na), self.critic_target2(nst, na)
+            dc = getattr(self, 'device_critics', None)   # an agent_glue.DeviceCritics over the two targets (make_critics): one launch
+            qt1, qt2 = dc(nst, na) if dc is not None else (self.critic_target1(nst, na), self.critic_target2(nst, na))
         q1, q2 = self.critic1(st, action), self.critic2(st, action)
         _, g_q1, g_q2, q_losses = blk.critic(q1, q2, qt1, qt2, nlp, reward, done, self.log_alpha, self.gamma)
         self.critic_opt1.zero_grad(set_to_none=True)

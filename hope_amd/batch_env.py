@@ -84,6 +84,8 @@ class ParkingBatch:
         self._sac_out = {}                            # (call, B) -> the outputs of sac_sample / sac_critic / sac_seed / sac_policy
         self._policy_shape, self._policy_out, self._policy_held = None, {}, None   # enable_policy's shape, B -> out, the loaded net's tensors
         self._policy_owner = None                     # the agent_glue.DeviceActor whose parameters the handle holds (one set per handle)
+        self._critic_shape, self._critic_out = None, {}            # enable_critics' (n_slots, has_img, has_action), (n, B) -> out
+        self._critic_held, self._critic_owner = {}, {}             # slot -> the loaded net's tensors / the agent_glue.DeviceCritics that loaded it
         self._imgenc_act, self._imgenc_max, self._imgenc_out, self._imgenc_held = None, 0, {}, None   # enable_img_encoder's act and room, B -> (token, features)
         self._imgenc_owner = None                     # the agent_glue.DeviceImgEncoder whose parameters the handle holds
         self.pool_size = self.n_dlp_cases = None
@@ -833,6 +835,61 @@ class ParkingBatch:
             if out is None:
                 out = self._policy_out[b] = torch.zeros((b, od), dtype=torch.float32, device=self.device)
         L.check(self.lib.hope_env_policy_forward(self.h, *ins, b, arg('out', out, shape=(b, od)), self._stream()), 'hope_env_policy_forward')
+        return out
+
+    # -- the critics' inference forward on the device (hope_env.h; rule: csrc/hope_critic_core.h) ----------------------
+    def enable_critics(self, n_slots=2, has_img=False, has_action=False, max_batch=None):
+        """the no-gradient forward of up to `n_slots` (1 .. 4) critic nets of one shape over one set of inputs as one fused kernel
+        (k_critic_forward) over parameter slots that k_critic_pack fills.  has_img: the nets take a ready-made image token; has_action:
+        they are SacCritics (a 2-wide action token); max_batch: the largest batch (default: the env's scenes).  The same n_slots and
+        shape again keeps the loaded slots; anything else drops them.  Independent of enable_policy.  Off by default."""
+        shape = (int(n_slots), int(bool(has_img)), int(bool(has_action)))
+        if not 1 <= shape[0] <= L.CRITIC_SLOTS:
+            raise ValueError(f'enable_critics: n_slots must be 1 .. {L.CRITIC_SLOTS}, not {n_slots}')
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_critic_enable(self.h, *shape, int(self.n if max_batch is None else max_batch)), 'hope_env_critic_enable')
+        if shape != self._critic_shape:
+            self._critic_shape, self._critic_out, self._critic_held, self._critic_owner = shape, {}, {}, {}
+        return self
+
+    def disable_critics(self):
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.hope_env_critic_disable(self.h), 'hope_env_critic_disable')
+        self._critic_shape, self._critic_out, self._critic_held, self._critic_owner = None, {}, {}, {}
+        return self
+
+    def critic_load(self, slot, net):
+        """pack the parameters of `net` (a critic policy.HopeNet or a policy.SacCritic of the enabled shape, float32 on this device)
+        into slot `slot`: one launch on the current stream, no host synchronisation; the net's tensors are held until the slot's next
+        load.  ValueError for a net of another configuration (nothing changes)."""
+        shape = L.critic_shape(net)
+        if self._critic_shape is None:
+            raise L.HopeError("hope_env_critic_load: the critics' forward is off (enable_critics first)")
+        if shape != self._critic_shape[1:]:
+            raise ValueError(f'critic_load: the net is (has_img, has_action) = {shape}, the handle was enabled for {self._critic_shape[1:]}')
+        p, keep = L.critic_params('hope_env_critic_load', net, self.device)
+        L.check(self.lib.hope_env_critic_load(self.h, int(slot), C.byref(p), self._stream()), 'hope_env_critic_load')
+        self._critic_held[int(slot)] = keep
+        self._critic_owner.pop(int(slot), None)
+        return self
+
+    def critic_forward(self, slots, lidar, target, mask, img_token=None, action=None, out=None):
+        """slots: the n slots to evaluate, in the order of the result's rows; lidar [B, 120], target [B, 5], mask [B, 42], img_token
+        [n, B, 128] (has_img; token i for slots[i]) or None, action [B, 2] (has_action) or None: float32 contiguous -> out [n, B], a
+        persistent tensor per (n, B) (overwritten by the next call with that n and B) unless `out` is given.  One launch on the current
+        stream, no host synchronisation."""
+        arg = partial(L.tensor_arg, 'hope_env_critic_forward', dtype=torch.float32, device=self.device)
+        sl = [int(s) for s in slots]
+        n = len(sl)
+        b = int(lidar.shape[0]) if hasattr(lidar, 'shape') and len(lidar.shape) == 2 else None
+        ins = [arg('lidar', lidar, shape=(b, L.LIDAR_NUM)), arg('target', target, shape=(b, L.TARGET_DIM)), arg('mask', mask, shape=(b, L.N_ACTION)),
+               arg('img_token', img_token, shape=(n, b, 128), optional=True), arg('action', action, shape=(b, 2), optional=True)]
+        if out is None:
+            out = self._critic_out.get((n, b))
+            if out is None:
+                out = self._critic_out[(n, b)] = torch.zeros((n, b), dtype=torch.float32, device=self.device)
+        L.check(self.lib.hope_env_critic_forward(self.h, (C.c_int * max(n, 1))(*sl), n, *ins, b, arg('out', out, shape=(n, b)), self._stream()),
+                'hope_env_critic_forward')
         return out
 
     # -- the image encoder's inference forward on the device (hope_env.h; rule: csrc/hope_imgenc_core.h) ----------------

@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward, the image encoder).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward, the image encoder, the critics' forward).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -242,6 +242,10 @@ struct hope_env {
     // the image encoder (hope_imgenc_kernel.h): packed = the 14 tensors in the kernels' layout (hope_imgenc_core.h IE_OFF_*), written by
     // k_imgenc_pack on the caller's stream; feat = the features between the two kernels, [max_batch][2048]; loaded: as for the policy
     struct ImgEnc { bool on = false, loaded = false; int act = 0, max_batch = 0; float* packed = nullptr; float* feat = nullptr; } imgenc;
+    // the critics' fused forward (hope_critic_kernel.h): packed = n_slots parameter sets, each in the forward's layout (hope_critic_core.h
+    // cc_layout), slot s written by k_critic_pack on the caller's stream; loaded[s]: a hope_env_critic_load of slot s has been enqueued
+    // since the enable
+    struct Critics { bool on = false, loaded[HOPE_CRITIC_SLOTS] = {}; int n_slots = 0, has_img = 0, has_action = 0, max_batch = 0; float* packed = nullptr; } critics;
     // HOPE_DEFER_RS: the search streams of the last step have not been joined into the caller's stream (ev_chain1_done, ev_search0_done)
     bool rs_pending = false;
 };
@@ -262,4 +266,5 @@ void sac_free(hope_env_t* h);
 // hope_policy.hip
 void policy_free(hope_env_t* h);
 void imgenc_free(hope_env_t* h);
+void critics_free(hope_env_t* h);
 }  // namespace hope

@@ -1,7 +1,8 @@
 // hope_policy.hip -- the policy's inference forward of the C ABI (include/hope_env.h "the policy's inference forward"): the packed
 // parameter buffer of the handle, k_policy_pack / k_policy_forward (hope_policy_kernel.h) and the host twin (hope_policy_core.h);
 // and the image encoder's ("the image encoder's inference forward"): k_imgenc_pack / k_imgenc_conv / k_imgenc_head
-// (hope_imgenc_kernel.h) and its twin (hope_imgenc_core.h).  The two features share no state.
+// (hope_imgenc_kernel.h) and its twin (hope_imgenc_core.h); and the critics' ("the critics' inference forward"): the handle's parameter
+// slots, k_critic_pack / k_critic_forward (hope_critic_kernel.h) and their twin (hope_critic_core.h).  The three features share no state.
 // Shares nothing with the other features but the handle (hope_handle.h); its kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include "hope_handle.h"
 #include "hope_policy_kernel.h"
 #include "hope_imgenc_kernel.h"
+#include "hope_critic_kernel.h"
 
 using namespace hope;
 
@@ -26,6 +28,27 @@ void hope::imgenc_free(hope_env_t* h) {
     if (h->imgenc.packed) hipFree(h->imgenc.packed);
     if (h->imgenc.feat) hipFree(h->imgenc.feat);
     h->imgenc = hope_env::ImgEnc{};
+}
+
+static_assert(sizeof(hope_critic_params_t) == CC_NPARAM * sizeof(const float*), "hope_critic_params_t is CC_NPARAM pointers, in cc_layout's order");
+
+void hope::critics_free(hope_env_t* h) {
+    if (h->critics.packed) hipFree(h->critics.packed);
+    h->critics = hope_env::Critics{};
+}
+
+template <int T>
+static int critic_launch(hope_env_t* h, const CcLayout& L, const CkSlots& slots, int n, const float* lidar, const float* target, const float* mask,
+                         const float* img, const float* action, int batch, float* out, hipStream_t st) {
+    static bool lds_set[64] = {};                              // per device: the kernel's dynamic LDS is above the default limit
+    if (h->device >= 0 && h->device < 64 && !lds_set[h->device]) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_critic_forward<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ck_lds_bytes(T)));
+        lds_set[h->device] = true;
+    }
+    hipLaunchKernelGGL(k_critic_forward<T>, dim3((unsigned)((batch + PK_TILE - 1) / PK_TILE), (unsigned)n), dim3(PK_THREADS), ck_lds_bytes(T), st,
+                       (const float*)h->critics.packed, L, slots, h->critics.has_img, h->critics.has_action, lidar, target, mask, img, action, (long long)batch, out);
+    HIPCHK(hipGetLastError());
+    return HOPE_OK;
 }
 
 template <int ACT>
@@ -146,6 +169,115 @@ int hope_policy_forward_host(const hope_policy_params_t* host_params, int n_toke
     if (rc != HOPE_OK)
         return fail(rc, "hope_policy_forward_host: bad argument (a null parameter, input or output, n_tokens not 3 or 4, out_dim not 1 or 2, tanh_out not 0 or 1, "
                         "an image token that does not go with n_tokens, or batch < 1)");
+    return HOPE_OK;
+}
+
+int hope_env_critic_enable(hope_env_t* h, int n_slots, int has_img, int has_action, int max_batch) {
+    HOPE_ENTER(h, "hope_env_critic_enable");
+    if (n_slots < 1 || n_slots > HOPE_CRITIC_SLOTS || !cc_shape_ok(has_img, has_action))
+        return fail(HOPE_EINVAL, "hope_env_critic_enable: n_slots must be 1 .. " + std::to_string(HOPE_CRITIC_SLOTS) + ", has_img and has_action 0 or 1");
+    if (max_batch < 1 || max_batch > HOPE_POLICY_MAX_BATCH)
+        return fail(HOPE_EINVAL, "hope_env_critic_enable: max_batch must be 1 .. " + std::to_string(HOPE_POLICY_MAX_BATCH));
+    hope_env::Critics& c = h->critics;
+    if (c.on && c.n_slots == n_slots && c.has_img == has_img && c.has_action == has_action) {
+        if (max_batch > c.max_batch) c.max_batch = max_batch;
+        return HOPE_OK;
+    }
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());                            // calls in flight read the buffer that another shape replaces
+    critics_free(h);
+    const size_t bytes = (size_t)n_slots * cc_layout(has_img, has_action).total * sizeof(float);
+    hipError_t e_ = hipMalloc((void**)&c.packed, bytes);
+    if (e_ != hipSuccess) {
+        c.packed = nullptr;
+        return fail(HOPE_ENOMEM, std::string("hope_env_critic_enable: ") + hipGetErrorString(e_));
+    }
+    e_ = hipMemset(c.packed, 0, bytes);
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    if (e_ != hipSuccess) {
+        critics_free(h);
+        return fail(HOPE_EHIP, std::string("hope_env_critic_enable: ") + hipGetErrorString(e_));
+    }
+    c.n_slots = n_slots; c.has_img = has_img; c.has_action = has_action; c.max_batch = max_batch;
+    c.on = true;
+    return HOPE_OK;
+}
+
+int hope_env_critic_disable(hope_env_t* h) {
+    HOPE_ENTER(h, "hope_env_critic_disable");
+    HOPE_ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    critics_free(h);
+    return HOPE_OK;
+}
+
+int hope_env_critic_load(hope_env_t* h, int slot, const hope_critic_params_t* p, void* stream) {
+    HOPE_ENTER(h, "hope_env_critic_load");
+    hope_env::Critics& c = h->critics;
+    HOPE_NEED(c.on, "hope_env_critic_load", "the critics' forward is off (hope_env_critic_enable first)");
+    if (slot < 0 || slot >= c.n_slots) return fail(HOPE_EINVAL, "hope_env_critic_load: slot must be 0 .. n_slots - 1 (" + std::to_string(c.n_slots - 1) + ")");
+    if (!p) return fail(HOPE_EINVAL, "hope_env_critic_load: null parameter struct");
+    CkPtrs ptrs;
+    uintptr_t bits = 0;
+    for (int i = 0; i < CC_NPARAM; ++i) {
+        ptrs.t[i] = ((const float* const*)p)[i];
+        if (i >= PC_NPARAM && !c.has_action) {
+            if (ptrs.t[i]) return fail(HOPE_EINVAL, "hope_env_critic_load: has_action is 0: the action tensors must be NULL");
+            continue;
+        }
+        if (!ptrs.t[i]) return fail(HOPE_EINVAL, "hope_env_critic_load: null tensor (field " + std::to_string(i) + " of hope_critic_params_t)");
+        bits |= (uintptr_t)ptrs.t[i];
+    }
+    if (bits & 3) return fail(HOPE_EINVAL, "hope_env_critic_load: misaligned tensor (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const CcLayout L = cc_layout(c.has_img, c.has_action);
+    hipLaunchKernelGGL(k_critic_pack, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ptrs, L, c.packed, slot);
+    HIPCHK(hipGetLastError());
+    c.loaded[slot] = true;
+    return HOPE_OK;
+}
+
+int hope_env_critic_forward(hope_env_t* h, const int* slots, int n, const float* lidar, const float* target, const float* mask, const float* img_token,
+                            const float* action, int batch, float* out, void* stream) {
+    HOPE_ENTER(h, "hope_env_critic_forward");
+    const hope_env::Critics& c = h->critics;
+    HOPE_NEED(c.on, "hope_env_critic_forward", "the critics' forward is off (hope_env_critic_enable first)");
+    if (!slots || n < 1 || n > c.n_slots) return fail(HOPE_EINVAL, "hope_env_critic_forward: slots must name 1 .. n_slots (" + std::to_string(c.n_slots) + ") slots");
+    CkSlots sl = {};
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= c.n_slots)
+            return fail(HOPE_EINVAL, "hope_env_critic_forward: slot " + std::to_string(slots[i]) + " is outside 0 .. n_slots - 1 (" + std::to_string(c.n_slots - 1) + ")");
+        for (int j = 0; j < i; ++j)
+            if (slots[j] == slots[i]) return fail(HOPE_EINVAL, "hope_env_critic_forward: slot " + std::to_string(slots[i]) + " is named twice");
+        sl.s[i] = slots[i];
+    }
+    for (int i = 0; i < n; ++i)
+        HOPE_NEED(c.loaded[sl.s[i]], "hope_env_critic_forward", "a slot has no parameters yet (hope_env_critic_load first)");
+    if (!lidar || !target || !mask || !out) return fail(HOPE_EINVAL, "hope_env_critic_forward: null lidar / target / mask / out");
+    if ((c.has_img != 0) != (img_token != nullptr))
+        return fail(HOPE_EINVAL, c.has_img ? "hope_env_critic_forward: has_img is 1: the image token is missing" : "hope_env_critic_forward: has_img is 0: there is no image token");
+    if ((c.has_action != 0) != (action != nullptr))
+        return fail(HOPE_EINVAL, c.has_action ? "hope_env_critic_forward: has_action is 1: the action is missing" : "hope_env_critic_forward: has_action is 0: there is no action");
+    if (batch < 1 || batch > c.max_batch)
+        return fail(HOPE_EINVAL, "hope_env_critic_forward: batch must be 1 .. max_batch (" + std::to_string(c.max_batch) + ")");
+    if (((uintptr_t)lidar | (uintptr_t)target | (uintptr_t)mask | (uintptr_t)img_token | (uintptr_t)action | (uintptr_t)out) & 3)
+        return fail(HOPE_EINVAL, "hope_env_critic_forward: misaligned buffer (every tensor 4 bytes)");
+    HOPE_ON_DEVICE(h);
+    const CcLayout L = cc_layout(c.has_img, c.has_action);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (cc_tokens(c.has_img, c.has_action)) {
+        case 3: return critic_launch<3>(h, L, sl, n, lidar, target, mask, img_token, action, batch, out, st);
+        case 4: return critic_launch<4>(h, L, sl, n, lidar, target, mask, img_token, action, batch, out, st);
+        default: return critic_launch<5>(h, L, sl, n, lidar, target, mask, img_token, action, batch, out, st);
+    }
+}
+
+int hope_critic_forward_host(const hope_critic_params_t* host_params, int has_img, int has_action, const float* lidar, const float* target, const float* mask,
+                             const float* img_token, const float* action, int64_t batch, float* out) {
+    const int rc = cc_forward_host(host_params, has_img, has_action, lidar, target, mask, img_token, action, batch, out);
+    if (rc != HOPE_OK)
+        return fail(rc, "hope_critic_forward_host: bad argument (a null parameter, input or output, has_img / has_action not 0 or 1, an image token, action or "
+                        "action tensors that do not go with them, or batch < 1)");
     return HOPE_OK;
 }
 

@@ -492,8 +492,12 @@ class PPOTrainer(HopeRollout):
     the batched `len(memory) % batch_size == 0`) run PPO.update and clear."""
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
-                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None, actor=None, img_encoder=None):
+                 curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None, actor=None, img_encoder=None,
+                 critics=None):
         """ring, actor, img_encoder: as HopeRollout.
+        critics: None -- the three no-gradient critic forwards of the agent's advantage block are torch modules (a hundred launches
+        each); 'device' -- `agent.device_critics` becomes an agent_glue.DeviceCritics over `env`, the critic and its target: two launches
+        of the library's fused kernel (the critics' image encoders stay in torch).
         minibatch: None -- the inner loop of the agent's update is torch code (seven index launches per minibatch, about twenty for the
         loss, as many again in autograd); 'device' -- the agent's `minibatch` becomes an agent_glue.DevicePpoBatch over `env` and this
         trainer's ring (either class): one launch for the gather, two for the loss and its gradients.
@@ -507,6 +511,7 @@ class PPOTrainer(HopeRollout):
                          pool_refresher=pool_refresher, defer_rs=defer_rs, curriculum=curriculum, chooser=chooser, obs_norm=obs_norm, ring=ring,
                          actor=actor, img_encoder=img_encoder)
         self.gae = G.make_gae(gae, env, agent)
+        self.device_critics = G.make_critics(critics, env, agent)
         self.minibatch = G.make_ppo_batch(minibatch, env, self.ring)
         if self.minibatch is not None:
             if not hasattr(agent, 'minibatch'):
@@ -535,8 +540,11 @@ class SACTrainer(HopeRollout):
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
                  pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, sac_update=None, actor=None,
-                 img_encoder=None):
-        """actor, img_encoder: as HopeRollout (the policy's mean once the memory is full; the critics' action token keeps them in torch)
+                 img_encoder=None, critics=None):
+        """actor, img_encoder: as HopeRollout (the policy's mean once the memory is full)
+        critics: None -- the update's two target-critic forwards are torch modules; 'device' -- `agent.device_critics` becomes an
+        agent_glue.DeviceCritics over `env` and the two targets: one launch of the library's fused kernel for both (their image encoders
+        and `_soft_update` stay in torch; the two critics that autograd runs through do too).
         chooser: accepted for symmetry with PPOTrainer; SAC samples without the mask (use_mask=False), where it is not used
         ring: as HopeRollout; with 'device' the batch is one k_ring_sample launch
         sac_update: None -- the agent's update computes the sample, the Q target and the losses in torch and autograd differentiates
@@ -550,6 +558,7 @@ class SACTrainer(HopeRollout):
             if not hasattr(agent, 'update_block'):
                 raise ValueError("sac_update='device' needs an agent with an update block (BatchedSAC)")
             agent.update_block = self.sac_update
+        self.device_critics = G.make_critics(critics, env, agent)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

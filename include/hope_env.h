@@ -1096,6 +1096,60 @@ int hope_debug_imgenc_stage(hope_env_t *h, int stage, const uint8_t *img, int64_
 int hope_imgenc_forward_host(const hope_imgenc_params_t *host_params, int act, const uint8_t *img, int64_t batch, float *token,
                              float *feat_or_null);
 
+/* ---- the critics' inference forward (additive to ABI 8) -------------------------------------------------------------------------
+ * The no-gradient forward of up to HOPE_CRITIC_SLOTS critic HopeNets (hope_amd/policy.py: a HopeNet with one linear output, or a
+ * SacCritic; the reference's SACCriticAdapter, src/model/agent/sac_agent.py:15-30) over ONE set of inputs as ONE kernel,
+ * k_critic_forward: the policy forward's network with T = 3 + has_img + has_action tokens in HopeNet.tokens' order -- lidar, target,
+ * mask, [the image token, ready-made, one per net: each critic has its own encoder, which stays with the caller], [action [batch][2]
+ * through embed_action] -- a (T x 128) -> 128 -> 1 head and no output tanh.  The handle keeps n_slots packed parameter sets of one
+ * shape, so that SAC's two target critics, or PPO's critic and its target, are evaluated by one launch without re-packing in turn.
+ * The arithmetic is the policy forward's rule extended to the action token (hope_amd/csrc/hope_critic_core.h), so the host twin below
+ * gives the same bits, and without an action token the bits of hope_policy_forward_host(..., out_dim 1, tanh_out 0).  A row's result
+ * depends on that row and that net only.  Independent of the policy forward and the image encoder above: enabling one leaves the
+ * others as they were.  Off until enabled; with it off no launch, pointer or output of any other entry point differs.  DESIGN.md 5o. */
+#define HOPE_CRITIC_SLOTS 4
+/* the float32 parameter tensors as torch holds them, [out][in] row-major and contiguous: hope_policy_params_t's fields (head2 is
+ * [1][128], [1]), then the action embedding, all four NULL exactly when has_action is 0 */
+typedef struct hope_critic_params {
+    const float *lidar_w1, *lidar_b1, *lidar_w2, *lidar_b2;
+    const float *target_w1, *target_b1, *target_w2, *target_b2;
+    const float *mask_w1, *mask_b1, *mask_w2, *mask_b2;
+    const float *ln1_g, *ln1_b;
+    const float *qkv_w;
+    const float *out_w, *out_b;
+    const float *ln2_g, *ln2_b;
+    const float *ff1_w, *ff1_b, *ff2_w, *ff2_b;
+    const float *head1_w, *head1_b;                              /* net.output.0 [128][T * 128], [128] */
+    const float *head2_w, *head2_b;                              /* net.output.2 [1][128], [1] */
+    const float *action_w1, *action_b1, *action_w2, *action_b2;  /* embed_action.0 [128][2], [128]; embed_action.2 [128][128], [128] */
+} hope_critic_params_t;
+/* allocate n_slots packed parameter sets of this shape.  1 <= n_slots <= HOPE_CRITIC_SLOTS, has_img and has_action 0 or 1, 1 <=
+ * max_batch <= HOPE_POLICY_MAX_BATCH, anything else HOPE_EINVAL.  Enabling again with the same n_slots and shape keeps the loaded
+ * slots and takes the larger max_batch; anything else drops them (loads must follow).  Host-synchronous. */
+int hope_env_critic_enable(hope_env_t *h, int n_slots, int has_img, int has_action, int max_batch);
+/* free them.  Host-synchronous (calls in flight use them). */
+int hope_env_critic_disable(hope_env_t *h);
+/* p: a HOST struct of DEVICE pointers, each aligned to 4 bytes.  k_critic_pack copies the tensors into slot `slot`, in the layout that
+ * the forward loads coalesced: one launch on `stream`, no host synchronisation; the tensors must stay unchanged until it has run.
+ * HOPE_ESTATE before the enable; HOPE_EINVAL for a slot outside 0 .. n_slots - 1, a NULL struct, a NULL or misaligned tensor, or
+ * action tensors that do not go with has_action (nothing is launched, the slot keeps what it had). */
+int hope_env_critic_load(hope_env_t *h, int slot, const hope_critic_params_t *p, void *stream);
+/* slots: HOST const int[n], 1 <= n <= n_slots, each loaded, no slot twice.  lidar [batch][120], target [batch][5], mask [batch][42],
+ * img_token [n][batch][128] (has_img; token i for net slots[i]) or NULL, action [batch][2] (has_action) or NULL, out [n][batch]:
+ * DEVICE memory, float32, contiguous, aligned to 4 bytes.  One launch on `stream` (a grid of ceil(batch / 32) x n workgroups), no
+ * host synchronisation.  HOPE_ESTATE before the enable or before the load of a slot that is used; HOPE_EINVAL for a NULL `slots`, an
+ * n, a slot or a batch out of range, a slot named twice, a NULL or misaligned pointer, or an image token or action that does not
+ * go with the shape; on any error nothing is launched. */
+int hope_env_critic_forward(hope_env_t *h, const int *slots, int n, const float *lidar, const float *target, const float *mask,
+                            const float *img_token, const float *action, int batch, float *out, void *stream);
+/* One net over HOST arrays and a struct of HOST pointers: pure host code from the same source, no handle, no device; bit-equal to
+ * the kernel.  img_token [batch][128] or NULL, action [batch][2] or NULL, out [batch].  No alignment requirements, no upper bound
+ * on batch.  HOPE_EINVAL for a NULL pointer, has_img / has_action not 0 or 1, an image token, action or action tensors that do not
+ * go with them, batch < 1. */
+int hope_critic_forward_host(const hope_critic_params_t *host_params, int has_img, int has_action, const float *lidar,
+                             const float *target, const float *mask, const float *img_token, const float *action, int64_t batch,
+                             float *out);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
