@@ -57,6 +57,10 @@ def main():
                     help="also run a short SAC and a short PPO loop with the updates' no-gradient critic forwards on the device "
                          "(critics='device': the two target critics, or the critic and its target, in one k_critic_forward launch instead of "
                          'two torch modules, k_critic_pack of a slot after its net changed)')
+    ap.add_argument('--device-optimizer', action='store_true',
+                    help="also run a short SAC and a short PPO loop with the optimiser block on the device (optimizer='device': every "
+                         'Adam step and every soft update of a target one k_optim launch per 64 tensors instead of torch\'s chain of '
+                         'multi-tensor launches; the torch optimisers keep the state)')
     ap.add_argument('--device-img-encoder', action='store_true',
                     help="also run a short PPO loop of an agent WITH the image token on an env that renders the bird's-eye image, the "
                          "actor's forward and its image encoder on the device (actor='device', img_encoder='device': k_imgenc_conv and "
@@ -221,6 +225,23 @@ def main():
             if rank == 0:
                 print(f'  device critics: 16 {type(tr).__name__[:3]} steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
                       f'{tr.device_critics.packs} parameter packs per slot')
+    if args.device_optimizer:
+        from hope_amd import agents as A
+        from hope_amd.rollout import PPOTrainer, SACTrainer
+        common = dict(seed=rank, use_planner='device' if args.device_planner else True, obs_norm='device' if args.device_norm else None,
+                      ring='device' if args.device_ring else None, critics='device' if args.device_critics else None, optimizer='device')
+        for tr in (SACTrainer(env, A.BatchedSAC(device=dev, use_img=False, batch_size=min(args.scenes, 4096)), horizon=4, update_every=2,
+                              sac_update='device' if args.device_sac_update else None, **common),
+                   PPOTrainer(env, A.BatchedPPO(device=dev, use_img=False, mini_batch=min(args.scenes, 16384), mini_epoch=1), horizon=4,
+                              gae='device' if args.device_gae else None, **common)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(16):
+                tr.step()
+            torch.cuda.synchronize()
+            if rank == 0:
+                print(f'  device optimizer: 16 {type(tr).__name__[:3]} steps ({tr.updates} updates) in {(time.perf_counter() - t0) * 1e3:.1f} ms, '
+                      f'{ {k: o.steps for k, o in tr.optimizers.items()} } optimiser steps, {tr.agent.soft_update.calls} soft updates')
     if args.device_img_encoder:
         from hope_amd import agents as A
         from hope_amd.rollout import PPOTrainer

@@ -1,5 +1,6 @@
 """ctypes binding of include/hope_env.h.  Fails loudly: there is no CPU fallback."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -32,6 +33,7 @@ SAC_MAX_BATCH = 1 << 20
 POLICY_MAX_BATCH = 1 << 20
 IMGENC_MAX_BATCH = 1 << 18
 CRITIC_SLOTS = 4
+OPTIM_F32, OPTIM_F64, OPTIM_MAX_GROUPS, OPTIM_CAP, OPTIM_CHUNK = 0, 1, 4, 64, 1024
 EVAL_STATE_WORDS = 10                                          # planes of the evaluation tracker's state block
 BUCKET_UNLABELLED = 255
 # hope_env_step_plan: words ahead of the chains / of a chain's scene ids, flag bits, kernel numbers
@@ -132,6 +134,17 @@ IMGENC_FIELDS = (('conv1_w', 'embed_img.net.0.layer.0.weight', (4, 3, 3, 3)), ('
 class ImgEncParams(C.Structure):
     """hope_imgenc_params_t: the addresses of the 14 float32 tensors of a HopeNet's image encoder; `imgenc_params` builds one"""
     _fields_ = [(k, C.c_void_p) for k, _, _ in IMGENC_FIELDS]
+
+
+class OptimEntry(C.Structure):
+    """hope_optim_entry_t: one tensor of an optimiser call; `optim_entries` builds a table of them"""
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('numel', C.c_int64), ('group', C.c_int32),
+                ('dtype', C.c_int32)]
+
+
+class OptimGroup(C.Structure):
+    """hope_optim_group_t: a parameter group's step; `optim_group` computes one from lr, betas, eps and the step count"""
+    _fields_ = [('c1', C.c_double), ('b2', C.c_double), ('c2', C.c_double), ('step_size', C.c_double), ('bc2s', C.c_double), ('eps', C.c_double)]
 
 
 # the prototypes of include/hope_env.h, one entry per exported call: name -> (return type, parameter types).  The parameter kinds:
@@ -276,6 +289,10 @@ PROTOTYPES = {
     'hope_env_imgenc_forward': (I, [P, P, I64, P, P, P]),
     'hope_debug_imgenc_stage': (I, [P, I, P, I64, P, P, P]),
     'hope_imgenc_forward_host': (I, [C.POINTER(ImgEncParams), I, P, I64, P, P]),
+    'hope_env_optim_adam': (I, [P, C.POINTER(OptimEntry), I, C.POINTER(OptimGroup), I, P]),
+    'hope_env_optim_polyak': (I, [P, C.POINTER(OptimEntry), I, D, P]),
+    'hope_optim_adam_host': (I, [C.POINTER(OptimEntry), I, C.POINTER(OptimGroup), I]),
+    'hope_optim_polyak_host': (I, [C.POINTER(OptimEntry), I, D]),
     'hope_env_num_scenes': (I, [P]),
     'hope_env_max_obstacles': (I, [P]),
     'hope_env_device_arch': (S, [P]),
@@ -525,3 +542,67 @@ def imgenc_params(call, module, device):
         setattr(p, field, tensor_arg(call, key, t, torch.float32, shape, device).value)
         keep.append(t)
     return p, keep
+
+
+def optim_group(lr, betas, eps, t):
+    """the hope_optim_group_t of a parameter group at its step t >= 1: the bias corrections folded into the step, as doubles"""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return OptimGroup(1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t), float(eps))
+
+
+def optim_entries(params, grads, ms=None, vs=None, groups=None, call='hope_env_optim_adam', device=None):
+    """the table of hope_optim_entry_t over the tensors params[i], grads[i], ms[i], vs[i] (Adam), or over targets and current tensors
+    (Polyak: optim_entries(targets, currents)) -> (pointer to the table, n, what must stay alive: the table's memory and the tensors).
+    groups[i]: the group index of entry i (default 0).  ValueError, naming the entry, for a tensor that is not contiguous, not float32
+    / float64, on another device than `device` (default: that of params[0]), or whose partners differ in shape or dtype -- tensor_arg's
+    conditions, asked here in one pass because a call has a hundred entries.  The table holds addresses only: keep the tensors alive
+    and in place until the call that takes it has been enqueued."""
+    import torch
+    cols = [list(params), list(grads)] + ([list(ms), list(vs)] if ms is not None else [])
+    names = ('p', 'g', 'm', 'v') if ms is not None else ('target', 'current')
+    n = len(cols[0])
+    if n < 1 or any(len(c) != n for c in cols):
+        raise ValueError(f'{call}: the lists must have one length >= 1, got {[len(c) for c in cols]}')
+    first = cols[0][0]
+    device = torch.device(device) if device is not None else first.device if torch.is_tensor(first) else None
+    f32, f64, strided, is_tensor = torch.float32, torch.float64, torch.strided, torch.is_tensor
+    table = np.zeros(n, dtype=_OPTIM_ENTRY)
+    try:
+        for k, col in zip('pgmv', cols):
+            table[k] = [x.data_ptr() for x in col]
+        heads = [(p.dtype, p.shape) for p in cols[0]]
+        ok = all(dt is f32 or dt is f64 for dt, _ in heads) and \
+            all(x.dtype is h[0] and x.shape == h[1] and x.device == device and x.layout is strided and x.is_contiguous() for col in cols for x, h in zip(col, heads))
+    except (AttributeError, RuntimeError):           # no tensor, or one without storage (sparse)
+        ok = False
+    if not ok:
+        _optim_entries_refuse(call, names, cols, device)
+    table['numel'] = [p.numel() for p in cols[0]]
+    table['dtype'] = [OPTIM_F64 if dt is f64 else OPTIM_F32 for dt, _ in heads]
+    if groups is not None:
+        table['group'] = groups
+    return table.ctypes.data_as(C.POINTER(OptimEntry)), n, (table, cols)
+
+
+_OPTIM_ENTRY = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('numel', np.int64), ('group', np.int32),
+                         ('dtype', np.int32)])
+assert _OPTIM_ENTRY.itemsize == C.sizeof(OptimEntry)
+
+
+def _optim_entries_refuse(call, names, cols, device):
+    """the ValueError of optim_entries: the first entry that does not pass, and why"""
+    import torch
+    for i, p in enumerate(cols[0]):
+        if not torch.is_tensor(p) or p.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f'{call}: entry {i}: {names[0]} must be a float32 or float64 tensor, got {getattr(p, "dtype", type(p).__name__)}')
+        for name, col in zip(names, cols):
+            x = col[i]
+            if not torch.is_tensor(x) or x.layout != torch.strided:
+                raise ValueError(f'{call}: entry {i}: {name} must be a dense tensor, got {type(x).__name__ if not torch.is_tensor(x) else x.layout}')
+            if x.dtype != p.dtype or x.shape != p.shape:
+                raise ValueError(f'{call}: entry {i}: {name} is {x.dtype} {list(x.shape)}, {names[0]} is {p.dtype} {list(p.shape)}')
+            if x.device != device:
+                raise ValueError(f'{call}: entry {i}: {name} is on {x.device}, the call on {device}')
+            if not x.is_contiguous():
+                raise ValueError(f'{call}: entry {i}: {name} is not contiguous')
+    raise ValueError(f'{call}: the tensors do not go together')

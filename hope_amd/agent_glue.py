@@ -12,6 +12,9 @@ Plain torch tensor code (any device); no custom kernels -- these are a few eleme
                                                      their host twins)
   DeviceSacUpdate      <-> SACAgent.update between its forwards   src/model/agent/sac_agent.py:250-337 (hope_env_sac_* or their host twins)
   DeviceActor          <-> the actor's inference forward   src/model/network.py:34-187 (hope_env_policy_forward or its host twin)
+  DeviceAdam /
+  DevicePolyak         <-> the optimiser steps and AgentBase._soft_update   src/model/agent/sac_agent.py:293-331, ppo_agent.py:337-340,
+                                                     agent_base.py:64 (hope_env_optim_adam / _polyak or their host twins)
   RolloutStorage       <-> ReplayMemory              src/model/replay_memory.py:6-49
 """
 import ctypes as C
@@ -1201,6 +1204,196 @@ def make_critics(kind, env, agent):
         raise ValueError(f"critics='device' needs a BatchedSAC or a BatchedPPO, not {type(agent).__name__}")
     agent.device_critics = DeviceCritics(env, nets)
     return agent.device_critics
+
+
+_ADAM_REFUSED = ('amsgrad', 'maximize', 'capturable', 'differentiable', 'fused')
+
+
+class DeviceAdam:
+    """A `torch.optim.Adam` whose `step()` is the library's optimiser block (include/hope_env.h "the optimiser block"; rule:
+    csrc/hope_optim_core.h): ONE launch of k_optim per 64 tensors instead of torch's chain of multi-tensor launches.  The wrapped
+    optimiser stays the truth and is kept as `.optimizer`: the step reads lr, betas and eps from its param_groups at every call (a
+    scheduler works), creates a parameter's state on first use exactly as torch does (`step` a CPU float32 scalar tensor, `exp_avg`
+    and `exp_avg_sq` from zeros_like), advances `step` by one, skips a parameter whose grad is None, and updates the same parameter
+    and state tensors in place -- so state_dict / load_state_dict / checkpoints go through `.optimizer` unchanged and a run can switch
+    between the two at any step.  After the launch the version counters of the parameters and the state tensors advance by one, so
+    that DeviceActor / DeviceCritics / DeviceImgEncoder re-pack as after a torch step.  The arithmetic is the library's one rule, not
+    torch's bits: see DESIGN 5p for the measured distance.  ValueError naming the option for amsgrad, weight_decay != 0, maximize,
+    capturable, differentiable, fused, a tensor lr, a sparse gradient, or an optimiser that is not Adam.  On an env without the
+    library (CPU tensors; tests/fake_env.OracleEnv) the same step runs on the host through hope_optim_adam_host."""
+
+    def __init__(self, env, optimizer):
+        if type(optimizer) is not torch.optim.Adam:
+            raise ValueError(f'optimizer: DeviceAdam wraps a torch.optim.Adam, not {type(optimizer).__name__}')
+        self.env, self.optimizer = env, optimizer
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'optim_adam')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'optim_adam')
+        self.steps = 0                                    # calls that moved at least one tensor
+        self._check()
+
+    # the wrapped optimiser's own surface
+    param_groups = property(lambda self: self.optimizer.param_groups)
+    state = property(lambda self: self.optimizer.state)
+
+    def state_dict(self):
+        return self.optimizer.state_dict()
+
+    def load_state_dict(self, state_dict):
+        return self.optimizer.load_state_dict(state_dict)
+
+    def zero_grad(self, set_to_none=True):
+        return self.optimizer.zero_grad(set_to_none=set_to_none)
+
+    def add_param_group(self, param_group):
+        return self.optimizer.add_param_group(param_group)
+
+    def _check(self):
+        for gi, group in enumerate(self.optimizer.param_groups):
+            for k in _ADAM_REFUSED:
+                if group.get(k):
+                    raise ValueError(f'{k}: DeviceAdam does not take {k}=True (param group {gi})')
+            if group.get('weight_decay', 0) != 0:
+                raise ValueError(f"weight_decay: DeviceAdam does not take weight_decay != 0 (param group {gi})")
+            if torch.is_tensor(group['lr']):
+                raise ValueError(f'lr: DeviceAdam does not take a tensor lr (param group {gi})')
+            if any(p.grad is not None and p.grad.is_sparse for p in group['params']):
+                raise ValueError(f'sparse gradient: DeviceAdam does not take sparse gradients (param group {gi})')
+
+    def _gather(self):
+        """what torch's _init_group does -> [(p, grad, exp_avg, exp_avg_sq, hyper key)] of the parameters that move; their `step`
+        has advanced.  `_check` comes first (step_optimizers): nothing here refuses."""
+        jobs = []
+        for group in self.optimizer.param_groups:
+            lr, betas, eps = float(group['lr']), group['betas'], float(group['eps'])
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                st = self.optimizer.state[p]
+                if len(st) == 0:
+                    st['step'] = torch.tensor(0.0, dtype=torch.float32)
+                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                jobs.append((p, p.grad, st['exp_avg'], st['exp_avg_sq'], (lr, float(betas[0]), float(betas[1]), eps), st['step']))
+        if jobs:                                          # only now, with nothing left to refuse, the counters move
+            torch._foreach_add_([j[5] for j in jobs], 1)
+        return [(p, g, m, v, hp + (int(step.item()),)) for p, g, m, v, hp, step in jobs]
+
+    @staticmethod
+    def _run(env, lib, jobs):
+        """jobs as ONE call per four distinct groups, in order"""
+        at = 0
+        while at < len(jobs):
+            keys, end = [], at
+            while end < len(jobs) and (jobs[end][4] in keys or len(keys) < L.OPTIM_MAX_GROUPS):
+                if jobs[end][4] not in keys:
+                    keys.append(jobs[end][4])
+                end += 1
+            part = jobs[at:end]
+            groups = [L.optim_group(k[0], (k[1], k[2]), k[3], k[4]) for k in keys]
+            cols = [[j[c] for j in part] for c in range(4)]
+            cols[1] = [g.contiguous() for g in cols[1]]   # (a gradient that autograd left strided: a copy; the others are updated in place)
+            group_of = [keys.index(j[4]) for j in part]
+            if lib is None:
+                env.optim_adam(*cols, groups, group_of)
+            else:
+                table, n, _keep = L.optim_entries(*cols, group_of, 'hope_optim_adam_host')
+                L.check(lib.hope_optim_adam_host(table, n, (L.OptimGroup * len(groups))(*groups), len(groups)), 'hope_optim_adam_host')
+            at = end
+        torch.autograd.graph.increment_version([x for j in jobs for x in (j[0], j[2], j[3])])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError('closure: DeviceAdam does not take a closure')
+        step_optimizers(self)
+
+
+def step_optimizers(*opts):
+    """`.step()` of every optimiser, in order.  DeviceAdams over one env run as ONE call of the library (one group per param group,
+    at most four to a call, else several calls); anything else -- torch optimisers, or a mix -- is each `.step()` in turn."""
+    if opts and all(isinstance(o, DeviceAdam) for o in opts) and all(o.env is opts[0].env for o in opts):
+        with torch.no_grad():
+            for o in opts:                                # every refusal before anything moves
+                o._check()
+            jobs = [o._gather() for o in opts]
+            flat = [j for js in jobs for j in js]
+            if flat:
+                DeviceAdam._run(opts[0].env, None if opts[0].on_device else opts[0]._lib, flat)
+            for o, js in zip(opts, jobs):
+                o.steps += bool(js)
+        return
+    for o in opts:
+        o.step()
+
+
+class DevicePolyak:
+    """agents._soft_update over the library's optimiser block: `polyak(pairs, tau)` with pairs = [(target_module, current_module), ...]
+    is target <- (1 - tau) * target + tau * current for every parameter of every pair, as ONE call (one launch per 64 tensors)
+    instead of two multi-tensor launches per pair.  The targets' version counters advance by one, so a DeviceCritics over them
+    re-packs as after `_soft_update`.  On an env without the library the same runs on the host through hope_optim_polyak_host."""
+
+    def __init__(self, env):
+        self.env = env
+        self.device = torch.device(env.device)
+        self.on_device = hasattr(env, 'optim_polyak')
+        if not self.on_device:
+            self._lib = _host_library(self.device, 'optim_polyak')
+        self.calls = 0
+
+    @torch.no_grad()
+    def polyak(self, pairs, tau):
+        targets, currents = [], []
+        for t, c in pairs:
+            tp, cp = list(t.parameters()), list(c.parameters())
+            if len(tp) != len(cp):
+                raise ValueError(f'DevicePolyak: a target with {len(tp)} parameters against a net with {len(cp)}')
+            targets += tp
+            currents += cp
+        if self.on_device:
+            self.env.optim_polyak(targets, currents, tau)
+        else:
+            table, n, _keep = L.optim_entries(targets, currents, call='hope_optim_polyak_host')
+            L.check(self._lib.hope_optim_polyak_host(table, n, float(tau)), 'hope_optim_polyak_host')
+        torch.autograd.graph.increment_version(targets)
+        self.calls += 1
+
+    __call__ = polyak
+
+
+_OPTIMIZER_NAMES = ('actor_opt', 'critic_opt', 'critic_opt1', 'critic_opt2', 'alpha_opt')
+
+
+def make_optimizers(kind, env, agent):
+    """the trainers' `optimizer` argument: None (today's path: torch.optim.Adam.step and agents._soft_update), or 'device' -- every
+    optimiser of the agent (actor_opt, critic_opt / critic_opt1, critic_opt2, alpha_opt: its float64 scalar is one entry, one launch)
+    becomes a DeviceAdam over `env` around the torch optimiser it was, and `agent.soft_update` a DevicePolyak's `polyak`.
+    -> {name: DeviceAdam} or None."""
+    if kind is None:
+        return None
+    if kind != 'device':
+        raise ValueError(f"optimizer must be None or 'device', not {kind!r}")
+    made = {}
+    for name in _OPTIMIZER_NAMES:
+        opt = getattr(agent, name, None)
+        if opt is None:
+            continue
+        if not isinstance(opt, DeviceAdam):
+            opt = DeviceAdam(env, opt)
+            setattr(agent, name, opt)
+        made[name] = opt
+    if not made:
+        raise ValueError(f"optimizer='device' needs an agent with Adam optimisers (BatchedPPO, BatchedSAC), not {type(agent).__name__}")
+    agent.soft_update = DevicePolyak(env)
+    return made
+
+
+def torch_optimizers(agent):
+    """the agent's optimisers as torch objects, in _OPTIMIZER_NAMES' order: what a checkpoint's 'optimizer' tuple holds, whichever path
+    steps them"""
+    opts = [getattr(agent, name, None) for name in _OPTIMIZER_NAMES]
+    return tuple(getattr(o, 'optimizer', o) for o in opts if o is not None)
 
 
 class RolloutStorage:

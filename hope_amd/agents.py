@@ -267,9 +267,12 @@ class BatchedPPO(_AgentCommon):
                     self.critic_opt.zero_grad(set_to_none=True)
                     (actor_loss + critic_loss).backward()         # disjoint parameter sets: same grads as two backward()s
                 self.allreduce_bytes += D.allreduce_gradients(params)
-                self.actor_opt.step()
-                self.critic_opt.step()
-            _soft_update(self.critic_target, self.critic, self.tau)                                   # :338
+                G.step_optimizers(self.actor_opt, self.critic_opt)
+            soft = getattr(self, 'soft_update', None)     # an agent_glue.DevicePolyak (make_optimizers)
+            if soft is not None:
+                soft([(self.critic_target, self.critic)], self.tau)
+            else:
+                _soft_update(self.critic_target, self.critic, self.tau)                               # :338
         self.last_losses = (float(actor_loss.detach()), float(critic_loss.detach()))
         return self.last_losses
 
@@ -310,6 +313,14 @@ class BatchedSAC(_AgentCommon):
         a = torch.clamp(mean + log_std.exp() * eps, -1, 1)
         return a, P.gaussian_log_prob(mean, log_std, a)
 
+    def _soft_updates(self):
+        soft = getattr(self, 'soft_update', None)         # an agent_glue.DevicePolyak (make_optimizers): both targets in one call
+        if soft is not None:
+            soft([(self.critic_target1, self.critic1), (self.critic_target2, self.critic2)], self.tau)
+        else:
+            _soft_update(self.critic_target1, self.critic1, self.tau)
+            _soft_update(self.critic_target2, self.critic2, self.tau)
+
     def update(self, batch, noise=None):
         """one SAC update (:263-337) on a batch {'obs', 'next_obs' (normalised dicts), 'action', 'reward', 'done'}.
         `noise` = (eps for the next-state action, eps for the policy-loss action), tests only."""
@@ -331,8 +342,7 @@ class BatchedSAC(_AgentCommon):
         (q1_loss + q2_loss).backward()
         cparams = list(self.critic1.parameters()) + list(self.critic2.parameters())
         self.allreduce_bytes += D.allreduce_gradients(cparams)
-        self.critic_opt1.step()
-        self.critic_opt2.step()
+        G.step_optimizers(self.critic_opt1, self.critic_opt2)
         for p in cparams:
             p.requires_grad_(False)
         a_, lp = self._sample_action(st, None if noise is None else noise[1])
@@ -350,8 +360,7 @@ class BatchedSAC(_AgentCommon):
             alpha_loss.backward()
             self.allreduce_bytes += D.allreduce_gradients([self.log_alpha])
             self.alpha_opt.step()
-        _soft_update(self.critic_target1, self.critic1, self.tau)
-        _soft_update(self.critic_target2, self.critic2, self.tau)
+        self._soft_updates()
         return float(actor_loss.detach()), float(q1_loss.detach())
 
     def _update_with_block(self, batch, noise=None):
@@ -372,8 +381,7 @@ class BatchedSAC(_AgentCommon):
         self.critic_opt2.zero_grad(set_to_none=True)
         torch.autograd.backward((q1, q2), (g_q1.view(q1.shape), g_q2.view(q2.shape)))
         self.allreduce_bytes += D.allreduce_gradients(list(self.critic1.parameters()) + list(self.critic2.parameters()))
-        self.critic_opt1.step()
-        self.critic_opt2.step()
+        G.step_optimizers(self.critic_opt1, self.critic_opt2)
         raw = self.actor(st)
         eps = torch.randn_like(raw) if noise is None else noise[1]
         a = blk.sample(raw, self.log_std, eps)[0].detach().requires_grad_()           # a leaf: autograd stops at the sampled action
@@ -390,6 +398,5 @@ class BatchedSAC(_AgentCommon):
             self.log_alpha.grad = g_log_alpha
             self.allreduce_bytes += D.allreduce_gradients([self.log_alpha])
             self.alpha_opt.step()
-        _soft_update(self.critic_target1, self.critic1, self.tau)
-        _soft_update(self.critic_target2, self.critic2, self.tau)
+        self._soft_updates()
         return float(p_losses[0]), float(q_losses[0])

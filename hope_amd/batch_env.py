@@ -892,6 +892,23 @@ class ParkingBatch:
                 'hope_env_critic_forward')
         return out
 
+    # -- the optimiser block on the device (hope_env.h; rule: csrc/hope_optim_core.h) ---------------------------------
+    def optim_adam(self, params, grads, exp_avgs, exp_avg_sqs, groups, group_of=None):
+        """one Adam step over the tensors params[i] with gradients grads[i] and state exp_avgs[i], exp_avg_sqs[i] (float32 or float64,
+        contiguous, on this device), updated in place.  groups: 1 .. 4 `_lib.OptimGroup`s (`_lib.optim_group`); group_of[i]: the
+        group of entry i (default 0).  ceil(len / 64) launches of k_optim on the current stream, no host synchronisation; nothing
+        is kept.  ValueError for tensors that do not go together (`_lib.optim_entries`)."""
+        table, n, _keep = L.optim_entries(params, grads, exp_avgs, exp_avg_sqs, group_of, 'hope_env_optim_adam', self.device)
+        garr = (L.OptimGroup * max(len(groups), 1))(*groups)
+        L.check(self.lib.hope_env_optim_adam(self.h, table, n, garr, len(groups), self._stream()), 'hope_env_optim_adam')
+        return self
+
+    def optim_polyak(self, targets, currents, tau):
+        """targets[i] <- (1 - tau) * targets[i] + tau * currents[i], in place: the same launches, the same rules."""
+        table, n, _keep = L.optim_entries(targets, currents, call='hope_env_optim_polyak', device=self.device)
+        L.check(self.lib.hope_env_optim_polyak(self.h, table, n, float(tau), self._stream()), 'hope_env_optim_polyak')
+        return self
+
     # -- the image encoder's inference forward on the device (hope_env.h; rule: csrc/hope_imgenc_core.h) ----------------
     def enable_img_encoder(self, act='tanh', max_batch=None):
         """HopeNet's image token (the two convolution blocks, fc1, output_mean, re_embed_img) for the reference configuration as two

@@ -1,7 +1,9 @@
 // hope_agent.hip -- the policy-side features of the C ABI (include/hope_env.h): replay of found Reeds-Shepp paths, masked choice of the
-// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring, PPO's minibatch, SAC's update -- and their host twins.  They share nothing with the
+// action, normalisation of the observations, bookkeeping of an evaluation run, PPO's advantage block, the transition ring, PPO's minibatch, SAC's update, the optimiser block -- and their host twins.  They share nothing with the
 // step path (hope_env.hip) but the handle (hope_handle.h); their kernels are instantiated here and nowhere else.
 #include <hip/hip_runtime.h>
+
+#include <string.h>
 
 #include <string>
 
@@ -14,6 +16,7 @@
 #include "hope_ring_kernel.h"
 #include "hope_ppo_kernel.h"
 #include "hope_sac_kernel.h"
+#include "hope_optim_kernel.h"
 
 using namespace hope;
 
@@ -839,6 +842,77 @@ int hope_sac_policy_host(const float* raw, const float* log_std, const float* ep
     const int rc = su_policy_host(raw, log_std, eps, q1, q2, g_action, log_alpha, target_entropy, batch, g_raw, g_log_std, g_log_alpha, losses);
     if (rc == HOPE_ENOMEM) return fail(rc, "hope_sac_policy_host: out of memory for the chunk partials");
     if (rc != HOPE_OK) return fail(rc, "hope_sac_policy_host: bad argument (a null input or output, batch < 1, or a target_entropy that is not finite)");
+    return HOPE_OK;
+}
+
+}  // extern "C"
+
+// ---- the optimiser block (include/hope_env.h; kernel: hope_optim_kernel.h, rule: hope_optim_core.h) ----
+static int optim_refused(const char* name, int rc, const OpBad& bad) {
+    std::string where = bad.kind == OP_BAD_ENTRY ? "entry " + std::to_string(bad.index) + ": " : bad.kind == OP_BAD_GROUP ? "group " + std::to_string(bad.index) + ": " : "";
+    return fail(rc, std::string(name) + ": " + where + bad.what);
+}
+
+// the checked entries as launches of k_optim<MODE>: OP_CAP entries at a time, each table built on the stack and handed over by value
+template <int MODE>
+static int optim_launch(const hope_optim_entry_t* e, int n, const hope_optim_group_t* g, int n_groups, double tau, hipStream_t st) {
+    OkTable tab;
+    for (int at = 0; at < n; at += OP_CAP) {
+        memset(&tab, 0, sizeof(tab));
+        for (int k = 0; k < n_groups; k++) tab.group[k] = g[k];
+        tab.tau = tau;
+        tab.omt = 1.0 - tau;
+        tab.n = n - at < OP_CAP ? n - at : OP_CAP;
+        uint32_t chunks = 0;
+        for (int i = 0; i < tab.n; i++) {
+            const hope_optim_entry_t& s = e[at + i];
+            OkEntry& d = tab.e[i];
+            d.p = s.p; d.g = s.g;
+            uintptr_t bits = (uintptr_t)s.p | (uintptr_t)s.g;
+            if (MODE == OP_ADAM) { d.m = s.m; d.v = s.v; bits |= (uintptr_t)s.m | (uintptr_t)s.v; }
+            d.numel = (uint32_t)s.numel;
+            d.first = chunks;
+            d.meta = s.dtype == HOPE_OPTIM_F64 ? OK_F64 : (bits & 15) ? 0u : OK_VEC;
+            if (MODE == OP_ADAM) d.meta |= (uint32_t)s.group << 2;
+            chunks += (uint32_t)((s.numel + OP_CHUNK - 1) / OP_CHUNK);       // <= 2^21 + n in all: the call's elements are <= 2^31
+        }
+        hipLaunchKernelGGL(k_optim<MODE>, dim3(chunks), dim3(OK_THREADS), 0, st, tab);
+        HIPCHK(hipGetLastError());
+    }
+    return HOPE_OK;
+}
+
+extern "C" {
+
+int hope_env_optim_adam(hope_env_t* h, const hope_optim_entry_t* entries, int n_entries, const hope_optim_group_t* groups, int n_groups, void* stream) {
+    HOPE_ENTER(h, "hope_env_optim_adam");
+    OpBad bad;
+    const int rc = op_check(OP_ADAM, entries, n_entries, groups, n_groups, 0.0, &bad);
+    if (rc != HOPE_OK) return optim_refused("hope_env_optim_adam", rc, bad);
+    HOPE_ON_DEVICE(h);
+    return optim_launch<OP_ADAM>(entries, n_entries, groups, n_groups, 0.0, (hipStream_t)stream);
+}
+
+int hope_env_optim_polyak(hope_env_t* h, const hope_optim_entry_t* entries, int n_entries, double tau, void* stream) {
+    HOPE_ENTER(h, "hope_env_optim_polyak");
+    OpBad bad;
+    const int rc = op_check(OP_POLYAK, entries, n_entries, nullptr, 0, tau, &bad);
+    if (rc != HOPE_OK) return optim_refused("hope_env_optim_polyak", rc, bad);
+    HOPE_ON_DEVICE(h);
+    return optim_launch<OP_POLYAK>(entries, n_entries, nullptr, 0, tau, (hipStream_t)stream);
+}
+
+int hope_optim_adam_host(const hope_optim_entry_t* entries, int n_entries, const hope_optim_group_t* groups, int n_groups) {
+    OpBad bad;
+    const int rc = op_adam_host(entries, n_entries, groups, n_groups, &bad);
+    if (rc != HOPE_OK) return optim_refused("hope_optim_adam_host", rc, bad);
+    return HOPE_OK;
+}
+
+int hope_optim_polyak_host(const hope_optim_entry_t* entries, int n_entries, double tau) {
+    OpBad bad;
+    const int rc = op_polyak_host(entries, n_entries, tau, &bad);
+    if (rc != HOPE_OK) return optim_refused("hope_optim_polyak_host", rc, bad);
     return HOPE_OK;
 }
 

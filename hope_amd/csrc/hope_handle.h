@@ -1,5 +1,5 @@
 // hope_handle.h -- the handle behind hope_env_t and the opening every hope_env_* entry point shares.  Private to the library's own
-// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update; hope_policy.hip: the fused policy forward, the image encoder, the critics' forward).
+// .hip files (hope_env.hip: create / destroy, step, pool, curriculum, debug; hope_agent.hip: planner, chooser, normalisation, evaluation, advantages, transition ring, PPO's minibatch, SAC's update, the optimiser block; hope_policy.hip: the fused policy forward, the image encoder, the critics' forward).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

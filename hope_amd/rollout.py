@@ -493,8 +493,11 @@ class PPOTrainer(HopeRollout):
 
     def __init__(self, env, agent, horizon=16, seed=0, use_planner=True, fresh_scenes=False, pool_refresher=None, defer_rs=True,
                  curriculum=None, chooser=None, obs_norm=None, gae=None, ring=None, minibatch=None, actor=None, img_encoder=None,
-                 critics=None):
+                 critics=None, optimizer=None):
         """ring, actor, img_encoder: as HopeRollout.
+        optimizer: None -- every optimiser step is torch.optim.Adam.step and the target's soft update agents._soft_update (a chain of
+        multi-tensor launches each); 'device' -- the agent's optimisers become agent_glue.DeviceAdams over `env` around the torch
+        optimisers they were and `agent.soft_update` an agent_glue.DevicePolyak: one launch of the library's k_optim per call.
         critics: None -- the three no-gradient critic forwards of the agent's advantage block are torch modules (a hundred launches
         each); 'device' -- `agent.device_critics` becomes an agent_glue.DeviceCritics over `env`, the critic and its target: two launches
         of the library's fused kernel (the critics' image encoders stay in torch).
@@ -517,6 +520,7 @@ class PPOTrainer(HopeRollout):
             if not hasattr(agent, 'minibatch'):
                 raise ValueError("minibatch='device' needs an agent with a minibatch loop (BatchedPPO)")
             agent.minibatch = self.minibatch
+        self.optimizers = G.make_optimizers(optimizer, env, agent)
         self.updates = 0
 
     def step(self):
@@ -540,8 +544,10 @@ class SACTrainer(HopeRollout):
 
     def __init__(self, env, agent, horizon=8, update_every=10, seed=0, use_planner=True, learn=True, fresh_scenes=False,
                  pool_refresher=None, defer_rs=True, curriculum=None, chooser=None, obs_norm=None, ring=None, sac_update=None, actor=None,
-                 img_encoder=None, critics=None):
+                 img_encoder=None, critics=None, optimizer=None):
         """actor, img_encoder: as HopeRollout (the policy's mean once the memory is full)
+        optimizer: as PPOTrainer: 'device' wraps critic_opt1, critic_opt2, actor_opt and alpha_opt and sends both soft updates through
+        one call.
         critics: None -- the update's two target-critic forwards are torch modules; 'device' -- `agent.device_critics` becomes an
         agent_glue.DeviceCritics over `env` and the two targets: one launch of the library's fused kernel for both (their image encoders
         and `_soft_update` stay in torch; the two critics that autograd runs through do too).
@@ -559,6 +565,7 @@ class SACTrainer(HopeRollout):
                 raise ValueError("sac_update='device' needs an agent with an update block (BatchedSAC)")
             agent.update_block = self.sac_update
         self.device_critics = G.make_critics(critics, env, agent)
+        self.optimizers = G.make_optimizers(optimizer, env, agent)
         self.update_every, self.learn, self.updates = update_every, learn, 0
 
     def step(self):

@@ -1150,6 +1150,58 @@ int hope_critic_forward_host(const hope_critic_params_t *host_params, int has_im
                              const float *target, const float *mask, const float *img_token, const float *action, int64_t batch,
                              float *out);
 
+/* ---- the optimiser block (additive to ABI 8) ----------------------------------------------------------------------------------
+ * What an update does after backward, for many tensors at once: Adam's step (torch.optim.Adam without amsgrad, weight decay or
+ * maximize) and the Polyak average of a target network (agents._soft_update; the reference's AgentBase._soft_update,
+ * src/model/agent/agent_base.py:64).  One kernel, k_optim, in two modes; a launch covers up to HOPE_OPTIM_CAP tensors, a workgroup
+ * HOPE_OPTIM_CHUNK elements of one of them, and the entry table travels as the kernel's argument.  The arithmetic is ONE rule
+ * (hope_amd/csrc/hope_optim_core.h: every operation a double operation, no fused multiply-add, each stored word rounded once), so
+ * the host twins below give the same bits; against torch's own Adam the difference is rounding, measured in DESIGN.md 5p.  The calls
+ * keep no state in the handle: there is nothing to enable, and with them unused no launch, pointer or output of any other entry
+ * point differs. */
+#define HOPE_OPTIM_F32 0
+#define HOPE_OPTIM_F64 1
+#define HOPE_OPTIM_MAX_GROUPS 4
+#define HOPE_OPTIM_CAP 64         /* entries per launch; a call with more becomes several launches, back to back on the stream */
+#define HOPE_OPTIM_CHUNK 1024
+/* one tensor of a call: contiguous, `numel` elements of float32 (HOPE_OPTIM_F32) or float64 (HOPE_OPTIM_F64), every pointer aligned
+ * to its element (16-byte alignment of all of an entry's pointers buys 16-byte accesses, nothing else).  Adam: p the parameter, g its
+ * gradient, m exp_avg, v exp_avg_sq, group the index into the call's groups; p, m and v are updated in place.  Polyak: p the TARGET
+ * tensor, updated in place, g the current net's tensor; m, v and group are not looked at.  No two entries of a call may overlap. */
+typedef struct hope_optim_entry {
+    void *p;
+    const void *g;
+    void *m;
+    void *v;
+    int64_t numel;
+    int32_t group;
+    int32_t dtype;
+} hope_optim_entry_t;
+/* a parameter group's step, from its lr, (beta1, beta2), eps and the step count t >= 1 this call is:
+ * c1 = 1 - beta1, b2 = beta2, c2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2s = sqrt(1 - beta2^t), eps */
+typedef struct hope_optim_group {
+    double c1;
+    double b2;
+    double c2;
+    double step_size;
+    double bc2s;
+    double eps;
+} hope_optim_group_t;
+/* entries: a HOST table of DEVICE pointers, n_entries >= 1; groups: a HOST table, 1 <= n_groups <= HOPE_OPTIM_MAX_GROUPS.  Both are
+ * read before the call returns (nothing is staged: gradients may live elsewhere at the next call).  ceil(n_entries / HOPE_OPTIM_CAP)
+ * launches on `stream`, no host synchronisation.  HOPE_EINVAL, with a text that names the entry or group, nothing launched and
+ * nothing written, for: a NULL table or a NULL pointer in an entry; n_entries < 1, a numel < 1 or more than 2^31 elements in all; a
+ * pointer not aligned to its element; a group index out of range or n_groups outside 1 .. 4; a dtype that is neither value; a
+ * hyper-parameter that is not finite, eps < 0 or bc2s <= 0. */
+int hope_env_optim_adam(hope_env_t *h, const hope_optim_entry_t *entries, int n_entries, const hope_optim_group_t *groups, int n_groups,
+                        void *stream);
+/* target <- (1 - tau) * target + tau * current for every entry.  As above; HOPE_EINVAL also for a tau outside [0, 1]. */
+int hope_env_optim_polyak(hope_env_t *h, const hope_optim_entry_t *entries, int n_entries, double tau, void *stream);
+/* The same over HOST pointers: pure host code from the same source, no handle, no device; bit-equal to the kernel.  The same
+ * refusals. */
+int hope_optim_adam_host(const hope_optim_entry_t *entries, int n_entries, const hope_optim_group_t *groups, int n_groups);
+int hope_optim_polyak_host(const hope_optim_entry_t *entries, int n_entries, double tau);
+
 /* ---- introspection ---------------------------------------------------------------------------- */
 int hope_env_num_scenes(const hope_env_t *h);
 int hope_env_max_obstacles(const hope_env_t *h);
